@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- fitted pixels/s of the NPP-Net optimisation step on MI355X (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line; --full also runs
+and reports everything else (the pre-drawn-pool loop, per-kernel times and roofline, the extras, PSNR, CPU baseline).
 
 Workload (BASELINE.json configs[1], SURVEY.md 8d "c2"): one 512x512 completion image, top-3
 periodicity proposals, 256-wide x 8-layer NPP_Net, bf16 MFMA operands / fp32 accumulate.
@@ -15,12 +18,12 @@ VGG19[0:18] trunk on the 2 * n_p * k patches -> contextual loss -> trunk data-gr
 libnpp_hip.so.  `value` is the loop THAT SAMPLES (round 6): every timed step is CompletionFit.step_full() on the
 reference's own random stream (models/sampler.py:297-354, train.py:164-181: the native MT19937 generator on a
 producer thread, the sampler's device launches one iteration ahead on their own stream), K = --steps iterations
-between barrier + synchronize, repeated for WINDOWS consecutive windows; the line reports the MEDIAN window
+between barrier + synchronize (--full: repeated for WINDOWS consecutive windows; the line reports the MEDIAN window)
 (`ms_per_step` x `steps` = that window; min / max of the windows in `config`).  The image, mask and lattice are
-resident in HBM; nothing is cached between steps.  `config.device_only_rows_per_s` keeps the round-2..5 definition
+resident in HBM; nothing is cached between steps.  `config.device_only_rows_per_s` (--full) keeps the round-2..5 definition
 (sampler outputs of 40 iterations pre-drawn, timed steps cycle through that pool with the exact 50 / 30 / 20 source
 mix).  Rows fitted per second, summed over ranks (each rank fits its own image: weak scaling, no data-path
-collective; one all_gather of the fitted images after the loop).  `mlp_only_step` is the same iteration without
+collective; one all_gather of the fitted images after the loop).  `mlp_only_step` (--full) is the same iteration without
 the patch losses (the round-1 line).
 """
 import argparse
@@ -54,11 +57,22 @@ def parse():
     ap.add_argument("--no-psnr", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the c4 embedder and full-loop extras")
     ap.add_argument("--ksplit", type=int, default=0, help="split-K of the weight-gradient launch; 0 = auto (CUs / tiles)")
-    ap.add_argument("--windows", type=int, default=WINDOWS, help="consecutive --steps windows of the sampling loop whose median is `value` "
-                    "(0: profiling runs -- only the pre-drawn-pool loop is run and reported, marked as such)")
+    ap.add_argument("--windows", type=int, default=None, help="consecutive --steps windows of the sampling loop whose median is `value` "
+                    f"(default 1, {WINDOWS} with --full; 0 with --full: profiling runs -- only the pre-drawn-pool loop is run and reported, "
+                    "marked as such)")
     ap.add_argument("--pool", type=int, default=40, help="pre-drawn sampler outputs the timed steps cycle through (a multiple of 10: the "
                     "sampler's 50 / 30 / 20 % source mix is then held exactly)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run and report everything beside the headline: the pre-drawn-pool loop, "
+                    "per-kernel times and roofline, the extras, PSNR and the CPU baseline (the --no-* switches thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.windows is None:
+        args.windows = WINDOWS if args.full else 1
+    if args.windows < 0 or (args.windows == 0 and not args.full):
+        ap.error("--windows 0 reports the pre-drawn-pool loop, which only --full runs")
+    return args
 
 
 def _dig(d, *keys):
@@ -164,6 +178,19 @@ def cpu_baseline(K, H, patch, n_pix, n_p, k, seconds_target=20.0):
                       f"VGG16 + LPIPS head every 5th) in {n_b * t_b:.1f}s"}
 
 
+def dump_outputs(fit, out_dir):
+    """--dump-outputs: what the timed loop's last iteration left for its caller, as float32 .npy files -- the fitted MLP
+    parameters, the adaptive pixel loss's latents, the prediction of that iteration's rows and its pixel and patch losses
+    (5 MB at the default size)."""
+    os.makedirs(out_dir, exist_ok=True)
+    net = fit.net
+    ws = net._ws_last
+    arrays = {"params": net.params, "latents": net.latents, "pred": ws["pred"][:ws["n_rows"]],
+              "pixel_loss": net.loss_buf, "patch_loss": fit.last_patch_loss}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def dry_run_dist(args, rank, world):
     """NPP_BENCH_DRYRUN=1: the launch / rendezvous / gather skeleton of the N-rank run without a GPU (gloo), for the CPU
     test of the `--gpus N` spawn path (tests/test_bench_spawn.py).  No kernel runs and nothing is measured."""
@@ -242,49 +269,20 @@ def main():
     H, K = args.size, args.K
     img, mask = syn.synthetic_image(H, seed=rank)           # each rank fits its own image
     angles, periods, shifts = syn.synthetic_periodicity(H, K)
-    P = syn.init_params(K, seed=rank)
     # Own image and own initial weights per rank, but the SAME sampler stream (seed 0) everywhere: the patch-source mix of
     # the pool ('same' iterations cost 1.5x a 'val' one) is then identical on every GPU, i.e. per-GPU work is fixed as N
     # grows (weak scaling) instead of the slowest random mix setting the max-over-ranks time.
-    fit = CompletionFit(img, mask, angles, periods, syn.SEED0_FREQS, P, device=dev, N_rand=8192,
-                        ksplit=args.ksplit, seed=0, shifts=shifts)
     if world > 1:
         args.no_extras = True          # the extras (c4 table, end-to-end, ranking, throughput mode) are N = 1 reports
-    net = fit.net
-    patch = fit.patch_size                                     # loaders.py:133-134 -> 96 at 512^2
+    # THE HEADLINE fit (the loop that samples, below): the iteration's geometry is read off it
+    fe = CompletionFit(img, mask, angles, periods, syn.SEED0_FREQS, syn.init_params(K, seed=rank), device=dev, N_rand=8192,
+                       ksplit=args.ksplit, seed=0, shifts=shifts, rng_mode="reference", prefetch=8)
+    patch = fe.patch_size                                      # loaders.py:133-134 -> 96 at 512^2
     assert patch == patch_size_from_period(periods[0])
-    n_pix, n_patch = fit.N_rand, fit.patch_num * patch * patch # patch_num = 2 (arg_config.py:63)
+    n_pix, n_patch = fe.N_rand, fe.patch_num * patch * patch   # patch_num = 2 (arg_config.py:63)
     n_rows = n_pix + n_patch
     bp = ops.pad_rows(n_rows)
-
-    # ---- synthetic inputs, resident in HBM before timing: the sampler's output for `pool` iterations
-    #      (train.py:152-181: sample_patches -> pixel draw), in the reference's RNG order ----
-    # The pool holds the sampler's expected patch-source mix EXACTLY (50 / 30 / 20 % val / train / same, sampler.py:297-354) AND
-    # in an order in which EVERY window of 10 consecutive entries (cyclically) holds 5 val / 3 train / 2 same: draws arrive in the
-    # reference's RNG order, fill per-source quotas and are then dealt into the period-10 pattern below -- so any --steps that is a
-    # multiple of 10 (the driver's 20 included) times the sampler's own mix ('same' iterations cost ~1.2x a 'val' one).
-    quota = {"val": args.pool // 2, "train": (args.pool * 3) // 10, "same": 0}
-    quota["same"] = args.pool - quota["val"] - quota["train"]
-    by_src = {"val": [], "train": [], "same": []}
-    while sum(len(v_) for v_ in by_src.values()) < args.pool:
-        b = fit.sample_batch()
-        if b is not None and len(by_src[b["source"]]) < quota[b["source"]]:   # k == 0 -> the reference skips the iteration (train.py:160-161)
-            assert b["n"] == n_rows and b["bp"] == bp
-            by_src[b["source"]].append(b)
-    pool = []
-    if args.pool % 10 == 0:
-        taken = {s_: 0 for s_ in by_src}
-        for i in range(args.pool):
-            s_ = POOL_PATTERN[i % 10]
-            pool.append(by_src[s_][taken[s_]])
-            taken[s_] += 1
-    else:
-        pool = by_src["val"] + by_src["train"] + by_src["same"]
-    mix = {s_: sum(b["source"] == s_ for b in pool) for s_ in ("val", "train", "same")}
-    ws = net.workspace(bp)
-
-    def step(i):
-        fit.step_from(pool[i % len(pool)])
+    ksplit = fe.net.ksplit
 
     def barrier():
         torch.cuda.synchronize()
@@ -292,45 +290,76 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    for i in range(max(args.warmup, len(pool))):               # every pool entry at least once (allocations, first-call setup)
-        step(i)
-    barrier()
-    # (no cyclic garbage collection inside the timed steps: a generation-2 pass over a process that holds torch + the pool is a
-    #  multi-millisecond host stall, visible in a 20-step region of ~12 ms)
     import gc
-    gc.collect()
-    gc.disable()
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        step(i)
-    barrier()
-    dt = time.perf_counter() - t0
-    gc.enable()
-    per_rank = None
-    if dist is not None:
-        t = torch.tensor([dt], dtype=torch.float64, device=dev)
-        allt = [torch.empty_like(t) for _ in range(world)]
-        dist.all_gather(allt, t)
-        per_rank = [n_rows * args.steps / float(x.item()) for x in allt]       # rows/s of every rank's own loop
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
-    dev_only_ms_per_step = dt / args.steps * 1e3
-    dev_only_value = world * n_rows * args.steps / dt
-    dev_only_per_rank = per_rank
-    mix_timed_dev = {s_: sum(pool[i % len(pool)]["source"] == s_ for i in range(args.steps)) for s_ in ("val", "train", "same")}
+    fit = dev_only_ms_per_step = dev_only_value = dev_only_per_rank = None
+    if args.full:                      # the pre-drawn-pool loop (`config.device_only_*`; --windows 0 reports it as the line)
+        fit = CompletionFit(img, mask, angles, periods, syn.SEED0_FREQS, syn.init_params(K, seed=rank), device=dev, N_rand=8192,
+                            ksplit=args.ksplit, seed=0, shifts=shifts)
+        net = fit.net
+        # ---- synthetic inputs, resident in HBM before timing: the sampler's output for `pool` iterations
+        #      (train.py:152-181: sample_patches -> pixel draw), in the reference's RNG order ----
+        # The pool holds the sampler's expected patch-source mix EXACTLY (50 / 30 / 20 % val / train / same, sampler.py:297-354) AND
+        # in an order in which EVERY window of 10 consecutive entries (cyclically) holds 5 val / 3 train / 2 same: draws arrive in the
+        # reference's RNG order, fill per-source quotas and are then dealt into the period-10 pattern below -- so any --steps that is a
+        # multiple of 10 times the sampler's own mix ('same' iterations cost ~1.2x a 'val' one).
+        quota = {"val": args.pool // 2, "train": (args.pool * 3) // 10, "same": 0}
+        quota["same"] = args.pool - quota["val"] - quota["train"]
+        by_src = {"val": [], "train": [], "same": []}
+        while sum(len(v_) for v_ in by_src.values()) < args.pool:
+            b = fit.sample_batch()
+            if b is not None and len(by_src[b["source"]]) < quota[b["source"]]:   # k == 0 -> the reference skips the iteration (train.py:160-161)
+                assert b["n"] == n_rows and b["bp"] == bp
+                by_src[b["source"]].append(b)
+        pool = []
+        if args.pool % 10 == 0:
+            taken = {s_: 0 for s_ in by_src}
+            for i in range(args.pool):
+                s_ = POOL_PATTERN[i % 10]
+                pool.append(by_src[s_][taken[s_]])
+                taken[s_] += 1
+        else:
+            pool = by_src["val"] + by_src["train"] + by_src["same"]
+        mix = {s_: sum(b["source"] == s_ for b in pool) for s_ in ("val", "train", "same")}
+        ws = net.workspace(bp)
+
+        def step(i):
+            fit.step_from(pool[i % len(pool)])
+
+        for i in range(max(args.warmup, len(pool))):               # every pool entry at least once (allocations, first-call setup)
+            step(i)
+        barrier()
+        # (no cyclic garbage collection inside the timed steps: a generation-2 pass over a process that holds torch + the pool is a
+        #  multi-millisecond host stall, visible in a 20-step region of ~12 ms)
+        gc.collect()
+        gc.disable()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            step(i)
+        barrier()
+        dt = time.perf_counter() - t0
+        gc.enable()
+        per_rank = None
+        if dist is not None:
+            t = torch.tensor([dt], dtype=torch.float64, device=dev)
+            allt = [torch.empty_like(t) for _ in range(world)]
+            dist.all_gather(allt, t)
+            per_rank = [n_rows * args.steps / float(x.item()) for x in allt]       # rows/s of every rank's own loop
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t.item())
+        dev_only_ms_per_step = dt / args.steps * 1e3
+        dev_only_value = world * n_rows * args.steps / dt
+        dev_only_per_rank = per_rank
+        mix_timed_dev = {s_: sum(pool[i % len(pool)]["source"] == s_ for i in range(args.steps)) for s_ in ("val", "train", "same")}
 
     # ---- THE HEADLINE: the loop that samples.  Own image / weights per rank, the SAME reference stream (seed 0)
     #      on every rank so that the per-window patch-source mix -- 'same' iterations cost ~1.2x a 'val' one -- is identical on
     #      every GPU (weak scaling: per-GPU work fixed as N grows).  WINDOWS windows of exactly --steps iterations, each between
     #      barrier + synchronize on both sides, max over ranks per window; reported: the median window. ----
     NW = max(0, int(args.windows))
-    fe = CompletionFit(img, mask, angles, periods, syn.SEED0_FREQS, syn.init_params(K, seed=rank), device=dev, N_rand=8192,
-                       ksplit=args.ksplit, seed=0, shifts=shifts, rng_mode="reference", prefetch=8)
+    gc.collect()                           # before the warm-up: a collection pause idles the GPU right in front of the first window
+    gc.disable()
     for _ in range(max(args.warmup, 20) if NW else 0):
         fe.step_full()
-    barrier()
-    gc.collect()
-    gc.disable()
     win_dt, win_ok, win_mix = [], [], []
     for w_ in range(NW):
         n_ok, mix_w = 0, {"val": 0, "train": 0, "same": 0}
@@ -365,8 +394,60 @@ def main():
         allt = [torch.empty_like(t) for _ in range(world)]
         dist.all_gather(allt, t)
         per_rank = [float(x.item()) for x in allt]               # (every rank's window is bounded by the same barriers)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(fe if args.windows else fit, args.dump_outputs)
+
+    # ---- the one collective of the job: gather the fitted images -- directly behind the timed loop, before any rank-0-only
+    #      extra (the other ranks would sit in the all_gather meanwhile) ----
+    gather_ms = None
+    if dist is not None:
+        out = fe.render_image().contiguous()
+        bufs = [torch.empty_like(out) for _ in range(world)]
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        dist.all_gather(bufs, out)
+        torch.cuda.synchronize()
+        gather_ms = (time.perf_counter() - t1) * 1e3
+        del bufs
     fe.close()
     del fe
+    stash8 = bool(ops.tune("stash8"))      # the 8-bit training stash (default): 2 one-byte arrays per snake layer (fp8 output, u8 snake'),
+                                           # fp8 f1 / f2 / embedding slots, bf8 gradients; the weight-gradient launch contracts them on the fp8 MFMA
+    line = {
+        "metric": "fitted pixels/sec/GPU (512^2 grid, 256-wide MLP) + iters-to-target-PSNR",
+        "value": value, "unit": "rows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16", "data": "synthetic",
+        "dtype_note": ("bf16 MFMA operands / fp32 accumulate, master weights, Adam and losses in the forward and the data-gradient chain; "
+                       + ("the weight-gradient products read the 8-bit training stash (bf8 x fp8, fp32 accumulate; npp_tune stash8=0 restores bf16 x bf16) -- "
+                          "parity: the reference's full 2000-iteration c2 fit reproduced to 55 dB between the two fitted images, every golden trajectory within 0.1 dB"
+                          if stash8 else "16-bit training stash")),
+        "config": {"workload": f"c2: {H}x{H} completion image, top-{K} proposals, 256-wide x 8-layer NPP_Net; "
+                               f"step = 1 complete optimisation iteration (train.py:133-264) over {n_pix} pixel rows + "
+                               f"2x{patch}^2 patch rows: fused embed+MLP fwd, adaptive robust pixel loss, patch plumbing, "
+                               f"VGG19 trunk + contextual loss + trunk dgrad (+ VGG16/LPIPS on 'same'), bwd chain, wgrad, Adam",
+                   "rows_per_step": n_rows, "image": [H, H], "K": K, "width": 256, "ksplit": ksplit,
+                   "images_per_gpu": 1, "patch_size": patch,
+                   "trunk_dtype": "fp16 forward / bf16 gradient MFMA, fp32 accumulate",
+                   "value_is": ((f"median of {args.windows} consecutive windows" if args.windows > 1 else "one window")
+                                + " of --steps iterations of the loop that samples (reference random stream, producer thread)"
+                                if args.windows > 0 else "--windows 0: the pre-drawn-pool loop (device only) -- a profiling run, not the headline definition"),
+                   "window_rows_per_s_min": min(win_rates), "window_rows_per_s_max": max(win_rates),
+                   "window_rows_per_s_all": ", ".join(f"{r_:.4g}" for r_ in win_rates),
+                   "timed_source_mix": f"val {win_mix[med]['val']} / train {win_mix[med]['train']} / same {win_mix[med]['same']} (the median window; the stream's own draw)",
+                   "training_stash": "8-bit" if stash8 else "16-bit"},
+        "value_per_gpu": value / world,
+        "final_gather_ms": gather_ms, "per_rank_rows_per_s": per_rank if per_rank is not None else [value],
+        "collective": {"backend": None, "ranks": 1} if dist is None else {"backend": backend + (" (RCCL)" if backend == "nccl" else ""),
+                                                                          "ranks": dist.get_world_size()},
+    }
+    if not args.full:                      # a plain run: the headline line and nothing else
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # the timed steps walk the pool in order: a step count that is not a multiple of the pool weighs the sources by the pool's
     # ORDER instead of its 50 / 30 / 20 mix ('same' iterations cost 1.3x): say so in the line instead of hiding it
     mix_timed = {s_: sum(pool[i % len(pool)]["source"] == s_ for i in range(args.steps)) for s_ in ("val", "train", "same")}   # (of the device-only loop)
@@ -393,18 +474,6 @@ def main():
         dist.all_gather(alle, te)
         e2e_ranks = {"host_enqueue_ms_per_iter": [float(x[0]) for x in alle]}
 
-    # ---- the one collective of the job: gather the fitted images -- directly behind the timed loop, before any rank-0-only
-    #      extra (the other ranks would sit in the all_gather meanwhile) ----
-    gather_ms = None
-    if dist is not None:
-        out = fit.render_image().contiguous()
-        bufs = [torch.empty_like(out) for _ in range(world)]
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        dist.all_gather(bufs, out)
-        torch.cuda.synchronize()
-        gather_ms = (time.perf_counter() - t1) * 1e3
-        del bufs
     if rank != 0:                          # everything below is rank 0's report
         if dist is not None:
             dist.barrier()
@@ -541,8 +610,6 @@ def main():
     dz_cols = 11 * W2 + W2 // 2 + 32               # dz of every layer (+ the padded rgb rows)
     wjob_rows = (W2 + 480) * 2 + (W2 + W2) * 10 + (W2 + 480) * (K - 1) + (W2 // 2 + W2) * 2 + (32 + W2 // 2)
     n_par = net.n_params
-    stash8 = bool(ops.tune("stash8"))      # the 8-bit training stash (default): 2 one-byte arrays per snake layer (fp8 output, u8 snake'),
-                                           # fp8 f1 / f2 / embedding slots, bf8 gradients; the weight-gradient launch contracts them on the fp8 MFMA
     if stash8:
         hbm_bytes = {"mlp_fwd_train": bp * (8 + 12 + 2 * z_cols + lin_cols + emb_cols) + 2.4e6,
                      "mlp_bwd_chain": bp * (24 + z_cols + dz_cols) + 1.5e6,
@@ -978,62 +1045,38 @@ def main():
         cpu = cpu_baseline(K, H, patch, n_pix, fit.patch_num, fit.topk)
 
     if rank == 0:
-        line = {
-            "metric": "fitted pixels/sec/GPU (512^2 grid, 256-wide MLP) + iters-to-target-PSNR",
-            "value": value, "unit": "rows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16", "data": "synthetic",
-            "dtype_note": ("bf16 MFMA operands / fp32 accumulate, master weights, Adam and losses in the forward and the data-gradient chain; "
-                           + ("the weight-gradient products read the 8-bit training stash (bf8 x fp8, fp32 accumulate; npp_tune stash8=0 restores bf16 x bf16) -- "
-                              "parity: the reference's full 2000-iteration c2 fit reproduced to 55 dB between the two fitted images, every golden trajectory within 0.1 dB"
-                              if stash8 else "16-bit training stash")),
-            "config": {"workload": f"c2: {H}x{H} completion image, top-{K} proposals, 256-wide x 8-layer NPP_Net; "
-                                   f"step = 1 complete optimisation iteration (train.py:133-264) over {n_pix} pixel rows + "
-                                   f"2x{patch}^2 patch rows: fused embed+MLP fwd, adaptive robust pixel loss, patch plumbing, "
-                                   f"VGG19 trunk + contextual loss + trunk dgrad (+ VGG16/LPIPS on 'same'), bwd chain, wgrad, Adam",
-                       "rows_per_step": n_rows, "image": [H, H], "K": K, "width": 256, "ksplit": net.ksplit,
-                       "images_per_gpu": 1, "patch_size": patch, "patch_source_mix_in_pool": mix,
-                       "trunk_dtype": "fp16 forward / bf16 gradient MFMA, fp32 accumulate",
-                       # flat copies of the report's other headline numbers (the driver's parser keeps scalars of `config` only)
-                       "value_is": (f"median of {args.windows} consecutive windows of --steps iterations of the loop that samples (reference random stream, producer thread)"
-                                    if args.windows > 0 else "--windows 0: the pre-drawn-pool loop (device only) -- a profiling run, not the headline definition"),
-                       "window_rows_per_s_min": min(win_rates), "window_rows_per_s_max": max(win_rates),
-                       "window_rows_per_s_all": ", ".join(f"{r_:.4g}" for r_ in win_rates),
-                       "timed_source_mix": f"val {win_mix[med]['val']} / train {win_mix[med]['train']} / same {win_mix[med]['same']} (the median window; the stream's own draw)",
-                       "device_only_rows_per_s": dev_only_value, "device_only_ms_per_step": dev_only_ms_per_step,
-                       "device_only_timed_source_mix": f"val {mix_timed['val']} / train {mix_timed['train']} / same {mix_timed['same']}",
-                       "device_only_mix_is_50_30_20": bool(mix_ok),
-                       "training_stash": "8-bit" if stash8 else "16-bit",
-                       "rows_per_s_incl_sampling_reference_rng": _e2e_rate(e2e, "same_stream_native_rng_producer_thread", n_rows),
-                       "rows_per_s_incl_sampling_fast_rng": _e2e_rate(e2e, "fast_mode", n_rows),
-                       "render_pixels_per_s": render_px_s, "iters_to_28dB": iters_to_target, "psnr_known_after_300_iters_dB": final_psnr,
-                       "stacked_M8_rows_per_s_per_gpu": _dig(stacked, "stacked_M8", "rows_per_s"),
-                       "stacked_M8_x_single": _dig(stacked, "stacked_M8", "x_single"),
-                       "stacked_M8_rows_per_s_incl_sampling_reference_rng": _dig(stacked, "stacked_M8", "e2e_reference_rng_rows_per_s"),
-                       "stacked_M4_rows_per_s_per_gpu": _dig(stacked, "stacked_M4", "rows_per_s"),
-                       "c4_embedder_1024sq_fp32_frac_of_hbm_peak": _dig(c4, "fp32", "frac_of_hbm_peak"),
-                       "c4_render_1024sq_fp32_pixels_per_s": _dig(c4, "render_1024sq_fp32_fused", "pixels_per_s"),
-                       "ms_per_iter_val": _dig(per_source, "val"), "ms_per_iter_train": _dig(per_source, "train"),
-                       "ms_per_iter_same": _dig(per_source, "same"), "host_enqueue_ms_per_iter": host_enqueue_ms},
+        # flat copies of the report's other numbers in `config` (a parser that keeps only its scalars still sees them)
+        line["config"].update({
+            "patch_source_mix_in_pool": mix,
+            "device_only_rows_per_s": dev_only_value, "device_only_ms_per_step": dev_only_ms_per_step,
+            "device_only_timed_source_mix": f"val {mix_timed['val']} / train {mix_timed['train']} / same {mix_timed['same']}",
+            "device_only_mix_is_50_30_20": bool(mix_ok),
+            "rows_per_s_incl_sampling_reference_rng": _e2e_rate(e2e, "same_stream_native_rng_producer_thread", n_rows),
+            "rows_per_s_incl_sampling_fast_rng": _e2e_rate(e2e, "fast_mode", n_rows),
+            "render_pixels_per_s": render_px_s, "iters_to_28dB": iters_to_target, "psnr_known_after_300_iters_dB": final_psnr,
+            "stacked_M8_rows_per_s_per_gpu": _dig(stacked, "stacked_M8", "rows_per_s"),
+            "stacked_M8_x_single": _dig(stacked, "stacked_M8", "x_single"),
+            "stacked_M8_rows_per_s_incl_sampling_reference_rng": _dig(stacked, "stacked_M8", "e2e_reference_rng_rows_per_s"),
+            "stacked_M4_rows_per_s_per_gpu": _dig(stacked, "stacked_M4", "rows_per_s"),
+            "c4_embedder_1024sq_fp32_frac_of_hbm_peak": _dig(c4, "fp32", "frac_of_hbm_peak"),
+            "c4_render_1024sq_fp32_pixels_per_s": _dig(c4, "render_1024sq_fp32_fused", "pixels_per_s"),
+            "ms_per_iter_val": _dig(per_source, "val"), "ms_per_iter_train": _dig(per_source, "train"),
+            "ms_per_iter_same": _dig(per_source, "same"), "host_enqueue_ms_per_iter": host_enqueue_ms})
+        line.update({
             "mlp_only_step": {"ms_per_step": mlp_ms, "rows_per_s": n_rows / (mlp_ms * 1e-3),
-                              "mlp_mfma_frac": 2 * train_macs * n_rows / (mlp_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS,
-                              },
-            "value_per_gpu": value / world,
+                              "mlp_mfma_frac": 2 * train_macs * n_rows / (mlp_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS},
             "value_incl_sampling": (n_rows / (e2e["same_stream_native_rng_producer_thread"]["ms_per_iter"] * 1e-3)
                                     if e2e and "same_stream_native_rng_producer_thread" in e2e else None),
             "render_pixels_per_s_per_gpu": render_px_s,
             "iters_to_28dB": iters_to_target, "psnr_known_after_300_iters": final_psnr,
-            "final_gather_ms": gather_ms, "per_rank_rows_per_s": per_rank if per_rank is not None else [value],
             "device_only_per_rank_rows_per_s": dev_only_per_rank,
-            "collective": {"backend": None, "ranks": 1} if dist is None else {"backend": backend + (" (RCCL)" if backend == "nccl" else ""),
-                                                                              "ranks": dist.get_world_size()},
             "end_to_end_incl_host_sampling": e2e or None,
             "c4_embedder_1024sq": c4, "proposal_ranking_candidate": ranking, "throughput_mode_2_images_per_gpu": two_fits, "ms_per_iter_by_patch_source": per_source,
             "netwidth_512_fused": w512, "remapping_task_1024sq": remap, "stacked_images_per_gpu": stacked,
             "host_enqueue_ms_per_iter": host_enqueue_ms, "all_ranks_incl_sampling": e2e_ranks,
             "patch_loss_kernels_us": {k_: round(v_ * 1e6, 1) for k_, v_ in patch_kt.items()},
             "roofline": roofline, "cpu_baseline": cpu,
-        }
+        })
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()

@@ -44,6 +44,13 @@ def test_bench_refuses_world_size_mismatch():
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
 
 
+def test_bench_refuses_bad_step_and_window_counts():
+    """--steps sets the number of timed steps (at least one); --windows 0 reports the pre-drawn-pool loop, which only --full runs."""
+    for extra in (["--steps", "0"], ["--windows", "0"], ["--windows", "-1", "--full"]):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1"] + extra, env=_env(), capture_output=True, text=True, timeout=120)
+        assert r.returncode != 0 and not any(l.startswith("{") for l in r.stdout.splitlines()), extra
+
+
 def test_launch_ranks_helper_returns_child_code(tmp_path):
     sys.path.insert(0, ROOT)
     from npp_amd.parallel import launch_ranks
@@ -92,7 +99,7 @@ def test_four_ranks_on_one_card_with_a_node_share_of_cpus_each():
         pytest.skip("no GPU")
     if len(os.sched_getaffinity(0)) < 8:
         pytest.skip("fewer than 8 CPUs")
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--steps", "40", "--warmup", "5", "--no-psnr", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--steps", "40", "--warmup", "5", "--full", "--no-psnr", "--no-cpu-baseline"],
                        env=_env(NPP_BENCH_DEVICE="0", NPP_BENCH_BACKEND="gloo", NPP_BENCH_CPUS_PER_RANK="2",
                                 HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -105,3 +112,29 @@ def test_four_ranks_on_one_card_with_a_node_share_of_cpus_each():
     print("host enqueue ms per iteration, per rank:", [round(v, 3) for v in e["host_enqueue_ms_per_iter"]],
           "| sampling-inclusive rows/s per rank (card shared 4 ways):", [round(v) for v in j["per_rank_rows_per_s"]])
     assert max(e["host_enqueue_ms_per_iter"]) < 0.6, e
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain run prints the headline line of exactly --steps timed steps (one window) and nothing beside it, and
+    --dump-outputs writes the last step's arrays as float32 .npy files within 64 MB (a child process, like the tests above)."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "10", "--warmup", "2", "--dump-outputs", str(out)],
+                       env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["steps"] == 10 and j["unit"] == "rows/s" and j["higher_is_better"] is True and j["dtype"] == "bf16"
+    assert j["ms_per_step"] > 0 and j["value"] > 1e6 and j["config"]["value_is"].startswith("one window")
+    assert "roofline" not in j and "cpu_baseline" not in j and "device_only_rows_per_s" not in j["config"]
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["latents.npy", "params.npy", "patch_loss.npy", "pixel_loss.npy", "pred.npy"]
+    arrays = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["pred"].shape == (j["config"]["rows_per_step"], 3)

@@ -3,7 +3,7 @@
 #   tools/ab.sh build_ab/libnpp_a.so build_ab/libnpp_b.so ...     ("" = the in-tree library)
 for rep in 1 2 3; do
   for lib in "$@"; do
-    NPP_LIB_PATH=${lib:+$PWD/$lib} python bench.py --no-cpu-baseline --no-psnr --no-extras --steps 100 2>/dev/null | python -c "
+    NPP_LIB_PATH=${lib:+$PWD/$lib} python bench.py --full --no-cpu-baseline --no-psnr --no-extras --steps 100 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$lib', round(d['value']/1e6,2), round(d['ms_per_step'],4), d['roofline']['all_kernels_us'])"
   done
 done
