@@ -122,6 +122,41 @@ int npp_embed_fwd(const int32_t* d_coords_yx, int64_t N, const npp_embed_cfg* cf
 int npp_warp_fwd(const int32_t* d_coords_yx, int64_t N, const npp_embed_cfg* cfg,
                  float* d_out, void* stream);
 
+/* ---- continuous coordinates: render a fitted network anywhere on the plane ----------------------------------------------
+ * The network is a function of the fit's pixel frame (row y, col x as floats; res = (cfg->H, cfg->W) only scales the two linear
+ * columns).  The _coordf forms take (N, 2) fp32 positions [y, x] instead of int32 pixel indices, with the same padding contract as
+ * their int32 neighbours.  The _grid forms take no coordinate buffer: canvas pixel (i, j) of a canvas `width` pixels wide sits at
+ *     y = y0 + i / sy,  x = x0 + j / sx
+ * (an IEEE fp32 quotient, then a separate fp32 add; i and j converted to fp32 exactly), and a launch covers canvas pixels
+ * [start, start + n) in row-major order, writing exactly n output rows (no padding: the surplus rows of the last 64-row tile
+ * compute on the last pixel and are not stored).  So integer scales nest: at scale S, pixel (S i, S j) is bit for bit pixel (i, j)
+ * of scale 1, and scale 1 at origin 0 is the int32 render of the full grid.  NPP_ERR_ARG (with a message) when sy or sx is not
+ * finite or not > 0, the origin is not finite, width < 1, start < 0, n < 0, or a canvas row or column index would reach 2^24
+ * (fp32 would no longer hold it exactly); n == 0 is a no-op. */
+typedef struct {
+  int64_t start, n;      /* first canvas pixel (row-major) and number of pixels of this launch */
+  int32_t width;         /* canvas width in pixels */
+  float y0, x0;          /* fit-frame position of canvas pixel (0, 0) */
+  float sy, sx;          /* canvas pixels per fit pixel (2 = twice the density) */
+} npp_grid;
+/* npp_mlp_fwd_act (bf16 chain, inference: no stash) over a canvas grid: d_out (n, 3).  out_act: 0 raw / 1 sigmoid / 2 tanh. */
+int npp_mlp_fwd_grid(const npp_grid* grid, const npp_embed_cfg* cfg, int width, const void* d_wf, const float* d_params,
+                     float* d_out, int out_act, void* stream);
+/* npp_mlp_fwd32 (exact fp32 chain) over a canvas grid: d_out (n, 3). */
+int npp_mlp_fwd32_grid(const npp_grid* grid, const npp_embed_cfg* cfg, int width, const void* d_w32, const float* d_params,
+                       float* d_out, int out_act, void* stream);
+/* npp_mlp_fwd_act (inference) on fp32 positions: coords (Bp, 2) -> d_pred (Bp, 3), Bp a multiple of NPP_ROW_TILE. */
+int npp_mlp_fwd_coordf(const float* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_wf,
+                       const float* d_params, float* d_pred, int out_act, void* stream);
+/* npp_mlp_fwd32 on fp32 positions: coords (Bp, 2) -> d_out (Bp, 3), Bp a multiple of NPP_ROW_TILE. */
+int npp_mlp_fwd32_coordf(const float* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_w32,
+                         const float* d_params, float* d_out, int out_act, void* stream);
+/* npp_warp_fwd on fp32 positions (the reference's Embedder_periodic.embed of a float tensor): (N, 2) -> (N, K*22), any N. */
+int npp_warp_fwd_coordf(const float* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, float* d_out, void* stream);
+/* npp_embed_fwd on fp32 positions: (N, 2) -> (N, K*462), any N; out_dtype / precise as there. */
+int npp_embed_fwd_coordf(const float* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, void* d_out, int out_dtype, int precise,
+                         void* stream);
+
 /* ---- a5+a6+a7: fused coordinate MLP -------------------------------------- */
 /* Workspace sizes (bytes) for a padded batch of Bp rows (multiple of NPP_ROW_TILE):
  *  sizes[0] 0 (reserved)

@@ -79,8 +79,16 @@ class EmbedCfg(C.Structure):
         return c
 
 
+class Grid(C.Structure):
+    """npp_grid (include/npp_hip.h): canvas pixels [start, start + n) of a canvas `width` pixels wide; pixel (i, j) is evaluated
+    at (y0 + i / sy, x0 + j / sx) of the fit's pixel frame."""
+    _fields_ = [("start", C.c_int64), ("n", C.c_int64), ("width", C.c_int32), ("y0", C.c_float), ("x0", C.c_float),
+                ("sy", C.c_float), ("sx", C.c_float)]
+
+
 _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 _cfgp = C.POINTER(EmbedCfg)
+_gridp = C.POINTER(Grid)
 
 # every symbol include/npp_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -101,6 +109,12 @@ SYMBOLS = {
     "npp_train_workspace": (_i32, [_i32, _i32, _i64, _i32, C.POINTER(_i64)]),
     "npp_mlp_fwd": (_i32, [_vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "npp_mlp_fwd_act": (_i32, [_vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "npp_mlp_fwd_grid": (_i32, [_gridp, _cfgp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "npp_mlp_fwd32_grid": (_i32, [_gridp, _cfgp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "npp_mlp_fwd_coordf": (_i32, [_vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "npp_mlp_fwd32_coordf": (_i32, [_vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "npp_warp_fwd_coordf": (_i32, [_vp, _i64, _cfgp, _vp, _vp]),
+    "npp_embed_fwd_coordf": (_i32, [_vp, _i64, _cfgp, _vp, _i32, _i32, _vp]),
     "npp_mlp_bwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "npp_mlp_wgrad": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "npp_mlp_wgrad_tiles": (_i32, [_i32]),

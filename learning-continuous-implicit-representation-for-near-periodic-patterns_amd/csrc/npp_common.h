@@ -98,6 +98,37 @@ __device__ __forceinline__ float warp_value(const EmbedDev& e, int p, int i, flo
   }
 }
 
+// ---- coordinate intake of the render paths (include/npp_hip.h "continuous coordinates") -------------------------------
+// Coordinate modes of the forward kernels: how row r's (y, x) enters.  A template parameter: the int32 form compiles as before.
+enum CoordMode { kCoordI32 = 0, kCoordF32 = 1, kCoordGrid = 2 };
+
+// Row r of a grid launch: canvas pixel start + min(r, n - 1) in row-major order (the surplus rows of the last 64-row tile
+// compute on the last pixel and are not stored), at y = y0 + i / sy, x = x0 + j / sx -- an IEEE quotient, then a separate add;
+// i, j < 2^24 (checked at launch), so their fp32 conversion is exact.
+__device__ __forceinline__ void grid_coord(const npp_grid& g, int64_t r, float& y, float& x) {
+  const int64_t p = g.start + (r < g.n ? r : g.n - 1);
+  const int64_t i = p / g.width;
+  const int32_t j = (int32_t)(p - i * g.width);
+  y = __fadd_rn(g.y0, __fdiv_rn((float)i, g.sy));
+  x = __fadd_rn(g.x0, __fdiv_rn((float)j, g.sx));
+}
+
+// (y, x) of row r in coordinate mode CM: int32 pixel indices, fp32 positions ((N, 2) [y, x]) or the implicit grid
+template <int CM>
+__device__ __forceinline__ void load_coord(const void* coords, const npp_grid& g, int64_t r, float& y, float& x) {
+  if (CM == kCoordGrid) {
+    grid_coord(g, r, y, x);
+  } else if (CM == kCoordF32) {
+    const float2 c = ((const float2*)coords)[r];
+    y = c.x;
+    x = c.y;
+  } else {
+    const int2 c = ((const int2*)coords)[r];
+    y = (float)c.x;
+    x = (float)c.y;
+  }
+}
+
 // Both functions of one argument from ONE reduction (bitwise the values sincos_pi2(x, false) / (x, true) return): the
 // precise embedder needs sin(f v) and cos(f v) of every (frequency, coordinate) pair.
 __device__ __forceinline__ void sincos_pi2_both(float x, float& sn, float& cs) {

@@ -43,6 +43,28 @@ int check_embed_cfg(const npp_embed_cfg* c, const char* who) {
   return NPP_OK;
 }
 
+// Arguments of a grid launch (include/npp_hip.h "continuous coordinates"); NPP_OK also for n == 0 (the caller returns early)
+int check_grid(const npp_grid* g, const char* who) {
+  if (!g) { set_error("%s: null grid", who); return NPP_ERR_ARG; }
+  if (!(isfinite(g->sy) && g->sy > 0.0f && isfinite(g->sx) && g->sx > 0.0f)) {
+    set_error("%s: scale (sy, sx) = (%g, %g) must be finite and > 0", who, g->sy, g->sx);
+    return NPP_ERR_ARG;
+  }
+  if (!(isfinite(g->y0) && isfinite(g->x0))) { set_error("%s: origin (%g, %g) must be finite", who, g->y0, g->x0); return NPP_ERR_ARG; }
+  if (g->width < 1) { set_error("%s: canvas width %d must be >= 1", who, g->width); return NPP_ERR_ARG; }
+  if (g->start < 0 || g->n < 0) { set_error("%s: start=%lld / n=%lld must be >= 0", who, (long long)g->start, (long long)g->n); return NPP_ERR_ARG; }
+  constexpr int64_t kExact = 1 << 24;                        // canvas indices above this are not exact in fp32
+  if (g->width > kExact) { set_error("%s: canvas width %d: column indices would reach 2^24", who, g->width); return NPP_ERR_ARG; }
+  if (g->n == 0) return NPP_OK;
+  if (g->start > INT64_MAX - g->n || (g->start + g->n - 1) / g->width >= kExact) {
+    set_error("%s: canvas pixels [%lld, %lld + %lld) at width %d: row indices would reach 2^24", who, (long long)g->start,
+              (long long)g->start, (long long)g->n, g->width);
+    return NPP_ERR_ARG;
+  }
+  if ((g->n + NPP_ROW_TILE - 1) / NPP_ROW_TILE > 0x7fffffffLL) { set_error("%s: n=%lld too large for one launch", who, (long long)g->n); return NPP_ERR_ARG; }
+  return NPP_OK;
+}
+
 #ifndef NPP_EMB_ROWS
 #define NPP_EMB_ROWS 32
 #endif
@@ -64,8 +86,9 @@ struct ColEnt { float f; int code; };            // code = v index | identity <<
 // wave-uniform (wave w takes jobs w, w+4, ...) so the constant tables are read through
 // scalar loads.  Phase 2: every thread produces column PAIRS (462 is even) so stores are
 // 8 B (fp32) / 4 B (bf16) and fully coalesced.
-template <bool PRECISE, bool BF16OUT>
-__global__ __launch_bounds__(kEmbThreads) void embed_kernel(const int32_t* __restrict__ coords,
+// FCOORD: the coordinates are fp32 positions (npp_embed_fwd_coordf) instead of int32 pixel indices.
+template <bool PRECISE, bool BF16OUT, bool FCOORD = false>
+__global__ __launch_bounds__(kEmbThreads) void embed_kernel(const void* __restrict__ coords,
                                                             int64_t N, EmbedDev e,
                                                             void* __restrict__ out) {
   __shared__ float sv[kEmbRows * kSvStride];
@@ -93,8 +116,14 @@ __global__ __launch_bounds__(kEmbThreads) void embed_kernel(const int32_t* __res
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int64_t r = row0 + lane;
-    const int2 c = (r < N && lane < kEmbRows) ? ((const int2*)coords)[r] : make_int2(0, 0);
-    const float y = (float)c.x, x = (float)c.y;   // (row=y, col=x): first member is y
+    float y, x;                                   // (row=y, col=x): first member is y
+    if (FCOORD) {
+      const float2 c = (r < N && lane < kEmbRows) ? ((const float2*)coords)[r] : make_float2(0.0f, 0.0f);
+      y = c.x; x = c.y;
+    } else {
+      const int2 c = (r < N && lane < kEmbRows) ? ((const int2*)coords)[r] : make_int2(0, 0);
+      y = (float)c.x; x = (float)c.y;
+    }
     for (int job = wave; job < K * 22; job += 4)
       if (lane < kEmbRows) sv[lane * kSvStride + job] = warp_value<PRECISE>(e, job / 22, job % 22, y, x);
   }
@@ -198,12 +227,13 @@ __global__ __launch_bounds__(kEmbThreads) void embed_kernel(const int32_t* __res
   }
 }
 
-__global__ void warp_kernel(const int32_t* __restrict__ coords, int64_t N, EmbedDev e,
+template <bool FCOORD = false>
+__global__ void warp_kernel(const void* __restrict__ coords, int64_t N, EmbedDev e,
                             float* __restrict__ out) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= N) return;
-  const int2 c = ((const int2*)coords)[r];
-  const float y = (float)c.x, x = (float)c.y;
+  float y, x;
+  load_coord<FCOORD ? kCoordF32 : kCoordI32>(coords, npp_grid{}, r, y, x);
   for (int p = 0; p < e.K; ++p)
     for (int i = 0; i < 22; ++i) out[r * (e.K * 22) + p * 22 + i] = warp_value<true>(e, p, i, y, x);
 }
@@ -212,34 +242,54 @@ __global__ void warp_kernel(const int32_t* __restrict__ coords, int64_t N, Embed
 
 using namespace npp;
 
-extern "C" int npp_embed_fwd(const int32_t* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, void* d_out,
-                             int out_dtype, int precise, void* stream) {
-  int rc = check_embed_cfg(cfg, "npp_embed_fwd");
+template <bool FCOORD>
+static int embed_launch(const void* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, void* d_out, int out_dtype, int precise,
+                        void* stream, const char* who) {
+  int rc = check_embed_cfg(cfg, who);
   if (rc) return rc;
-  if (N < 0 || (N > 0 && (!d_coords_yx || !d_out))) { set_error("npp_embed_fwd: bad N/pointers"); return NPP_ERR_ARG; }
-  if (out_dtype != 0 && out_dtype != 1) { set_error("npp_embed_fwd: out_dtype %d", out_dtype); return NPP_ERR_ARG; }
+  if (N < 0 || (N > 0 && (!d_coords_yx || !d_out))) { set_error("%s: bad N/pointers", who); return NPP_ERR_ARG; }
+  if (out_dtype != 0 && out_dtype != 1) { set_error("%s: out_dtype %d", who, out_dtype); return NPP_ERR_ARG; }
   if (N == 0) return NPP_OK;
   const EmbedDev e = make_embed_dev(*cfg);
   const dim3 grid((unsigned)((N + kEmbRows - 1) / kEmbRows)), block(kEmbThreads);
   hipStream_t s = (hipStream_t)stream;
   if (precise) {
-    if (out_dtype) hipLaunchKernelGGL((embed_kernel<true, true>), grid, block, 0, s, d_coords_yx, N, e, d_out);
-    else hipLaunchKernelGGL((embed_kernel<true, false>), grid, block, 0, s, d_coords_yx, N, e, d_out);
+    if (out_dtype) hipLaunchKernelGGL((embed_kernel<true, true, FCOORD>), grid, block, 0, s, d_coords_yx, N, e, d_out);
+    else hipLaunchKernelGGL((embed_kernel<true, false, FCOORD>), grid, block, 0, s, d_coords_yx, N, e, d_out);
   } else {
-    if (out_dtype) hipLaunchKernelGGL((embed_kernel<false, true>), grid, block, 0, s, d_coords_yx, N, e, d_out);
-    else hipLaunchKernelGGL((embed_kernel<false, false>), grid, block, 0, s, d_coords_yx, N, e, d_out);
+    if (out_dtype) hipLaunchKernelGGL((embed_kernel<false, true, FCOORD>), grid, block, 0, s, d_coords_yx, N, e, d_out);
+    else hipLaunchKernelGGL((embed_kernel<false, false, FCOORD>), grid, block, 0, s, d_coords_yx, N, e, d_out);
   }
-  return check_launch("npp_embed_fwd");
+  return check_launch(who);
+}
+
+template <bool FCOORD>
+static int warp_launch(const void* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, float* d_out, void* stream, const char* who) {
+  int rc = check_embed_cfg(cfg, who);
+  if (rc) return rc;
+  if (N < 0 || (N > 0 && (!d_coords_yx || !d_out))) { set_error("%s: bad N/pointers", who); return NPP_ERR_ARG; }
+  if (N == 0) return NPP_OK;
+  const EmbedDev e = make_embed_dev(*cfg);
+  hipLaunchKernelGGL(warp_kernel<FCOORD>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     d_coords_yx, N, e, d_out);
+  return check_launch(who);
+}
+
+extern "C" int npp_embed_fwd(const int32_t* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, void* d_out,
+                             int out_dtype, int precise, void* stream) {
+  return embed_launch<false>(d_coords_yx, N, cfg, d_out, out_dtype, precise, stream, "npp_embed_fwd");
+}
+
+extern "C" int npp_embed_fwd_coordf(const float* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, void* d_out,
+                                    int out_dtype, int precise, void* stream) {
+  return embed_launch<true>(d_coords_yx, N, cfg, d_out, out_dtype, precise, stream, "npp_embed_fwd_coordf");
 }
 
 extern "C" int npp_warp_fwd(const int32_t* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, float* d_out,
                             void* stream) {
-  int rc = check_embed_cfg(cfg, "npp_warp_fwd");
-  if (rc) return rc;
-  if (N < 0 || (N > 0 && (!d_coords_yx || !d_out))) { set_error("npp_warp_fwd: bad N/pointers"); return NPP_ERR_ARG; }
-  if (N == 0) return NPP_OK;
-  const EmbedDev e = make_embed_dev(*cfg);
-  hipLaunchKernelGGL(warp_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     d_coords_yx, N, e, d_out);
-  return check_launch("npp_warp_fwd");
+  return warp_launch<false>(d_coords_yx, N, cfg, d_out, stream, "npp_warp_fwd");
+}
+
+extern "C" int npp_warp_fwd_coordf(const float* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, float* d_out, void* stream) {
+  return warp_launch<true>(d_coords_yx, N, cfg, d_out, stream, "npp_warp_fwd_coordf");
 }

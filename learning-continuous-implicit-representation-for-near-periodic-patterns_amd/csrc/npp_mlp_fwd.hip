@@ -123,6 +123,10 @@ struct FwdArgs {
   Stack S;
   const EmbedDev* estack;
   int64_t wf_stride16, params_stride, act_stride;     // 16-byte units / floats / bytes per image
+  // render paths (CM != kCoordI32, inference only): fp32 positions instead of coords, or the implicit canvas grid (pred then
+  // holds g.n rows)
+  const float* coordsf;
+  npp_grid g;
 };
 
 struct EmbTabs {
@@ -675,8 +679,11 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[NTW][kNB], char* out, int
 // pressure in a kernel that already spills 40 of them.
 // ACT: the output nonlinearity is read from A_.out_act (npp_mlp_fwd_act: tanh / raw); false = the sigmoid, compiled in -- a template
 // parameter for the same reason as STACK (the run-time test cost the default launch 0.9 us in a same-box A/B)
-template <int TRAIN, bool MULTI, bool EMB_IN = false, bool STACK = false, bool ACT = false>
+// CM: coordinate mode (npp_common.h CoordMode) of the render paths -- fp32 positions (npp_mlp_fwd_coordf) or the implicit canvas
+// grid (npp_mlp_fwd_grid); both read the nonlinearity from A_.out_act like ACT.  kCoordI32 is every other launch, unchanged.
+template <int TRAIN, bool MULTI, bool EMB_IN = false, bool STACK = false, bool ACT = false, int CM = kCoordI32>
 __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdArgs A_, EmbedDev e_arg, NetDesc d) {
+  static_assert(CM == kCoordI32 || (TRAIN == 0 && !EMB_IN && !STACK), "the render coordinate modes are inference-only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if (TRAIN == 2) set_fp16_ovfl();
   int img_ = 0, wg = blockIdx.x, xslot_ = blockIdx.x >> 3, xcount_ = ((int)gridDim.x + 7) >> 3;
@@ -743,9 +750,16 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
   const int nt0 = kNTW * L.wave;         // this wave's neuron tiles in 256-wide layers
 
   if (!EMB_IN && L.tid < kRowTile) {
-    const int2 c = ((const int2*)s_coords)[row0 + L.tid];
-    sY[L.tid] = (float)c.x;              // (row=y, col=x)
-    sX[L.tid] = (float)c.y;
+    if (CM == kCoordI32) {
+      const int2 c = ((const int2*)s_coords)[row0 + L.tid];
+      sY[L.tid] = (float)c.x;              // (row=y, col=x)
+      sX[L.tid] = (float)c.y;
+    } else {
+      float y, x;
+      load_coord<CM>(A_.coordsf, A_.g, row0 + L.tid, y, x);
+      sY[L.tid] = y;
+      sX[L.tid] = x;
+    }
   }
   wg_barrier();
 
@@ -958,8 +972,8 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
 #pragma unroll
       for (int w = 0; w < kNT / 2; ++w) z += sRGB[(w * kRowTile + row) * 3 + c];   // P's neuron tiles, in order
       float o = 1.0f / (1.0f + __expf(-z));                         // helpers.py:56 sigmoid
-      if ((EMB_IN || ACT) && A_.out_act != 1) o = A_.out_act == 2 ? tanhf(z) : z;   // helpers.py:57-58 tanh (--normalize_type 2) / raw network output
-      s_pred[(row0 + row) * 3 + c] = o;
+      if ((EMB_IN || ACT || CM != kCoordI32) && A_.out_act != 1) o = A_.out_act == 2 ? tanhf(z) : z;   // helpers.py:57-58 tanh (--normalize_type 2) / raw network output
+      if (CM != kCoordGrid || row0 + row < A_.g.n) s_pred[(row0 + row) * 3 + c] = o;   // a grid launch stores exactly g.n rows
     }
   }
 #pragma unroll
@@ -1077,6 +1091,61 @@ extern "C" int npp_mlp_fwd_emb(const float* d_emb, int64_t ld, int64_t Bp, int K
   EmbedDev e{};
   e.K = K;
   return fwd_launch(A, e, make_desc(K), true, stream, "npp_mlp_fwd_emb");
+}
+
+// ---- render paths: fp32 positions / the implicit canvas grid (include/npp_hip.h "continuous coordinates") -----------------------
+namespace npp {
+int check_grid(const npp_grid* g, const char* who);
+}
+
+template <int CM>
+static int fwd_launch_render(const FwdArgs& A, const npp_embed_cfg* cfg, int64_t n_wg, void* stream, const char* who) {
+  const EmbedDev e = make_embed_dev(*cfg);
+  const NetDesc d = make_desc(cfg->K);
+  const dim3 grid((unsigned)n_wg), block(kThreads);
+  hipStream_t s = (hipStream_t)stream;
+#define NPP_LAUNCH_RENDER(M)                                                                                   \
+  do {                                                                                                         \
+    static SmemOnce once;                                                                                      \
+    if (!smem_attr(once, (const void*)mlp_fwd_kernel<0, M, false, false, false, CM>, kSmemFwd)) {              \
+      set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH;                                             \
+    }                                                                                                          \
+    hipLaunchKernelGGL((mlp_fwd_kernel<0, M, false, false, false, CM>), grid, block, kSmemFwd, s, A, e, d);    \
+  } while (0)
+  if (d.K > 1) NPP_LAUNCH_RENDER(true);
+  else NPP_LAUNCH_RENDER(false);
+#undef NPP_LAUNCH_RENDER
+  return check_launch(who);
+}
+
+extern "C" int npp_mlp_fwd_coordf(const float* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_wf,
+                                  const float* d_params, float* d_pred, int out_act, void* stream) {
+  const char* who = "npp_mlp_fwd_coordf";
+  int rc = check_embed_cfg(cfg, who);
+  if (rc) return rc;
+  if ((rc = fwd_check(Bp, width, d_coords_yx, d_wf, d_params, d_pred, who))) return rc;
+  if (out_act < 0 || out_act > 2) { set_error("%s: out_act=%d", who, out_act); return NPP_ERR_ARG; }
+  FwdArgs A{};
+  A.Bp = Bp; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_pred; A.out_act = out_act;
+  A.coordsf = d_coords_yx;
+  return fwd_launch_render<kCoordF32>(A, cfg, Bp / kRowTile, stream, who);
+}
+
+extern "C" int npp_mlp_fwd_grid(const npp_grid* grid, const npp_embed_cfg* cfg, int width, const void* d_wf, const float* d_params,
+                                float* d_out, int out_act, void* stream) {
+  const char* who = "npp_mlp_fwd_grid";
+  int rc = check_grid(grid, who);
+  if (rc) return rc;
+  if ((rc = check_embed_cfg(cfg, who))) return rc;
+  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
+  if (grid->n == 0) return NPP_OK;
+  if (!d_wf || !d_params || !d_out) { set_error("%s: null pointer", who); return NPP_ERR_ARG; }
+  if (out_act < 0 || out_act > 2) { set_error("%s: out_act=%d", who, out_act); return NPP_ERR_ARG; }
+  const int64_t n_wg = (grid->n + kRowTile - 1) / kRowTile;
+  FwdArgs A{};
+  A.Bp = n_wg * kRowTile; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_out; A.out_act = out_act;
+  A.g = *grid;
+  return fwd_launch_render<kCoordGrid>(A, cfg, n_wg, stream, who);
 }
 
 // ---- stacked form: M images per launch (npp_common.h "stacked launches") ----------------------------------------------------

@@ -23,6 +23,7 @@ namespace npp {
 
 EmbedDev make_embed_dev(const npp_embed_cfg& c);
 int check_embed_cfg(const npp_embed_cfg* c, const char* who);
+int check_grid(const npp_grid* g, const char* who);
 
 constexpr int kT32 = 32 * kNT;                     // threads: 2 neuron tiles per wave (4 waves at W = 256, 8 at W = 512)
 constexpr int kRegion32 = kW * kRowTile * 4;       // 64 KiB: 256 features x 64 rows fp32
@@ -37,6 +38,9 @@ struct Fwd32Args {
   const float* params;
   float* pred;
   int32_t out_act;
+  // render paths (CM != kCoordI32): fp32 positions instead of coords, or the implicit canvas grid (pred then holds g.n rows)
+  const float* coordsf;
+  npp_grid g;
 };
 
 // B operands generated from the 22 warped coordinates of one proposal (sV[i][row], fp32): k-step q < 220 contracts
@@ -61,7 +65,8 @@ struct EmbSrc32 {
   }
 };
 
-template <bool MULTI>
+// CM: coordinate mode (npp_common.h CoordMode) -- int32 pixel indices, fp32 positions or the implicit canvas grid
+template <bool MULTI, int CM = kCoordI32>
 __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedDev e_arg, NetDesc d, Desc32 d32) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* R = smem;
@@ -97,9 +102,16 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
   const float* P = A_.params;
   const int nt0 = 2 * wave;
   if (tid < kRowTile) {
-    const int2 c = ((const int2*)A_.coords)[row0 + tid];
-    sY[tid] = (float)c.x;
-    sX[tid] = (float)c.y;
+    if (CM == kCoordI32) {
+      const int2 c = ((const int2*)A_.coords)[row0 + tid];
+      sY[tid] = (float)c.x;
+      sX[tid] = (float)c.y;
+    } else {
+      float y, x;
+      load_coord<CM>(A_.coordsf, A_.g, row0 + tid, y, x);
+      sY[tid] = y;
+      sX[tid] = x;
+    }
   }
   wg_barrier();
 
@@ -234,7 +246,7 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
 #pragma unroll
     for (int w = 0; w < kNT / 2; ++w) z += sRGB[(w * kRowTile + row) * 3 + c];
     const float o = A_.out_act == 1 ? 1.0f / (1.0f + expf(-z)) : (A_.out_act == 2 ? tanhf(z) : z);
-    A_.pred[(row0 + row) * 3 + c] = o;
+    if (CM != kCoordGrid || row0 + row < A_.g.n) A_.pred[(row0 + row) * 3 + c] = o;
   }
 }
 
@@ -276,6 +288,25 @@ extern "C" int npp_pack_weights32(const float* d_params, void* d_w32, int K, int
   return check_launch("npp_pack_weights32");
 }
 
+template <int CM>
+static int fwd32_launch(const Fwd32Args& A, const npp_embed_cfg* cfg, int64_t n_wg, void* stream, const char* who) {
+  const EmbedDev e = make_embed_dev(*cfg);
+  const NetDesc d = make_desc(cfg->K);
+  const Desc32 d32 = make_desc32(cfg->K);
+  const dim3 grid((unsigned)n_wg), block(kT32);
+  hipStream_t s = (hipStream_t)stream;
+  if (cfg->K > 1) {
+    static SmemOnce once;
+    if (!smem_attr(once, (const void*)mlp_fwd32_kernel<true, CM>, kSmem32)) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; }
+    hipLaunchKernelGGL((mlp_fwd32_kernel<true, CM>), grid, block, kSmem32, s, A, e, d, d32);
+  } else {
+    static SmemOnce once;
+    if (!smem_attr(once, (const void*)mlp_fwd32_kernel<false, CM>, kSmem32)) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; }
+    hipLaunchKernelGGL((mlp_fwd32_kernel<false, CM>), grid, block, kSmem32, s, A, e, d, d32);
+  }
+  return NPP_OK;
+}
+
 extern "C" int npp_mlp_fwd32(const int32_t* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_w32,
                              const float* d_params, float* d_out, int out_act, void* stream) {
   int rc = check_embed_cfg(cfg, "npp_mlp_fwd32");
@@ -284,19 +315,34 @@ extern "C" int npp_mlp_fwd32(const int32_t* d_coords_yx, int64_t Bp, const npp_e
   if (Bp <= 0 || Bp % kRowTile || Bp / kRowTile > 0x7fffffffLL) { set_error("npp_mlp_fwd32: Bp=%lld must be a positive multiple of %d", (long long)Bp, kRowTile); return NPP_ERR_ARG; }
   if (!d_coords_yx || !d_w32 || !d_params || !d_out || out_act < 0 || out_act > 2) { set_error("npp_mlp_fwd32: bad argument"); return NPP_ERR_ARG; }
   Fwd32Args A{d_coords_yx, Bp, (const float*)d_w32, d_params, d_out, out_act};
-  const EmbedDev e = make_embed_dev(*cfg);
-  const NetDesc d = make_desc(cfg->K);
-  const Desc32 d32 = make_desc32(cfg->K);
-  const dim3 grid((unsigned)(Bp / kRowTile)), block(kT32);
-  hipStream_t s = (hipStream_t)stream;
-  if (cfg->K > 1) {
-    static SmemOnce once;
-    if (!smem_attr(once, (const void*)mlp_fwd32_kernel<true>, kSmem32)) { set_error("npp_mlp_fwd32: smem attribute"); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL((mlp_fwd32_kernel<true>), grid, block, kSmem32, s, A, e, d, d32);
-  } else {
-    static SmemOnce once;
-    if (!smem_attr(once, (const void*)mlp_fwd32_kernel<false>, kSmem32)) { set_error("npp_mlp_fwd32: smem attribute"); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL((mlp_fwd32_kernel<false>), grid, block, kSmem32, s, A, e, d, d32);
-  }
+  if ((rc = fwd32_launch<kCoordI32>(A, cfg, Bp / kRowTile, stream, "npp_mlp_fwd32"))) return rc;
   return check_launch("npp_mlp_fwd32");
+}
+
+extern "C" int npp_mlp_fwd32_coordf(const float* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_w32,
+                                    const float* d_params, float* d_out, int out_act, void* stream) {
+  const char* who = "npp_mlp_fwd32_coordf";
+  int rc = check_embed_cfg(cfg, who);
+  if (rc) return rc;
+  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
+  if (Bp <= 0 || Bp % kRowTile || Bp / kRowTile > 0x7fffffffLL) { set_error("%s: Bp=%lld must be a positive multiple of %d", who, (long long)Bp, kRowTile); return NPP_ERR_ARG; }
+  if (!d_coords_yx || !d_w32 || !d_params || !d_out || out_act < 0 || out_act > 2) { set_error("%s: bad argument", who); return NPP_ERR_ARG; }
+  Fwd32Args A{nullptr, Bp, (const float*)d_w32, d_params, d_out, out_act, d_coords_yx, npp_grid{}};
+  if ((rc = fwd32_launch<kCoordF32>(A, cfg, Bp / kRowTile, stream, who))) return rc;
+  return check_launch(who);
+}
+
+extern "C" int npp_mlp_fwd32_grid(const npp_grid* grid, const npp_embed_cfg* cfg, int width, const void* d_w32, const float* d_params,
+                                  float* d_out, int out_act, void* stream) {
+  const char* who = "npp_mlp_fwd32_grid";
+  int rc = check_grid(grid, who);
+  if (rc) return rc;
+  if ((rc = check_embed_cfg(cfg, who))) return rc;
+  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
+  if (grid->n == 0) return NPP_OK;
+  if (!d_w32 || !d_params || !d_out || out_act < 0 || out_act > 2) { set_error("%s: bad argument", who); return NPP_ERR_ARG; }
+  const int64_t n_wg = (grid->n + kRowTile - 1) / kRowTile;
+  Fwd32Args A{nullptr, n_wg * kRowTile, (const float*)d_w32, d_params, d_out, out_act, nullptr, *grid};
+  if ((rc = fwd32_launch<kCoordGrid>(A, cfg, n_wg, stream, who))) return rc;
+  return check_launch(who);
 }

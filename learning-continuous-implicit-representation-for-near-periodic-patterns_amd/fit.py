@@ -531,6 +531,11 @@ class CompletionFit:
         """Full H x W grid through the fused forward: the 'fitted pixels/s' pass."""
         return self.net.render(self.i_all_dev).reshape(self.H, self.W, 3)
 
+    def save_model(self, path, **meta):
+        """The fitted network as a model file (modelfile.py), for render.py / NPPNet.load: weights, adaptive latents, embedder
+        configuration, plus the task and the iteration count as metadata.  Not a checkpoint: state_dict() is the one to resume from."""
+        self.net.save(path, **{"task": self.task, "iterations": self.iteration, **meta})
+
     def psnr(self, region="known"):
         """-10 log10 MSE over known / unknown pixels against the clean image."""
         pred = self.render_image()

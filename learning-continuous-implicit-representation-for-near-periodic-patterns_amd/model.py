@@ -13,6 +13,37 @@ from ._lib import EmbedCfg, param_layout, NPP_E, NPP_WIDTH
 LATENT_ALPHA_INIT = 2.3841858e-07   # logit(0.5) in fp32 (robust_loss_pytorch/util.py:75-83)
 
 
+def _render_fn(precision):
+    if precision not in ("bf16", "fp32"):
+        raise ValueError(f"precision {precision!r}: 'bf16' (fused chain) or 'fp32' (exact chain)")
+    return "mlp_fwd" if precision == "bf16" else "mlp_fwd32"
+
+
+def _pair(v):
+    """One number or a pair -> (float, float)."""
+    a = np.asarray(v, dtype=np.float64).reshape(-1)
+    if a.size == 1:
+        a = np.repeat(a, 2)
+    if a.size != 2:
+        raise ValueError(f"expected one number or a pair, got {v!r}")
+    return float(a[0]), float(a[1])
+
+
+def canvas_coords(size, origin=(0.0, 0.0), scale=(1.0, 1.0), start=0, n=None):
+    """The fit-frame positions of canvas pixels [start, start + n) (row-major) of a size = (H', W') canvas, (n, 2) float32 [y, x]:
+    y = y0 + i / sy, x = x0 + j / sx as the grid launches form them -- an IEEE fp32 quotient, then a separate fp32 add.  So
+    NPPNet.render_at(canvas_coords(...)) is render_grid(...) bit for bit, and at an integer scale S the positions of pixels
+    (S i, S j) are the integers (y0 + i, x0 + j) exactly."""
+    Hc, Wc = (int(s) for s in size)
+    n = Hc * Wc - int(start) if n is None else int(n)
+    p = np.arange(int(start), int(start) + n, dtype=np.int64)
+    sy, sx = (np.float32(s) for s in _pair(scale))
+    y0, x0 = (np.float32(o) for o in _pair(origin))
+    y = y0 + (p // Wc).astype(np.float32) / sy
+    x = x0 + (p % Wc).astype(np.float32) / sx
+    return np.stack([y, x], 1).astype(np.float32)
+
+
 class NPPNet:
     """NPP_Net (K>1) / NPP_Net_top1 (K==1) with its embedders, optimiser state and the
     adaptive pixel-loss latents (the reference's module-level `adaptive_pix`,
@@ -133,11 +164,88 @@ class NPPNet:
         bp = ops.pad_rows(n)
         if bp != n:
             coords = torch.cat([coords, torch.zeros((bp - n, 2), dtype=torch.int32, device=coords.device)], 0)
+        return ops.mlp_fwd32(coords.contiguous(), self.cfg, self._w32_pack(), self.params, out_act=self.out_act, width=self.width)[:n]
+
+    # ---- rendering at continuous positions (include/npp_hip.h "continuous coordinates") -------------------------------
+    def _w32_pack(self):
+        """The fp32 weight pack of the exact chain (render_fp32, render_at / render_grid in fp32), rebuilt when the parameters have
+        changed since it was made."""
         stamp = (self.opt_step, self.params._version)
         if getattr(self, "_w32_stamp", None) != stamp:
             self._w32 = ops.pack_weights32(self.params, self.K, getattr(self, "_w32", None), self.width)
             self._w32_stamp = stamp
-        return ops.mlp_fwd32(coords.contiguous(), self.cfg, self._w32, self.params, out_act=self.out_act, width=self.width)[:n]
+        return self._w32
+
+    def render_at(self, coords, precision="bf16"):
+        """The network at arbitrary real positions: coords (N, 2) [row y, col x] in the fit's pixel frame (sub-pixel, negative and
+        past the border alike; a tensor or an array, converted to float32) -> (N, 3) on the device.  precision: 'bf16' (the fused
+        chain of render()) or 'fp32' (the exact chain of render_fp32())."""
+        fn = _render_fn(precision)
+        c = torch.as_tensor(coords).to(device=self.device, dtype=torch.float32)
+        if c.dim() != 2 or c.shape[1] != 2:
+            raise ValueError(f"coords: expected (N, 2), got {tuple(c.shape)}")
+        n = c.shape[0]
+        if n == 0:
+            return torch.empty((0, 3), dtype=torch.float32, device=self.device)
+        bp = ops.pad_rows(n)
+        if bp != n:
+            c = torch.cat([c, c.new_zeros((bp - n, 2))], 0)
+        w = self._w32_pack() if precision == "fp32" else self.wf
+        return getattr(ops, fn + "_coordf")(c.contiguous(), self.cfg, w, self.params, out_act=self.out_act, width=self.width)[:n]
+
+    def render_grid(self, size, origin=(0.0, 0.0), scale=(1.0, 1.0), precision="bf16", chunk_rows=1 << 22):
+        """A canvas of size = (H', W') pixels whose pixel (i, j) is the network at (y0 + i / sy, x0 + j / sx) of the fit's frame
+        (origin = (y0, x0); scale = (sy, sx) canvas pixels per fit pixel, or one number for both) -> (H', W', 3) float32 on the
+        device.  Chunked grid launches of at most chunk_rows pixels: no coordinate buffer is ever built.  Scale 1 at origin 0 is
+        render() of the full int32 grid bit for bit; at an integer scale S, pixel (S i, S j) is pixel (i, j) of scale 1."""
+        fn = _render_fn(precision)
+        Hc, Wc = (int(s) for s in size)
+        if Hc < 1 or Wc < 1:
+            raise ValueError(f"size {tuple(size)}: both sides must be >= 1")
+        if int(chunk_rows) < 1:
+            raise ValueError(f"chunk_rows {chunk_rows} must be >= 1")
+        sy, sx = _pair(scale)
+        y0, x0 = _pair(origin)
+        total = Hc * Wc
+        out = torch.empty((total, 3), dtype=torch.float32, device=self.device)
+        w = self._w32_pack() if precision == "fp32" else self.wf
+        launch = getattr(ops, fn + "_grid")
+        for s0 in range(0, total, int(chunk_rows)):
+            n = min(int(chunk_rows), total - s0)
+            launch(ops.grid_arg(s0, n, Wc, (y0, x0), (sy, sx)), self.cfg, w, self.params, out=out[s0:s0 + n], out_act=self.out_act,
+                   width=self.width)
+        return out.view(Hc, Wc, 3)
+
+    # ---- model file (modelfile.py) ---------------------------------------------------------
+    def embedder_config(self):
+        """(angles_deg (K, 2), periods (K, 2), freqs (10,), freq_offsets (5,), res (H, W)) as the embedder was built with."""
+        c = self.cfg
+        ang = np.array([[c.angles_deg[k][o] for o in range(2)] for k in range(self.K)], np.float32)
+        per = np.array([[c.periods[k][o] for o in range(2)] for k in range(self.K)], np.float32)
+        return ang, per, np.array(list(c.freqs), np.float32), np.array(list(c.offsets), np.float32), (int(c.H), int(c.W))
+
+    def save(self, path, **meta):
+        """Write the network as a model file (modelfile.py: weights under the reference's names, adaptive latents, embedder
+        configuration; meta: optional strings such as task / image / iterations)."""
+        from . import modelfile
+        ang, per, freqs, offs, res = self.embedder_config()
+        modelfile.write(path, self.state_dict(), self.latents.detach().cpu().numpy(), ang, per, freqs, res, self.width,
+                        out_act=self.out_act, freq_offsets=offs, **meta)
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        """An NPPNet from a model file, ready to render (no optimiser state: a fresh Adam if it were trained on).  .meta holds the
+        file's string metadata.  ValueError for a file that is not a model file this build reads."""
+        from . import modelfile
+        from ._lib import FUSED_WIDTHS
+        d = modelfile.read(path)
+        if d["width"] not in FUSED_WIDTHS:
+            raise ValueError(f"{path}: width {d['width']} has no fused library (built: {FUSED_WIDTHS})")
+        net = cls(d["angles_deg"], d["periods"], d["freqs"], d["res"], params=d["params"], device=device,
+                  offsets=tuple(float(o) for o in d["freq_offsets"]), width=d["width"], out_act=d["out_act"])
+        net.latents.copy_(torch.from_numpy(d["latents"]).to(net.device))
+        net.meta = dict(d["meta"])
+        return net
 
     def forward_train(self, coords_padded):
         """Forward with stashes; coords must already be padded to a multiple of 64 rows."""

@@ -155,6 +155,27 @@ def warp_fwd(coords, cfg):
     return out
 
 
+def embed_fwd_coordf(coords, cfg, out_dtype=torch.float32, precise=True):
+    """embed_fwd on (N,2) fp32 positions [row y, col x] of the fit's pixel frame (any real value: sub-pixel, negative, past the border)."""
+    _req(coords, torch.float32, "coords")
+    n = coords.shape[0]
+    out = torch.empty((n, cfg.K * NPP_E), dtype=out_dtype, device=coords.device)
+    code = {torch.float32: 0, torch.bfloat16: 1}[out_dtype]
+    check(lib().npp_embed_fwd_coordf(_p(coords), n, C.byref(cfg), _p(out), code, int(bool(precise)), _stream()),
+          "npp_embed_fwd_coordf")
+    return out
+
+
+def warp_fwd_coordf(coords, cfg):
+    """warp_fwd on (N,2) fp32 positions: Embedder_periodic.embed of a float tensor (embedder.py:140-148), the precise arithmetic of
+    warp_fwd."""
+    _req(coords, torch.float32, "coords")
+    n = coords.shape[0]
+    out = torch.empty((n, cfg.K * 22), dtype=torch.float32, device=coords.device)
+    check(lib().npp_warp_fwd_coordf(_p(coords), n, C.byref(cfg), _p(out), _stream()), "npp_warp_fwd_coordf")
+    return out
+
+
 def pack_bytes(K, which, width=NPP_WIDTH):
     n = lib(width).npp_pack_bytes(K, width, which)
     check(n, "npp_pack_bytes", width)
@@ -287,6 +308,59 @@ def mlp_fwd32(coords_yx, cfg, w32, params, out=None, out_act=1, width=NPP_WIDTH)
         out = torch.empty((Bp, 3), dtype=torch.float32, device=coords_yx.device)
     check(lib(width).npp_mlp_fwd32(_p(coords_yx), Bp, C.byref(cfg), width, _p(w32), _p(params), _p(out), int(out_act), _stream()),
           "npp_mlp_fwd32", width)
+    return out
+
+
+def mlp_fwd_coordf(coords, cfg, wf, params, out=None, out_act=1, width=NPP_WIDTH):
+    """Fused bf16 render on fp32 positions: coords (Bp,2) float32 [y, x], Bp % 64 == 0 -> (Bp,3)."""
+    _req(coords, torch.float32, "coords")
+    bp = coords.shape[0]
+    if out is None:
+        out = torch.empty((bp, 3), dtype=torch.float32, device=coords.device)
+    check(lib(width).npp_mlp_fwd_coordf(_p(coords), bp, C.byref(cfg), width, _p(wf), _p(params), _p(out), int(out_act), _stream()),
+          "npp_mlp_fwd_coordf", width)
+    return out
+
+
+def mlp_fwd32_coordf(coords, cfg, w32, params, out=None, out_act=1, width=NPP_WIDTH):
+    """Exact-fp32 render on fp32 positions: coords (Bp,2) float32 [y, x], Bp % 64 == 0 -> (Bp,3)."""
+    _req(coords, torch.float32, "coords")
+    bp = coords.shape[0]
+    if out is None:
+        out = torch.empty((bp, 3), dtype=torch.float32, device=coords.device)
+    check(lib(width).npp_mlp_fwd32_coordf(_p(coords), bp, C.byref(cfg), width, _p(w32), _p(params), _p(out), int(out_act), _stream()),
+          "npp_mlp_fwd32_coordf", width)
+    return out
+
+
+def grid_arg(start, n, canvas_width, origin=(0.0, 0.0), scale=(1.0, 1.0)):
+    """npp_grid: canvas pixels [start, start + n) of a canvas `canvas_width` wide, pixel (i, j) at (y0 + i / sy, x0 + j / sx)."""
+    from ._lib import Grid
+    return Grid(int(start), int(n), int(canvas_width), float(origin[0]), float(origin[1]), float(scale[0]), float(scale[1]))
+
+
+def _grid_out(out, n, device):
+    if out is None:
+        return torch.empty((n, 3), dtype=torch.float32, device=device)
+    _req(out, torch.float32, "out")
+    if out.dim() != 2 or out.shape[1] != 3 or out.shape[0] < n:
+        raise ValueError(f"out: expected at least ({n}, 3), got {tuple(out.shape)}")
+    return out
+
+
+def mlp_fwd_grid(grid, cfg, wf, params, out=None, out_act=1, width=NPP_WIDTH):
+    """Fused bf16 render of grid.n canvas pixels (grid: grid_arg(...)) -> out[:grid.n] (n, 3); no coordinate buffer, no padding."""
+    out = _grid_out(out, grid.n, params.device)
+    check(lib(width).npp_mlp_fwd_grid(C.byref(grid), C.byref(cfg), width, _p(wf), _p(params), _p(out), int(out_act), _stream()),
+          "npp_mlp_fwd_grid", width)
+    return out
+
+
+def mlp_fwd32_grid(grid, cfg, w32, params, out=None, out_act=1, width=NPP_WIDTH):
+    """Exact-fp32 render of grid.n canvas pixels -> out[:grid.n] (n, 3)."""
+    out = _grid_out(out, grid.n, params.device)
+    check(lib(width).npp_mlp_fwd32_grid(C.byref(grid), C.byref(cfg), width, _p(w32), _p(params), _p(out), int(out_act), _stream()),
+          "npp_mlp_fwd32_grid", width)
     return out
 
 

@@ -97,7 +97,9 @@ class Embedder_periodic:
         c = inputs
         if c.dtype != torch.int32:
             if c.is_floating_point() and not bool((c == c.round()).all()):
-                raise NotImplementedError("non-integer coordinates: the kernels take pixel indices (train.py:89-105 passes them)")
+                # sub-pixel / resampled positions (the module is a function of the plane): the same precise warp on fp32 positions
+                v = ops.warp_fwd_coordf(c.to(torch.float32).contiguous(), self.cfg)
+                return v if self.include_input else torch.cat([v[:, 1:11], v[:, 12:22]], 1).contiguous()
             c = c.to(torch.int32)
         v = ops.warp_fwd(c.contiguous(), self.cfg)                         # (N, 22): [x_n, 10 x orientation 0, y_n, 10 x orientation 1]
         if self.include_input:

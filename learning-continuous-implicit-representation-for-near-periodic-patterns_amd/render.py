@@ -1,0 +1,77 @@
+"""Render a saved NPP-Net (train.py --save_model -> model.npz) on any canvas: a denser grid than the image it was fitted to, a window
+that reaches past the image border (the periodic warps carry the pattern on), or both.
+
+    python -m npp_amd.render --model results/completion_top3/<name>/model.npz --out big.png --scale 2
+    python -m npp_amd.render --model M.npz --out ext.png --origin -256 -256 --size 723 837
+
+Canvas pixel (i, j) is the network at (y0 + i / sy, x0 + j / sx) of the fit's pixel frame (NPPNet.render_grid).  --size defaults to
+ceil(H sy) x ceil(W sx): the fit's own canvas at that density.  The PNG is written with the conversion of the test-set dumps
+(io.imsave: clip to [0, 1], round to 8 bit); --npy keeps the float32 values."""
+import argparse
+import math
+import os
+import sys
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m npp_amd.render", description=__doc__.split("\n")[0])
+    ap.add_argument("--model", required=True, help="model file written by `python -m npp_amd.train --save_model`")
+    ap.add_argument("--out", required=True, help="output image (PNG)")
+    ap.add_argument("--scale", type=float, nargs="+", default=[1.0], metavar="S",
+                    help="canvas pixels per fit pixel: one value, or SY SX (default 1)")
+    ap.add_argument("--origin", type=float, nargs=2, default=[0.0, 0.0], metavar=("Y0", "X0"),
+                    help="fit-frame position of canvas pixel (0, 0) (default 0 0)")
+    ap.add_argument("--size", type=int, nargs=2, default=None, metavar=("H", "W"), help="canvas size (default ceil(H sy) x ceil(W sx))")
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"], help="bf16: the fused chain of the fit; fp32: the exact chain")
+    ap.add_argument("--npy", default=None, help="also write the (H, W, 3) float32 canvas as .npy")
+    ap.add_argument("--chunk_rows", type=int, default=1 << 22, help="canvas pixels per launch")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+    if len(args.scale) not in (1, 2):
+        ap.error("--scale takes one value S or two values SY SX")
+    sy, sx = (args.scale * 2)[:2]
+    if not all(math.isfinite(s) and s > 0 for s in (sy, sx)):
+        ap.error(f"--scale {args.scale}: must be finite and > 0")
+    if not all(math.isfinite(o) for o in args.origin):
+        ap.error(f"--origin {args.origin}: must be finite")
+    if args.size is not None and min(args.size) < 1:
+        ap.error(f"--size {args.size}: both sides must be >= 1")
+    if args.chunk_rows < 1:
+        ap.error(f"--chunk_rows {args.chunk_rows}: must be >= 1")
+    args.scale = (sy, sx)
+    return args, ap
+
+
+def main(argv=None):
+    """-> the rendered canvas, (H, W, 3) float32 NumPy.  Every argument and the model file are checked before the GPU is touched."""
+    args, ap = parse(argv)
+    from . import modelfile
+    if not os.path.isfile(args.model):
+        ap.error(f"--model {args.model}: no such file")
+    try:
+        d = modelfile.read(args.model)
+    except ValueError as e:
+        ap.error(f"--model: {e}")
+    sy, sx = args.scale
+    H, W = d["res"]
+    size = tuple(args.size) if args.size is not None else (math.ceil(H * sy), math.ceil(W * sx))
+    out_dir = os.path.dirname(os.path.abspath(args.out))
+    if not os.path.isdir(out_dir):
+        ap.error(f"--out {args.out}: directory {out_dir} does not exist")
+
+    from . import io as nio
+    from .model import NPPNet
+    net = NPPNet.load(args.model, device=args.device)
+    img = net.render_grid(size, origin=tuple(args.origin), scale=(sy, sx), precision=args.precision, chunk_rows=args.chunk_rows)
+    img = img.cpu().numpy()
+    nio.imsave(args.out, img)               # what dump_testset writes as pred_rgb_img.png (a tanh output is clipped there too)
+    if args.npy:
+        import numpy as np
+        np.save(args.npy, img)
+    print(f"rendered {size[0]} x {size[1]} ({args.precision}) at scale ({sy:g}, {sx:g}), origin ({args.origin[0]:g}, {args.origin[1]:g}) "
+          f"of a {H} x {W} fit -> {args.out}")
+    return img
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

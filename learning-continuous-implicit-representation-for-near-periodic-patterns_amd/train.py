@@ -77,6 +77,8 @@ def parse(argv=None):
                     help="run WITHOUT pretrained VGG19 / VGG16 / LPIPS-lin weights (fixed-seed random trunks: synthetic and bench "
                          "runs only -- the losses then differ from the reference's)")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--save_model", action="store_true",
+                    help="after a successful fit, write the network as model.npz into the image's result directory (npp_amd.render reads it)")
     return ap.parse_args(argv)
 
 
@@ -217,6 +219,12 @@ def _finish(job, failed):
     (Ctrl-C) keeps the test sets it has already written.  Raises a writer's error when the loop itself succeeded."""
     write_error = None
     job.fit.close()                                         # the sampler's producer thread
+    if failed is None and job.args.save_model:              # --save_model: the fitted network, before the fit is released
+        try:
+            job.fit.save_model(os.path.join(job.outroot, "model.npz"), image=job.name, iterations=job.args.N_iters - 1)
+        except Exception as e:
+            write_error = e
+            print(f"[WARN] writing the model file failed: {e}")
     # first the writers: a queued dump_testset re-creates its directory (os.makedirs(..., exist_ok=True)), so nothing is
     # removed while one may still run
     for p in job.pending:
