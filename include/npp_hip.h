@@ -773,7 +773,9 @@ int npp_lpips_plain_layer(const float* d_f0, const float* d_f1, int N, int C, in
                           float scale, float* d_out, void* stream);
 /* The same with the workgroups' partial sums added in block order instead of by float atomics (the candidate SCORES that rank the
  * proposals, NPP_proposal/search.py:193, are then bit-reproducible): d_scratch = NPP_LPIPS_PLAIN_SCRATCH_FLOATS floats, zeroed once by
- * the caller (each launch re-arms it); launches that may run concurrently need scratches of their own. */
+ * the caller.  Layout: 256 partial-sum slots (a launch uses the first min(256, ceil(N hw / 16))), then the arrival counter at the
+ * fixed slot 256, which every launch leaves at zero: one scratch serves successive launches of any (N, hw).  Launches that may
+ * run concurrently need scratches of their own. */
 #define NPP_LPIPS_PLAIN_SCRATCH_FLOATS 264
 int npp_lpips_plain_layer_det(const float* d_f0, const float* d_f1, int N, int C, int hw, const float* d_lin, float scale, float* d_out,
                               float* d_scratch, void* stream);

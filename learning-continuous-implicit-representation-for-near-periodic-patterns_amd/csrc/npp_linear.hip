@@ -273,10 +273,14 @@ __global__ void act_fwd_kernel(const float* __restrict__ x, int64_t n, int act, 
   y[t] = act == 2 ? 1.0f / (1.0f + expf(-v)) : (act == 3 ? tanhf(v) : v);
 }
 
+constexpr int LPIPS_PLAIN_MAX_BLOCKS = 256;   // the grid cap = the partial-sum slots; the counter sits behind them
+static_assert(LPIPS_PLAIN_MAX_BLOCKS + 1 <= NPP_LPIPS_PLAIN_SCRATCH_FLOATS, "the plain LPIPS scratch holds 256 partials + the counter");
 // LPIPS.forward(use_robust=False), one tap (lpips.py:99-101,110,117,130): sum over (n, pos) of
 // sum_c lin_c (f0_c / (|f0| + eps) - f1_c / (|f1| + eps))^2, scaled by coef.  16 positions x 16 channel lanes per block.
-// scratch (nullable): [gridDim.x partial sums | arrival counter], zero before the first launch that uses it -- the block that arrives
-// last adds the partials in block order (bit-reproducible score); null: one float atomicAdd per block
+// scratch (nullable): NPP_LPIPS_PLAIN_SCRATCH_FLOATS floats = [256 partial-sum slots, the first gridDim.x <= 256 used | arrival counter
+// at the FIXED slot 256, whatever the grid], counter zero before the first launch that uses it; the last block's wrap-around re-arms
+// it, so one scratch serves launches of any shape one after the other -- the block that arrives last adds the partials in block
+// order (bit-reproducible score); null: one float atomicAdd per block
 __global__ __launch_bounds__(256) void lpips_plain_kernel(const float* __restrict__ f0, const float* __restrict__ f1, int N, int C, int hw,
                                                           const float* __restrict__ lin, float coef, float* __restrict__ out, float* scratch) {
   __shared__ float red[2][16][17];
@@ -319,7 +323,7 @@ __global__ __launch_bounds__(256) void lpips_plain_kernel(const float* __restric
     return;
   }
   if (threadIdx.x == 0) share_store(scratch + blockIdx.x, coef * (tot[0] + tot[1] + tot[2] + tot[3]));
-  if (block_last_arriver((unsigned*)(scratch + gridDim.x), (int)gridDim.x) && threadIdx.x == 0) {
+  if (block_last_arriver((unsigned*)(scratch + LPIPS_PLAIN_MAX_BLOCKS), (int)gridDim.x) && threadIdx.x == 0) {
     float s = 0.0f;
     for (unsigned b = 0; b < gridDim.x; ++b) s += share_load(scratch + b);
     *out += s;                                   // (the taps of a score are consecutive launches on one stream: one writer at a time)
@@ -693,7 +697,8 @@ extern "C" int npp_lpips_plain_layer(const float* d_f0, const float* d_f1, int N
   return lpips_plain_go(d_f0, d_f1, N, C, hw, d_lin, scale, d_out, nullptr, stream);
 }
 // the same with the blocks' partial sums added in block order (bit-reproducible): d_scratch = NPP_LPIPS_PLAIN_SCRATCH_FLOATS floats,
-// zeroed once by the caller (the launch re-arms it), not shared by launches that may run concurrently
+// zeroed once by the caller; every launch leaves the arrival counter (slot 256, independent of the grid) at zero again, so one scratch
+// serves successive launches of ANY (N, hw); the partial-sum slots need no content.  Not shared by launches that may run concurrently
 extern "C" int npp_lpips_plain_layer_det(const float* d_f0, const float* d_f1, int N, int C, int hw, const float* d_lin, float scale,
                                          float* d_out, float* d_scratch, void* stream) {
   if (!d_scratch) { set_error("npp_lpips_plain_layer_det: null scratch"); return NPP_ERR_ARG; }
@@ -706,8 +711,9 @@ static int lpips_plain_go(const float* d_f0, const float* d_f1, int N, int C, in
     return NPP_ERR_ARG;
   }
   const int64_t groups = ((int64_t)N * hw + 15) / 16;
-  hipLaunchKernelGGL(lpips_plain_kernel, dim3((unsigned)(groups < 256 ? groups : 256)), dim3(256), 0, (hipStream_t)stream, d_f0, d_f1, N, C,
-                     hw, d_lin, scale / (float)hw, d_out, d_scratch);
+  const unsigned blocks = (unsigned)(groups < LPIPS_PLAIN_MAX_BLOCKS ? groups : LPIPS_PLAIN_MAX_BLOCKS);
+  hipLaunchKernelGGL(lpips_plain_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_f0, d_f1, N, C, hw, d_lin, scale / (float)hw, d_out,
+                     d_scratch);
   return check_launch("npp_lpips_plain_layer");
 }
 

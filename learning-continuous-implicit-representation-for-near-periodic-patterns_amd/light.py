@@ -903,6 +903,16 @@ class ProposalRanker:
         return d[order], order, details
 
 
+def _serial_members(B, n):
+    """The most chains (<= n) of B rows that one launch may carry with the block height -- hence the per-block partial sums -- of a
+    single chain's launch.  The rule itself lives in the library (light_rows_per_wg); this only asks it."""
+    alone = ops.light_part_blocks(1, B)
+    c = 1
+    while c < n and ops.light_part_blocks(c + 1, B) == alone:
+        c += 1
+    return c
+
+
 @torch.no_grad()
 def rank_images(rankers, cand_lists, topk=10):
     """ProposalRanker.rank for SEVERAL images of one rank at once: candidate k of every image rides in one launch
@@ -912,7 +922,9 @@ def rank_images(rankers, cand_lists, topk=10):
     single-rank default) the candidates of ONE image are a chain, but the chains of different images are independent: 9 x 300
     iterations of ~0.1 ms are then paid once for all the images instead of once per image.
     Per image the arithmetic is that of the serial deterministic loop (same launches, same block and summation order per candidate:
-    identical bits).  Images must share the fit's hyper-parameters; they are grouped by batch rows (min(N_rand, known pixels)).
+    identical bits).  The fp32 backward pass switches to taller blocks beyond a number of chains per launch (24 at B = 2048), which
+    would change the tree of the per-block loss sums: a group larger than that is walked in chunks that stay below the switch.
+    Images must share the fit's hyper-parameters; they are grouped by batch rows (min(N_rand, known pixels)).
     -> per image (sorted distances, order, per-candidate details), like ProposalRanker.rank."""
     if not rankers:
         return []
@@ -930,7 +942,13 @@ def rank_images(rankers, cand_lists, topk=10):
     for i, rk in enumerate(rankers):
         groups.setdefault(min(rk.N_rand, rk.i_train.shape[0]), []).append(i)
     init = default_light_init(r0.Wn, r0.D)
+    chunks = []
     for B, members in groups.items():
+        # fp32: the backward pass sums the folded loss per block, and the block height follows the number of chains in the launch
+        # (ops.light_part_blocks): a launch stays on the serial loop's side of that switch, or the sums take another tree
+        cap = len(members) if bf16 or B % 32 else _serial_members(B, len(members))
+        chunks += [(B, members[m0:m0 + cap]) for m0 in range(0, len(members), cap)]
+    for B, members in chunks:
         if B % (64 if bf16 else 32) or len(members) == 1 or (bf16 and len(members) > 16):   # a batch the fused chains do not take, or nothing to stack: the image's own loop
             for i in members:
                 d, order, det = rankers[i].rank(cand_lists[i], topk=topk)

@@ -1098,7 +1098,9 @@ LPIPS_PLAIN_SCRATCH = 264               # NPP_LPIPS_PLAIN_SCRATCH_FLOATS (includ
 
 
 def lpips_plain_layer(f0, f1, lin, scale, out, scratch=None):
-    """scratch (LPIPS_PLAIN_SCRATCH zeroed floats, one per tap launched back to back): the fixed-order, bit-reproducible form."""
+    """scratch (LPIPS_PLAIN_SCRATCH floats, zeroed once, one per tap launched back to back): the fixed-order, bit-reproducible form.
+    The kernel keeps its arrival counter at the fixed slot 256 and leaves it at zero, so a scratch may be re-used by later
+    launches of any (N, h, w); it must not be shared by launches that may run concurrently."""
     _req(f0, torch.float32, "f0")
     _req(f1, torch.float32, "f1", f0.shape)
     N, C = f0.shape[:2]

@@ -83,6 +83,16 @@ def test_stash8_switch_and_its_host_side_checks():
     assert L.npp_light_part_blocks(9, 100) < 0 and L.npp_light_part_blocks(9, 2048) in (32, 64) and L.npp_light_part_blocks(64, 2048) == 32
 
 
+def test_plain_lpips_scratch_size_is_the_same_in_the_header_and_in_ops():
+    """NPP_LPIPS_PLAIN_SCRATCH_FLOATS (include/npp_hip.h) and ops.LPIPS_PLAIN_SCRATCH are written down twice by hand: 256 partial-sum
+    slots, then the arrival counter at slot 256 (csrc/npp_linear.hip lpips_plain_kernel) -- a smaller Python value would put the
+    counter behind the allocation."""
+    from npp_amd import ops
+    with open(os.path.join(ROOT, "include", "npp_hip.h")) as f:
+        m = re.findall(r"^#define\s+NPP_LPIPS_PLAIN_SCRATCH_FLOATS\s+(\d+)\s*$", f.read(), re.M)
+    assert len(m) == 1 and int(m[0]) == ops.LPIPS_PLAIN_SCRATCH and ops.LPIPS_PLAIN_SCRATCH > 256
+
+
 def test_light_chain_entry_points_validate_on_the_host():
     """The fused NPP_Net_light entry points refuse topologies / shapes they are not built for before anything is launched (no GPU
     needed to see it), and their layout queries are consistent."""
