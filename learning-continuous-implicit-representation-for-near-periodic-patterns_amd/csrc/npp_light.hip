@@ -16,7 +16,7 @@
 // tile is 32 consecutive rows of one feature -- a coalesced 128-byte store -- and the weight-gradient GEMMs (npp_linear.hip,
 // batched, strided operands) take both operands contiguous along the rows they contract.
 #include "npp_chain32.h"
-#include "npp_light_layout.h"
+#include "npp_light_common.h"
 
 namespace npp {
 
@@ -24,8 +24,6 @@ constexpr int light_region_bytes(int nb) { return kLHp * nb * 32 * 4; }   // the
 constexpr int kLThreads = 256;
 
 // packed weights of one candidate (16-byte units): forward pack, then the transposed pack of the backward chain
-enum { LF_L0 = 0, LF_L1, LF_L2, LF_L3, LF_F1, LF_POS, LF_N };
-enum { LB_POS = 0, LB_F1, LB_L3, LB_L2, LB_L1, LB_N };
 struct LightPackDesc {
   int32_t f_off[LF_N], f_groups[LF_N], f_nt[LF_N];
   int32_t b_off[LB_N], b_groups[LB_N];
@@ -56,12 +54,9 @@ struct LightArgs {
   float* dstash;                                // (C, LD_ROWS, B)  backward only
   int64_t B;
   const int64_t* idx; int64_t n_src;            // forward: rows idx[r] of x_per (C, n_src, 20) / x_pos (n_src, 42); idx null: rows r, n_src = B
-  const float* gt;                              // backward with the pixel loss folded in: targets (B, 3) ... (null: d pred is an input)
-  const float* latents; const float* spline; int n_knots; float x_scale;      // ... its adaptive-loss latents (C, 6) and spline table
-  float* loss; float* dlatent;                  // ... and where the loss words (C) / latent gradients (C, 6) accumulate
-  float* part;                                  // npp_light_bwd_det: (C, blocks, 8) -- every block leaves its seven sums here instead (no atomics)
-  // "multi" forms (candidate = one IMAGE's fit: its own pixel rows, positional table and targets): elements per candidate, 0 = shared
-  int64_t x_pos_cs, idx_cs, gt_cs;
+  LightLossArgs lo;                             // backward: the pixel loss folded in
+  // "multi" forms (candidate = one IMAGE's fit: its own pixel rows and positional table): elements per candidate, 0 = shared
+  int64_t x_pos_cs, idx_cs;
 };
 
 // ---- packs ----------------------------------------------------------------------------------------------------------------
@@ -80,9 +75,7 @@ __global__ void light_pack_kernel(LightArgs a, LightPackDesc pd, float* __restri
   const int lane = r & 63, nt = (r >> 6) % nt_n, g = (r >> 6) / nt_n;
   const int row = nt * 32 + (lane & 31), h = lane >> 5;
   // source matrix (out x in, leading dimension ld) of this pack entry
-  const int fwd_layer[LF_N] = {0, 1, 2, 3, 5, 4};          // npp_light_desc index: periodic 0..3, pos (4), feature1 (5), rgb (6)
-  const int bwd_layer[LB_N] = {4, 5, 3, 2, 1};
-  const int li = bwd ? bwd_layer[l] : fwd_layer[l];
+  const int li = bwd ? light_bwd_layer(l) : light_fwd_layer(l);
   const float* Wm = P + a.L.w_off[li];
   const int ld = a.L.ld[li], n_out = a.L.n_out[li], n_in = a.L.n_in[li];
   f32x4_t o;
@@ -105,35 +98,19 @@ struct LightAdamArgs {
   npp_light_desc L;
   float *p, *m, *v, *g; int64_t stride; int32_t n;         // (C, stride) blobs, n live floats per candidate
   float* pack; int64_t pack_stride;
-  float *lat, *lat_m, *lat_v, *dlat, *zero;               // (C, 6) x 4, (C)
-  float step_size, b1, b2, inv_sqrt_bc2, eps;
-  const float* part; int32_t n_part; float* loss_cur;     // npp_light_adam_pack_det: the blocks' partial sums, added here in block order
+  LightLatentArgs t;                                       // latents, Adam's scalars, npp_light_adam_pack_det's partial sums
 };
 __global__ __launch_bounds__(256) void light_adam_pack_kernel(LightAdamArgs a, LightPackDesc pd) {
   const int c = blockIdx.y;
   if (blockIdx.x == gridDim.x - 1) {
-    const int t = threadIdx.x;
-    if (t < 6) {
-      const int i = c * 6 + t;
-      float g = a.dlat[i];
-      if (a.part)                                             // fixed order: bit-reproducible latent gradients
-        for (int b = 0; b < a.n_part; ++b) g += a.part[((int64_t)c * a.n_part + b) * 8 + 1 + t];
-      float m = a.lat_m[i], v = a.lat_v[i];
-      a.lat[i] = adam_update(a.lat[i], m, v, g, a.step_size, a.b1, a.b2, a.inv_sqrt_bc2, a.eps);
-      a.lat_m[i] = m; a.lat_v[i] = v; a.dlat[i] = 0.0f;
-    } else if (t == 6 && a.zero) a.zero[c] = 0.0f;
-    else if (t == 64 && a.part && a.loss_cur) {               // (another wave: the two sums run side by side)
-      float l = 0.0f;
-      for (int b = 0; b < a.n_part; ++b) l += a.part[((int64_t)c * a.n_part + b) * 8];
-      a.loss_cur[c] += l;
-    }
+    light_latent_step(a.t, c);
     return;
   }
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n) return;
   const int64_t gi = (int64_t)c * a.stride + i;
   float m = a.m[gi], v = a.v[gi];
-  const float w = adam_update(a.p[gi], m, v, a.g[gi], a.step_size, a.b1, a.b2, a.inv_sqrt_bc2, a.eps);
+  const float w = adam_update(a.p[gi], m, v, a.g[gi], a.t.step_size, a.t.b1, a.t.b2, a.t.inv_sqrt_bc2, a.t.eps);
   a.p[gi] = w; a.m[gi] = m; a.v[gi] = v; a.g[gi] = 0.0f;
   // which weight is this?  (biases and rgb_linear are read from the blob by the chains: nothing to scatter)
   int li = -1;
@@ -144,11 +121,11 @@ __global__ __launch_bounds__(256) void light_adam_pack_kernel(LightAdamArgs a, L
   const int off = i - (int)a.L.w_off[li], ld = a.L.ld[li];
   const int row = off / ld, col = off - row * ld;
   float* pk = a.pack + (int64_t)c * a.pack_stride;
-  const int lf = li < 4 ? LF_L0 + li : (li == 4 ? LF_POS : LF_F1);
+  const int lf = light_fwd_entry(li);
   if (col < pd.f_groups[lf] * 8)
     pk[(int64_t)(pd.f_off[lf] + ((col >> 3) * pd.f_nt[lf] + (row >> 5)) * 64 + ((col & 7) >> 2) * 32 + (row & 31)) * 4 + (col & 3)] = w;
   if (li >= 1 && col < kLW) {                                  // transposed pack: A[m = col][k = row]
-    const int lb = li == 4 ? LB_POS : (li == 5 ? LB_F1 : (li == 3 ? LB_L3 : (li == 2 ? LB_L2 : LB_L1)));
+    const int lb = light_bwd_entry(li);
     pk[(int64_t)(pd.b_off[lb] + ((row >> 3) * 8 + (col >> 5)) * 64 + ((row & 7) >> 2) * 32 + (col & 31)) * 4 + (row & 3)] = w;
   }
 }
@@ -335,75 +312,12 @@ __global__ __launch_bounds__(kLThreads, NB == 2 ? 2 : 3) void light_bwd_kernel(L
   const float* S = a.stash + (int64_t)c * LS_ROWS * B;
   float* D = a.dstash + (int64_t)c * LD_ROWS * B;
   const int nt0 = 2 * wave;
-  // d raw = d pred * pred (1 - pred); with the pixel loss folded in (a.gt): d pred = d img2mse(robust_loss_adaptive)/d pred right here
-  // (models/mse_calculator.py:13-27 without a mask: the arithmetic of pixel_loss_body, npp_common.h), loss / latent gradients by atomics
-  __shared__ ChanParams cp[3];
-  __shared__ float sred[7];
-  __shared__ float swv[kLThreads / 64][7];
-  if (a.gt) {
-    if (tid < 3) cp[tid] = chan_params(a.latents[c * 6 + tid], a.latents[c * 6 + 3 + tid], a.spline, a.n_knots, a.x_scale);
-    if (tid < 7) sred[tid] = 0.0f;
-    wg_barrier();
-  }
-  float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;                 // this thread's loss term and latent-gradient terms (channel tid % 3)
-  if (tid < RT * 3) {
-    const int64_t g = ((int64_t)c * B + row0) * 3 + tid;
-    const float p = a.pred[g];
-    float dp;
-    if (a.gt) {
-      const int ch = tid % 3;
-      const ChanParams q = cp[ch];
-      const float inv = 1.0f / (3.0f * (float)B);
-      const float x = p - a.gt[c * a.gt_cs + row0 * 3 + tid];
-      const float xs = x / q.c, ssx = xs * xs;
-      const float u = ssx / q.beta + 1.0f, e = 0.5f * q.alpha, lnu = logf(u);
-      const float ue = expf(e * lnu), ue1 = ue / u;
-      dp = inv * (x / (q.c * q.c)) * ue1;
-      t0 = (q.beta / q.alpha) * (ue - 1.0f) + q.logc_plus_logz;
-      t1 = -(2.0f / (q.alpha * q.alpha)) * (ue - 1.0f) + (q.beta / q.alpha) * ue * (0.5f * lnu + e * ssx / (q.beta * q.beta * u)) + q.dlogz;
-      t2 = -(x * x) / (q.c * q.c * q.c) * ue1 + 1.0f / q.c;
-      if (!a.part) {
-        atomicAdd(&sred[0], t0);
-        atomicAdd(&sred[1 + ch], t1);
-        atomicAdd(&sred[4 + ch], t2);
-      }
-    } else {
-      dp = a.dpred[g];
-    }
-    const float d = dp * p * (1.0f - p);
+  // d raw = d pred * pred (1 - pred), the pixel loss folded in (light_loss_head): kept three ways
+  light_loss_head<kLThreads, RT>(a.lo, a.pred, a.dpred, c, B, row0, blockIdx.x, gridDim.x, [&](int64_t g, float d) {
     a.draw[g] = d;
     sD[tid] = d;
     D[(int64_t)(LD_RAW + tid % 3) * B + row0 + tid / 3] = d;       // d raw^T for rgb_linear's weight gradient
-  }
-  if (a.gt && a.part) {
-    // deterministic form (every wave, whole: threads past the 3 RT values carry zeros): the seven sums of a wave by shuffle
-    // butterflies -- a fixed tree, masked-out lanes add exact zeros -- then the waves' results in wave order
-    const int ch = tid % 3;
-    const float v7[7] = {t0, ch == 0 ? t1 : 0.0f, ch == 1 ? t1 : 0.0f, ch == 2 ? t1 : 0.0f, ch == 0 ? t2 : 0.0f, ch == 1 ? t2 : 0.0f, ch == 2 ? t2 : 0.0f};
-#pragma unroll
-    for (int k7 = 0; k7 < 7; ++k7) {
-      float v = v7[k7];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      if (lane == 0) swv[wave][k7] = v;
-    }
-  }
-  wg_barrier();
-  if (a.gt && tid < 7) {
-    const float inv = 1.0f / (3.0f * (float)B);
-    if (a.part) {
-      float v = 0.0f;
-#pragma unroll
-      for (int w_ = 0; w_ < kLThreads / 64; ++w_) v += swv[w_][tid];                        // wave order
-      const float o = tid == 0 ? v * inv : (tid < 4 ? inv * v * cp[tid - 1].dalpha_dl : inv * v * cp[tid - 4].dc_dl);
-      a.part[((int64_t)c * gridDim.x + blockIdx.x) * 8 + tid] = o;                          // summed in block order by npp_light_adam_pack_det
-    } else {
-      const float v = sred[tid];
-      if (tid == 0) atomicAdd(a.loss + c, v * inv);
-      else if (tid < 4) atomicAdd(a.dlatent + c * 6 + (tid - 1), inv * v * cp[tid - 1].dalpha_dl);
-      else atomicAdd(a.dlatent + c * 6 + 3 + (tid - 4), inv * v * cp[tid - 4].dc_dl);
-    }
-  }
+  });
   // d a_p = d raw W_rgb; d z_p = d a_p * snake'(z_p) -> region rows 0..127 + stash
   {
     const float* Wr = P + a.L.w_off[6];
@@ -457,14 +371,7 @@ static int light_check(const npp_light_desc* L, const void* p0, const void* p1, 
     set_error("%s: bad argument (C=%d B=%lld; B a positive multiple of 32)", who, C, (long long)B);
     return NPP_ERR_ARG;
   }
-  const int n_out[7] = {kLW, kLW, kLW, kLW, kLPosOut, kLW, 3}, n_in[7] = {kLPer, kLW, kLW, kLW, kLW + kLPos, kLW, kLPosOut};
-  for (int i = 0; i < 7; ++i)
-    if (L->n_out[i] != n_out[i] || L->n_in[i] != n_in[i] || L->ld[i] < n_in[i] || L->w_off[i] < 0 || L->b_off[i] < 0) {
-      set_error("%s: layer %d is %d x %d (ld %d): this build fuses NPP_Net_light(D=4, W=256) with 20 / 42 input columns only", who, i,
-                L->n_out[i], L->n_in[i], L->ld[i]);
-      return NPP_ERR_UNSUPPORTED;
-    }
-  return NPP_OK;
+  return light_topology_check(L, who);
 }
 
 // Rows per workgroup: 64 (two batch tiles share every weight fragment) or 32.  A chain is one long dependent sequence per workgroup
@@ -549,7 +456,30 @@ extern "C" int npp_light_part_blocks(int C, int64_t B) { return (C < 1 || B < 32
 static int light_bwd_go(const npp_light_desc* L, const float* d_params, int64_t params_stride, const float* d_pack, int64_t pack_stride,
                         const float* d_stash, const float* d_pred, const float* d_dpred, const float* d_gt, const float* d_latents,
                         const float* d_spline, int n_knots, float x_scale, float* d_loss, float* d_dlatent, int C, int64_t B,
-                        float* d_draw, float* d_dstash, float* d_part, void* stream, int64_t gt_cs = 0);
+                        float* d_draw, float* d_dstash, float* d_part, void* stream, int64_t gt_cs = 0) {
+  int rc = light_check(L, d_params, d_pack, C, B, "npp_light_bwd");
+  if (rc) return rc;
+  if (!d_stash || !d_pred || !d_draw || !d_dstash || (d_gt ? (!d_latents || !d_spline || n_knots < 2 || !d_loss || !d_dlatent) : !d_dpred)) {
+    set_error("npp_light_bwd: null argument (d_dpred, or d_gt with latents / spline / loss / dlatent)");
+    return NPP_ERR_ARG;
+  }
+  LightArgs a{};
+  a.L = *L; a.params = d_params; a.params_stride = params_stride; a.pack = d_pack; a.pack_stride = pack_stride;
+  a.stash = (float*)d_stash; a.pred = (float*)d_pred; a.dpred = d_dpred; a.draw = d_draw; a.dstash = d_dstash; a.B = B;
+  a.lo = LightLossArgs{d_gt, d_latents, d_spline, n_knots, x_scale, d_loss, d_dlatent, d_part, gt_cs};
+  if (light_rows_per_wg(C, B, true) == 64) {
+    static SmemOnce once;
+    if (!smem_attr(once, (const void*)light_bwd_kernel<2>, light_region_bytes(2))) { set_error("npp_light_bwd: smem attribute"); return NPP_ERR_LAUNCH; }
+    hipLaunchKernelGGL(light_bwd_kernel<2>, dim3((unsigned)(B / 64), (unsigned)C), dim3(kLThreads), light_region_bytes(2), (hipStream_t)stream, a,
+                       light_pack_desc());
+  } else {
+    static SmemOnce once;
+    if (!smem_attr(once, (const void*)light_bwd_kernel<1>, light_region_bytes(1))) { set_error("npp_light_bwd: smem attribute"); return NPP_ERR_LAUNCH; }
+    hipLaunchKernelGGL(light_bwd_kernel<1>, dim3((unsigned)(B / 32), (unsigned)C), dim3(kLThreads), light_region_bytes(1), (hipStream_t)stream, a,
+                       light_pack_desc());
+  }
+  return check_launch("npp_light_bwd");
+}
 
 extern "C" int npp_light_bwd(const npp_light_desc* L, const float* d_params, int64_t params_stride, const float* d_pack, int64_t pack_stride,
                              const float* d_stash, const float* d_pred, const float* d_dpred, const float* d_gt, const float* d_latents,
@@ -579,38 +509,24 @@ extern "C" int npp_light_bwd_det_multi(const npp_light_desc* L, const float* d_p
                       d_part, d_part, C, B, d_draw, d_dstash, d_part, stream, B * 3);
 }
 
-static int light_bwd_go(const npp_light_desc* L, const float* d_params, int64_t params_stride, const float* d_pack, int64_t pack_stride,
-                        const float* d_stash, const float* d_pred, const float* d_dpred, const float* d_gt, const float* d_latents,
-                        const float* d_spline, int n_knots, float x_scale, float* d_loss, float* d_dlatent, int C, int64_t B,
-                        float* d_draw, float* d_dstash, float* d_part, void* stream, int64_t gt_cs) {
-  int rc = light_check(L, d_params, d_pack, C, B, "npp_light_bwd");
-  if (rc) return rc;
-  if (!d_stash || !d_pred || !d_draw || !d_dstash || (d_gt ? (!d_latents || !d_spline || n_knots < 2 || !d_loss || !d_dlatent) : !d_dpred)) {
-    set_error("npp_light_bwd: null argument (d_dpred, or d_gt with latents / spline / loss / dlatent)");
-    return NPP_ERR_ARG;
-  }
-  LightArgs a{};
-  a.L = *L; a.params = d_params; a.params_stride = params_stride; a.pack = d_pack; a.pack_stride = pack_stride;
-  a.stash = (float*)d_stash; a.pred = (float*)d_pred; a.dpred = d_dpred; a.draw = d_draw; a.dstash = d_dstash; a.B = B;
-  a.gt = d_gt; a.latents = d_latents; a.spline = d_spline; a.n_knots = n_knots; a.x_scale = x_scale; a.loss = d_loss; a.dlatent = d_dlatent;
-  a.part = d_part; a.gt_cs = gt_cs;
-  if (light_rows_per_wg(C, B, true) == 64) {
-    static SmemOnce once;
-    if (!smem_attr(once, (const void*)light_bwd_kernel<2>, light_region_bytes(2))) { set_error("npp_light_bwd: smem attribute"); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL(light_bwd_kernel<2>, dim3((unsigned)(B / 64), (unsigned)C), dim3(kLThreads), light_region_bytes(2), (hipStream_t)stream, a,
-                       light_pack_desc());
-  } else {
-    static SmemOnce once;
-    if (!smem_attr(once, (const void*)light_bwd_kernel<1>, light_region_bytes(1))) { set_error("npp_light_bwd: smem attribute"); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL(light_bwd_kernel<1>, dim3((unsigned)(B / 32), (unsigned)C), dim3(kLThreads), light_region_bytes(1), (hipStream_t)stream, a,
-                       light_pack_desc());
-  }
-  return check_launch("npp_light_bwd");
-}
-
 static int light_adam_go(const npp_light_desc* L, float* d_params, float* d_m, float* d_v, float* d_grad, int64_t stride, int64_t n, int C,
                          float* d_pack, int64_t pack_stride, float* d_lat, float* d_lat_m, float* d_lat_v, float* d_dlat, float* d_zero,
-                         float lr, float beta1, float beta2, float eps, int step, const float* d_part, int n_part, float* d_loss_cur, void* stream);
+                         float lr, float beta1, float beta2, float eps, int step, const float* d_part, int n_part, float* d_loss_cur, void* stream) {
+  int rc = light_check(L, d_params, d_pack, C, 32, "npp_light_adam_pack");
+  if (rc) return rc;
+  const LightPackDesc pd = light_pack_desc();
+  if (!d_m || !d_v || !d_grad || !d_lat || !d_lat_m || !d_lat_v || !d_dlat || n < 1 || n > stride || n > 0x7fffffffLL || step < 1 ||
+      pack_stride < 4 * (int64_t)pd.total) {
+    set_error("npp_light_adam_pack: bad argument");
+    return NPP_ERR_ARG;
+  }
+  LightAdamArgs a{};
+  a.L = *L; a.p = d_params; a.m = d_m; a.v = d_v; a.g = d_grad; a.stride = stride; a.n = (int32_t)n;
+  a.pack = d_pack; a.pack_stride = pack_stride;
+  a.t = light_latent_args(d_lat, d_lat_m, d_lat_v, d_dlat, d_zero, lr, beta1, beta2, eps, step, d_part, n_part, d_loss_cur);
+  hipLaunchKernelGGL(light_adam_pack_kernel, dim3((unsigned)((n + 255) / 256 + 1), (unsigned)C), dim3(256), 0, (hipStream_t)stream, a, pd);
+  return check_launch("npp_light_adam_pack");
+}
 extern "C" int npp_light_adam_pack(const npp_light_desc* L, float* d_params, float* d_m, float* d_v, float* d_grad, int64_t stride, int64_t n, int C,
                                    float* d_pack, int64_t pack_stride, float* d_lat, float* d_lat_m, float* d_lat_v, float* d_dlat, float* d_zero,
                                    float lr, float beta1, float beta2, float eps, int step, void* stream) {
@@ -626,25 +542,4 @@ extern "C" int npp_light_adam_pack_det(const npp_light_desc* L, float* d_params,
   if (!d_part || n_part < 1) { set_error("npp_light_adam_pack_det: d_part / n_part"); return NPP_ERR_ARG; }
   return light_adam_go(L, d_params, d_m, d_v, d_grad, stride, n, C, d_pack, pack_stride, d_lat, d_lat_m, d_lat_v, d_dlat, d_zero, lr, beta1, beta2,
                        eps, step, d_part, n_part, d_loss_cur, stream);
-}
-static int light_adam_go(const npp_light_desc* L, float* d_params, float* d_m, float* d_v, float* d_grad, int64_t stride, int64_t n, int C,
-                         float* d_pack, int64_t pack_stride, float* d_lat, float* d_lat_m, float* d_lat_v, float* d_dlat, float* d_zero,
-                         float lr, float beta1, float beta2, float eps, int step, const float* d_part, int n_part, float* d_loss_cur, void* stream) {
-  int rc = light_check(L, d_params, d_pack, C, 32, "npp_light_adam_pack");
-  if (rc) return rc;
-  const LightPackDesc pd = light_pack_desc();
-  if (!d_m || !d_v || !d_grad || !d_lat || !d_lat_m || !d_lat_v || !d_dlat || n < 1 || n > stride || n > 0x7fffffffLL || step < 1 ||
-      pack_stride < 4 * (int64_t)pd.total) {
-    set_error("npp_light_adam_pack: bad argument");
-    return NPP_ERR_ARG;
-  }
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  LightAdamArgs a{};
-  a.L = *L; a.p = d_params; a.m = d_m; a.v = d_v; a.g = d_grad; a.stride = stride; a.n = (int32_t)n;
-  a.pack = d_pack; a.pack_stride = pack_stride;
-  a.lat = d_lat; a.lat_m = d_lat_m; a.lat_v = d_lat_v; a.dlat = d_dlat; a.zero = d_zero;
-  a.step_size = (float)((double)lr / bc1); a.b1 = beta1; a.b2 = beta2; a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2)); a.eps = eps;
-  a.part = d_part; a.n_part = n_part; a.loss_cur = d_loss_cur;
-  hipLaunchKernelGGL(light_adam_pack_kernel, dim3((unsigned)((n + 255) / 256 + 1), (unsigned)C), dim3(256), 0, (hipStream_t)stream, a, pd);
-  return check_launch("npp_light_adam_pack");
 }

@@ -18,8 +18,7 @@
 // linear ones.
 #include <stdlib.h>
 
-#include "npp_common.h"
-#include "npp_light_layout.h"
+#include "npp_light_common.h"
 
 namespace npp {
 
@@ -32,27 +31,22 @@ constexpr int kL16SmemF = 2 * kL16Region + kL16RegionX;
 constexpr int kL16SmemB = 2 * kL16Region + kRowTile * 3 * 4;
 
 // packs of one candidate, 16-byte units: forward [layer][k-step][neuron tile][lane], then the transposed packs of the backward chain
-enum { HF_L0 = 0, HF_L1, HF_L2, HF_L3, HF_F1, HF_POS, HF_N };
-enum { HB_POS = 0, HB_F1, HB_L3, HB_L2, HB_L1, HB_N };
 struct L16Pack {
-  int32_t f_off[HF_N], f_ks[HF_N], f_nt[HF_N];
-  int32_t b_off[HB_N], b_ks[HB_N];
+  int32_t f_off[LF_N], f_ks[LF_N], f_nt[LF_N];
+  int32_t b_off[LB_N], b_ks[LB_N];
   int32_t f_total, total;
 };
 __host__ __device__ inline L16Pack l16_pack_desc() {
   L16Pack d{};
   int off = 0;
-  const int ks[HF_N] = {2, kKSAct, kKSAct, kKSAct, kKSAct, kL16KsHp}, nt[HF_N] = {kNT, kNT, kNT, kNT, kNT, kNT / 2};
-  for (int l = 0; l < HF_N; ++l) { d.f_off[l] = off; d.f_ks[l] = ks[l]; d.f_nt[l] = nt[l]; off += ks[l] * nt[l] * 64; }
+  const int ks[LF_N] = {2, kKSAct, kKSAct, kKSAct, kKSAct, kL16KsHp}, nt[LF_N] = {kNT, kNT, kNT, kNT, kNT, kNT / 2};
+  for (int l = 0; l < LF_N; ++l) { d.f_off[l] = off; d.f_ks[l] = ks[l]; d.f_nt[l] = nt[l]; off += ks[l] * nt[l] * 64; }
   d.f_total = off;
-  const int bk[HB_N] = {kLPosOut / 16, kKSAct, kKSAct, kKSAct, kKSAct};
-  for (int l = 0; l < HB_N; ++l) { d.b_off[l] = off; d.b_ks[l] = bk[l]; off += bk[l] * kNT * 64; }
+  const int bk[LB_N] = {kLPosOut / 16, kKSAct, kKSAct, kKSAct, kKSAct};
+  for (int l = 0; l < LB_N; ++l) { d.b_off[l] = off; d.b_ks[l] = bk[l]; off += bk[l] * kNT * 64; }
   d.total = off;
   return d;
 }
-// npp_light_desc index of a pack entry: periodic 0..3, pos (4), feature1 (5), rgb (6)
-__host__ __device__ inline int l16_fwd_layer(int l) { return l < 4 ? l : (l == HF_F1 ? 5 : 4); }
-__host__ __device__ inline int l16_bwd_layer(int l) { return l == HB_POS ? 4 : (l == HB_F1 ? 5 : (l == HB_L3 ? 3 : (l == HB_L2 ? 2 : 1))); }
 
 struct L16Args {
   npp_light_desc L;
@@ -64,13 +58,9 @@ struct L16Args {
   float* pred;                                       // (C, B, 3)
   const float* dpred;                                // (C, B, 3), backward without the folded loss
   int64_t B;
-  const float* gt; const float* latents; const float* spline; int n_knots; float x_scale;
-  float* loss; float* dlatent;
-  // (round 6) bit-reproducible form: every block leaves its seven loss / latent-gradient sums in part[(c n_wg + wg) * 8 + k] (no atomics;
-  // npp_light16_adam_pack_det adds them in block order).  "multi" forms (candidate = one IMAGE's fit): elements per candidate of the
-  // positional table, the row indices and the targets; 0 = shared
-  float* part;
-  int64_t x_pos_cs, idx_cs, gt_cs;
+  LightLossArgs lo;                                  // backward: the pixel loss folded in
+  // "multi" forms (candidate = one IMAGE's fit): elements per candidate of the positional table and the row indices; 0 = shared
+  int64_t x_pos_cs, idx_cs;
 };
 
 // ---- packs ----------------------------------------------------------------------------------------------------------------
@@ -82,13 +72,13 @@ __global__ void light16_pack_kernel(L16Args a, L16Pack pd, bf16x8* __restrict__ 
   const float* P = a.params + (int64_t)blockIdx.y * a.params_stride;
   const bool bwd = u >= pd.f_total;
   int l = 0;
-  if (!bwd) { for (int q = 1; q < HF_N; ++q) if (u >= pd.f_off[q]) l = q; }
-  else { for (int q = 1; q < HB_N; ++q) if (u >= pd.b_off[q]) l = q; }
+  if (!bwd) { for (int q = 1; q < LF_N; ++q) if (u >= pd.f_off[q]) l = q; }
+  else { for (int q = 1; q < LB_N; ++q) if (u >= pd.b_off[q]) l = q; }
   const int r = u - (bwd ? pd.b_off[l] : pd.f_off[l]);
   const int nt_n = bwd ? kNT : pd.f_nt[l];
   const int lane = r & 63, nt = (r >> 6) % nt_n, ks = (r >> 6) / nt_n;
   const int m = nt * 32 + (lane & 31), hh = lane >> 5;
-  const int li = bwd ? l16_bwd_layer(l) : l16_fwd_layer(l);
+  const int li = bwd ? light_bwd_layer(l) : light_fwd_layer(l);
   const float* Wm = P + a.L.w_off[li];
   const int ld = a.L.ld[li], n_out = a.L.n_out[li], n_in = a.L.n_in[li];
   bf16x8 o;
@@ -113,28 +103,12 @@ struct L16AdamArgs {
   float *p, *m, *v; int64_t stride; int32_t n;
   const float* gslabs; int32_t n_slabs; int64_t slab_stride, slab_cand_stride;
   __bf16* pack; int64_t pack_stride16;
-  float *lat, *lat_m, *lat_v, *dlat, *zero;
-  float step_size, b1, b2, inv_sqrt_bc2, eps;
-  const float* part; int32_t n_part; float* loss_cur;   // npp_light16_adam_pack_det: the blocks' sums of npp_light16_bwd_det, added in block order
+  LightLatentArgs t;                                    // latents, Adam's scalars, npp_light16_adam_pack_det's partial sums
 };
 __global__ __launch_bounds__(256) void light16_adam_pack_kernel(L16AdamArgs a, L16Pack pd) {
   const int c = blockIdx.y;
   if (blockIdx.x == gridDim.x - 1) {
-    const int t = threadIdx.x;
-    if (t < 6) {
-      const int i = c * 6 + t;
-      float g = a.dlat[i];
-      if (a.part)
-        for (int b = 0; b < a.n_part; ++b) g += a.part[((int64_t)c * a.n_part + b) * 8 + 1 + t];
-      float m = a.lat_m[i], v = a.lat_v[i];
-      a.lat[i] = adam_update(a.lat[i], m, v, g, a.step_size, a.b1, a.b2, a.inv_sqrt_bc2, a.eps);
-      a.lat_m[i] = m; a.lat_v[i] = v; a.dlat[i] = 0.0f;
-    } else if (t == 6 && a.zero) a.zero[c] = 0.0f;
-    else if (t == 64 && a.part && a.loss_cur) {
-      float l = 0.0f;
-      for (int b = 0; b < a.n_part; ++b) l += a.part[((int64_t)c * a.n_part + b) * 8];
-      a.loss_cur[c] += l;
-    }
+    light_latent_step(a.t, c);
     return;
   }
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -144,7 +118,7 @@ __global__ __launch_bounds__(256) void light16_adam_pack_kernel(L16AdamArgs a, L
   float g = gs[0];
   for (int s = 1; s < a.n_slabs; ++s) g += gs[(int64_t)s * a.slab_stride];
   float m = a.m[gi], v = a.v[gi];
-  const float w = adam_update(a.p[gi], m, v, g, a.step_size, a.b1, a.b2, a.inv_sqrt_bc2, a.eps);
+  const float w = adam_update(a.p[gi], m, v, g, a.t.step_size, a.t.b1, a.t.b2, a.t.inv_sqrt_bc2, a.t.eps);
   a.p[gi] = w; a.m[gi] = m; a.v[gi] = v;
   int li = -1;
 #pragma unroll
@@ -156,14 +130,14 @@ __global__ __launch_bounds__(256) void light16_adam_pack_kernel(L16AdamArgs a, L
   if (col >= a.L.n_in[li]) return;                        // pad column of the stored matrix
   __bf16* pk = a.pack + (int64_t)c * a.pack_stride16 * 8;
   const __bf16 wb = (__bf16)w;
-  const int lf = li < 4 ? HF_L0 + li : (li == 4 ? HF_POS : HF_F1);
+  const int lf = light_fwd_entry(li);
   {
     const int c16 = col & 15;
     const int64_t unit = pd.f_off[lf] + ((int64_t)(col >> 4) * pd.f_nt[lf] + (row >> 5)) * 64 + (row & 31) + 32 * unperm_hh(c16);
     pk[unit * 8 + unperm_j(c16)] = wb;
   }
   if (li >= 1 && col < kLW) {                               // transposed pack: A[m = col][k = row]
-    const int lb = li == 4 ? HB_POS : (li == 5 ? HB_F1 : (li == 3 ? HB_L3 : (li == 2 ? HB_L2 : HB_L1)));
+    const int lb = light_bwd_entry(li);
     const int c16 = row & 15;
     const int64_t unit = pd.b_off[lb] + ((int64_t)(row >> 4) * kNT + (col >> 5)) * 64 + (col & 31) + 32 * unperm_hh(c16);
     pk[unit * 8 + unperm_j(c16)] = wb;
@@ -337,7 +311,7 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_fwd_kernel(L16Args a, 
   LRing<2> ring;
   LRing<1> ringp;
   ring.rsrc = ringp.rsrc = make_wrsrc(a.pack + (int64_t)c * a.pack_stride16, pd.total);
-  lring_fill<2, kNT>(ring, (wptr_t)pd.f_off[HF_L0], nt0, L.lane);
+  lring_fill<2, kNT>(ring, (wptr_t)pd.f_off[LF_L0], nt0, L.lane);
 
   // inputs -> fragments: x_per (2 k-steps, region R1) and x_pos (4 k-steps, region RX), both also into their stash arrays
   {
@@ -363,7 +337,7 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_fwd_kernel(L16Args a, 
   L16Bias<1> bnp;
   // periodic_linears.0: 20 (32 slots) -> 256, snake: R1 -> R0
   l16_bias<2>(acc, P + a.L.b_off[0], nt0, L);
-  lmma<2, l16_tot(2), 2, kNT>(acc, R1, (wptr_t)pd.f_off[HF_L0], (wptr_t)pd.f_off[HF_L1], nt0, L, ring);
+  lmma<2, l16_tot(2), 2, kNT>(acc, R1, (wptr_t)pd.f_off[LF_L0], (wptr_t)pd.f_off[LF_L1], nt0, L, ring);
   l16_bias_fetch<2>(bn, P + a.L.b_off[1], nt0, L);
   l16_epi<true, 2>(acc, R0, nt0, arr(L16A_Z0), A, wg, L);
   wg_barrier();
@@ -373,15 +347,15 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_fwd_kernel(L16Args a, 
     char* in = (l & 1) ? R0 : R1;
     char* out = (l & 1) ? R1 : R0;
     l16_bias_apply<2>(acc, bn);
-    lmma<A, l16_tot(A), 2, kNT>(acc, in, (wptr_t)pd.f_off[HF_L0 + l], (wptr_t)pd.f_off[HF_L0 + l + 1], nt0, L, ring);
+    lmma<A, l16_tot(A), 2, kNT>(acc, in, (wptr_t)pd.f_off[LF_L0 + l], (wptr_t)pd.f_off[LF_L0 + l + 1], nt0, L, ring);
     l16_bias_fetch<2>(bn, P + a.L.b_off[l == 3 ? 5 : l + 1], nt0, L);
     l16_epi<true, 2>(acc, out, nt0, arr(L16A_Z0 + A * l), A, wg, L);
     wg_barrier();
   }
   // feature_linear1 (linear): R1 -> R0, also the first 16 k-steps of the [f1 | x_pos] stash
   l16_bias_apply<2>(acc, bn);
-  lmma<A, l16_tot(A), 2, kNT>(acc, R1, (wptr_t)pd.f_off[HF_F1], kNoW, nt0, L, ring);
-  lring_fill<1, kNT / 2>(ringp, (wptr_t)pd.f_off[HF_POS], L.wave, L.lane);
+  lmma<A, l16_tot(A), 2, kNT>(acc, R1, (wptr_t)pd.f_off[LF_F1], kNoW, nt0, L, ring);
+  lring_fill<1, kNT / 2>(ringp, (wptr_t)pd.f_off[LF_POS], L.wave, L.lane);
   l16_bias_fetch<1>(bnp, P + a.L.b_off[4], L.wave, L);
   l16_epi<false, 2>(acc, R0, nt0, arr(L16A_HP), kL16KsHp, wg, L);
   wg_barrier();
@@ -389,8 +363,8 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_fwd_kernel(L16Args a, 
   f32x16 accp[1][kNB];
   constexpr wptr_t UP = (kNT / 2) * 64;
   l16_bias_apply<1>(accp, bnp);
-  lmma<A, l16_tot(A), 1, kNT / 2>(accp, R0, (wptr_t)pd.f_off[HF_POS], (wptr_t)pd.f_off[HF_POS] + A * UP, L.wave, L, ringp);
-  lmma<4, l16_tot(4), 1, kNT / 2>(accp, RX, (wptr_t)pd.f_off[HF_POS] + A * UP, kNoW, L.wave, L, ringp);
+  lmma<A, l16_tot(A), 1, kNT / 2>(accp, R0, (wptr_t)pd.f_off[LF_POS], (wptr_t)pd.f_off[LF_POS] + A * UP, L.wave, L, ringp);
+  lmma<4, l16_tot(4), 1, kNT / 2>(accp, RX, (wptr_t)pd.f_off[LF_POS] + A * UP, kNoW, L.wave, L, ringp);
   l16_epi<true, 1>(accp, nullptr, L.wave, arr(L16A_ZP), kLPosOut / 16, wg, L);
   // rgb_linear 128 -> 3 + sigmoid (models/helpers.py:55-56): per-lane partial dot over its 16 neurons, lane halves by shuffle,
   // the four waves through LDS
@@ -502,7 +476,7 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_bwd_kernel(L16Args a, 
   // everything the prologue needs from memory first: the weight ring of the first data-gradient part, rgb_linear's rows, z_p
   LRing<2> ring;
   ring.rsrc = make_wrsrc(a.pack + (int64_t)c * a.pack_stride16, pd.total);
-  lring_fill<2, kNT>(ring, (wptr_t)pd.b_off[HB_POS], kt0, L.lane);
+  lring_fill<2, kNT>(ring, (wptr_t)pd.b_off[LB_POS], kt0, L.lane);
   f16x8 zp_pre[kNB][2];
 #pragma unroll
   for (int bt = 0; bt < kNB; ++bt)
@@ -518,71 +492,8 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_bwd_kernel(L16Args a, 
       for (int r = 0; r < 16; ++r) wr[q][r] = Wr[q * ldr + L.wave * 32 + acc_row(r, L.h)];
   }
 
-  // d raw = d pred * pred (1 - pred); with the pixel loss folded in (a.gt): d pred = d img2mse(robust_loss_adaptive)/d pred right here
-  // (models/mse_calculator.py:13-27 without a mask: the arithmetic of pixel_loss_body, npp_common.h), loss / latent gradients by atomics
-  __shared__ ChanParams cp[3];
-  __shared__ float sred[7];
-  __shared__ float swv[kL16Threads / 64][7];
-  if (a.gt) {
-    if (tid < 3) cp[tid] = chan_params(a.latents[c * 6 + tid], a.latents[c * 6 + 3 + tid], a.spline, a.n_knots, a.x_scale);
-    if (tid < 7) sred[tid] = 0.0f;
-    wg_barrier();
-  }
-  float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;                 // this thread's loss term and latent-gradient terms (channel tid % 3)
-  if (tid < kRowTile * 3) {
-    const int64_t g = ((int64_t)c * B + row0) * 3 + tid;
-    const float p = a.pred[g];
-    float dp;
-    if (a.gt) {
-      const int ch = tid % 3;
-      const ChanParams q = cp[ch];
-      const float inv = 1.0f / (3.0f * (float)B);
-      const float x = p - a.gt[(int64_t)c * a.gt_cs + row0 * 3 + tid];
-      const float xs = x / q.c, ssx = xs * xs;
-      const float u = ssx / q.beta + 1.0f, e = 0.5f * q.alpha, lnu = logf(u);
-      const float ue = expf(e * lnu), ue1 = ue / u;
-      dp = inv * (x / (q.c * q.c)) * ue1;
-      t0 = (q.beta / q.alpha) * (ue - 1.0f) + q.logc_plus_logz;
-      t1 = -(2.0f / (q.alpha * q.alpha)) * (ue - 1.0f) + (q.beta / q.alpha) * ue * (0.5f * lnu + e * ssx / (q.beta * q.beta * u)) + q.dlogz;
-      t2 = -(x * x) / (q.c * q.c * q.c) * ue1 + 1.0f / q.c;
-      if (!a.part) {
-        atomicAdd(&sred[0], t0);
-        atomicAdd(&sred[1 + ch], t1);
-        atomicAdd(&sred[4 + ch], t2);
-      }
-    } else {
-      dp = a.dpred[g];
-    }
-    sD[tid] = dp * p * (1.0f - p);
-  }
-  if (a.gt && a.part) {
-    // deterministic form (every wave, whole: threads past the 3 x 64 values carry zeros): the seven sums of a wave by shuffle butterflies
-    // -- a fixed tree -- then the waves' results in wave order (csrc/npp_light.hip light_bwd_kernel does the same)
-    const int ch = tid % 3, lane_ = tid & 63, wave_ = tid >> 6;
-    const float v7[7] = {t0, ch == 0 ? t1 : 0.0f, ch == 1 ? t1 : 0.0f, ch == 2 ? t1 : 0.0f, ch == 0 ? t2 : 0.0f, ch == 1 ? t2 : 0.0f, ch == 2 ? t2 : 0.0f};
-#pragma unroll
-    for (int k7 = 0; k7 < 7; ++k7) {
-      float v = v7[k7];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      if (lane_ == 0) swv[wave_][k7] = v;
-    }
-  }
-  wg_barrier();
-  if (a.gt && tid < 7) {
-    const float inv = 1.0f / (3.0f * (float)B);
-    if (a.part) {
-      float v = 0.0f;
-#pragma unroll
-      for (int w_ = 0; w_ < kL16Threads / 64; ++w_) v += swv[w_][tid];
-      a.part[((int64_t)c * n_wg + wg) * 8 + tid] = tid == 0 ? v * inv : (tid < 4 ? inv * v * cp[tid - 1].dalpha_dl : inv * v * cp[tid - 4].dc_dl);
-    } else {
-      const float v = sred[tid];
-      if (tid == 0) atomicAdd(a.loss + c, v * inv);
-      else if (tid < 4) atomicAdd(a.dlatent + c * 6 + (tid - 1), inv * v * cp[tid - 1].dalpha_dl);
-      else atomicAdd(a.dlatent + c * 6 + 3 + (tid - 4), inv * v * cp[tid - 4].dc_dl);
-    }
-  }
+  // d raw = d pred * pred (1 - pred), the pixel loss folded in (light_loss_head)
+  light_loss_head<kL16Threads, kRowTile>(a.lo, a.pred, a.dpred, c, B, row0, wg, n_wg, [&](int64_t, float d) { sD[tid] = d; });
   // d raw as a 2-k-step W-format array (rgb_linear's weight gradient): features 0..2 real, the rest zero
   {
     const int q1 = tid >> 7, bt = (tid >> 6) & 1, row = bt * 32 + L.b;
@@ -624,7 +535,7 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_bwd_kernel(L16Args a, 
   constexpr int KP = kLPosOut / 16, A = kKSAct;
   // d f1 = W_pos[:, :256]^T d z_p  (feature_linear1 is linear: this IS its d z; x_pos gets no gradient): R0 -> R1
   l16_zero(acc);
-  lmma<KP, l16_tot(KP), 2, kNT>(acc, R0, (wptr_t)pd.b_off[HB_POS], (wptr_t)pd.b_off[HB_F1], kt0, L, ring);
+  lmma<KP, l16_tot(KP), 2, kNT>(acc, R0, (wptr_t)pd.b_off[LB_POS], (wptr_t)pd.b_off[LB_F1], kt0, L, ring);
   l16_bepi<false>(acc, R1, nullptr, dzr(L16D_F1), wg, kt0, L);
   wg_barrier();
   // d z_3 = (W_f1^T d f1) * snake'(z_3), d z_2 = (W_3^T d z_3) * snake'(z_2), ..., d z_0: R1 -> R0 -> R1 -> R0
@@ -635,7 +546,7 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_bwd_kernel(L16Args a, 
     char* out = (j & 1) ? R1 : R0;
     l16_zero(acc);
     l16_zfetch(zpre, zs(L16A_Z0 + A * l), wg, kt0, L);
-    lmma<A, l16_tot(A), 2, kNT>(acc, in, (wptr_t)pd.b_off[HB_F1 + j], j == 3 ? kNoW : (wptr_t)pd.b_off[HB_F1 + j + 1], kt0, L, ring);
+    lmma<A, l16_tot(A), 2, kNT>(acc, in, (wptr_t)pd.b_off[LB_F1 + j], j == 3 ? kNoW : (wptr_t)pd.b_off[LB_F1 + j + 1], kt0, L, ring);
     l16_bepi<true>(acc, j == 3 ? nullptr : out, &zpre, dzr(L16D_Z0 + A * l), wg, kt0, L);
     if (j != 3) wg_barrier();
   }
@@ -650,14 +561,7 @@ static int l16_check(const npp_light_desc* L, const void* p0, const void* p1, in
     set_error("%s: bad argument (C=%d B=%lld; B a positive multiple of %d)", who, C, (long long)B, kRowTile);
     return NPP_ERR_ARG;
   }
-  const int n_out[7] = {kLW, kLW, kLW, kLW, kLPosOut, kLW, 3}, n_in[7] = {kLPer, kLW, kLW, kLW, kLW + kLPos, kLW, kLPosOut};
-  for (int i = 0; i < 7; ++i)
-    if (L->n_out[i] != n_out[i] || L->n_in[i] != n_in[i] || L->ld[i] < n_in[i] || L->w_off[i] < 0 || L->b_off[i] < 0) {
-      set_error("%s: layer %d is %d x %d (ld %d): this build fuses NPP_Net_light(D=4, W=256) with 20 / 42 input columns only", who, i,
-                L->n_out[i], L->n_in[i], L->ld[i]);
-      return NPP_ERR_UNSUPPORTED;
-    }
-  return NPP_OK;
+  return light_topology_check(L, who);
 }
 
 extern "C" int64_t npp_light16_pack_bytes(void) { return 16 * (int64_t)l16_pack_desc().total; }
@@ -681,23 +585,6 @@ extern "C" int npp_light16_pack(const npp_light_desc* L, const float* d_params, 
 
 static int l16_fwd_go(const npp_light_desc* L, const float* d_params, int64_t params_stride, const void* d_pack,
                       int64_t pack_stride_bytes, const float* d_x_per, const float* d_x_pos, const int64_t* d_idx, int64_t n_src,
-                      int C, int64_t B, void* d_actF, int64_t act_stride_bytes, float* d_pred, int64_t x_pos_cs, int64_t idx_cs, void* stream);
-extern "C" int npp_light16_fwd(const npp_light_desc* L, const float* d_params, int64_t params_stride, const void* d_pack,
-                               int64_t pack_stride_bytes, const float* d_x_per, const float* d_x_pos, const int64_t* d_idx, int64_t n_src,
-                               int C, int64_t B, void* d_actF, int64_t act_stride_bytes, float* d_pred, void* stream) {
-  return l16_fwd_go(L, d_params, params_stride, d_pack, pack_stride_bytes, d_x_per, d_x_pos, d_idx, n_src, C, B, d_actF, act_stride_bytes, d_pred, 0, 0,
-                    stream);
-}
-// "multi" form (round 6): candidate c = one IMAGE's fit -- its own positional table d_x_pos (C, n_src, 42) and pixel rows d_idx (C, B)
-extern "C" int npp_light16_fwd_multi(const npp_light_desc* L, const float* d_params, int64_t params_stride, const void* d_pack,
-                                     int64_t pack_stride_bytes, const float* d_x_per, const float* d_x_pos, const int64_t* d_idx, int64_t n_src,
-                                     int C, int64_t B, void* d_actF, int64_t act_stride_bytes, float* d_pred, void* stream) {
-  if (!d_idx) { set_error("npp_light16_fwd_multi: null row indices"); return NPP_ERR_ARG; }
-  return l16_fwd_go(L, d_params, params_stride, d_pack, pack_stride_bytes, d_x_per, d_x_pos, d_idx, n_src, C, B, d_actF, act_stride_bytes, d_pred,
-                    n_src * kLPos, B, stream);
-}
-static int l16_fwd_go(const npp_light_desc* L, const float* d_params, int64_t params_stride, const void* d_pack,
-                      int64_t pack_stride_bytes, const float* d_x_per, const float* d_x_pos, const int64_t* d_idx, int64_t n_src,
                       int C, int64_t B, void* d_actF, int64_t act_stride_bytes, float* d_pred, int64_t x_pos_cs, int64_t idx_cs, void* stream) {
   int rc = l16_check(L, d_params, d_pack, C, B, "npp_light16_fwd");
   if (rc) return rc;
@@ -717,12 +604,46 @@ static int l16_fwd_go(const npp_light_desc* L, const float* d_params, int64_t pa
                      l16_pack_desc(), n_wg, C);
   return check_launch("npp_light16_fwd");
 }
+extern "C" int npp_light16_fwd(const npp_light_desc* L, const float* d_params, int64_t params_stride, const void* d_pack,
+                               int64_t pack_stride_bytes, const float* d_x_per, const float* d_x_pos, const int64_t* d_idx, int64_t n_src,
+                               int C, int64_t B, void* d_actF, int64_t act_stride_bytes, float* d_pred, void* stream) {
+  return l16_fwd_go(L, d_params, params_stride, d_pack, pack_stride_bytes, d_x_per, d_x_pos, d_idx, n_src, C, B, d_actF, act_stride_bytes, d_pred, 0, 0,
+                    stream);
+}
+// "multi" form (round 6): candidate c = one IMAGE's fit -- its own positional table d_x_pos (C, n_src, 42) and pixel rows d_idx (C, B)
+extern "C" int npp_light16_fwd_multi(const npp_light_desc* L, const float* d_params, int64_t params_stride, const void* d_pack,
+                                     int64_t pack_stride_bytes, const float* d_x_per, const float* d_x_pos, const int64_t* d_idx, int64_t n_src,
+                                     int C, int64_t B, void* d_actF, int64_t act_stride_bytes, float* d_pred, void* stream) {
+  if (!d_idx) { set_error("npp_light16_fwd_multi: null row indices"); return NPP_ERR_ARG; }
+  return l16_fwd_go(L, d_params, params_stride, d_pack, pack_stride_bytes, d_x_per, d_x_pos, d_idx, n_src, C, B, d_actF, act_stride_bytes, d_pred,
+                    n_src * kLPos, B, stream);
+}
 
 static int l16_bwd_go(const npp_light_desc* L, const float* d_params, int64_t params_stride, const void* d_pack,
                       int64_t pack_stride_bytes, const void* d_actF, int64_t act_stride_bytes, const float* d_pred,
                       const float* d_dpred, const float* d_gt, const float* d_latents, const float* d_spline, int n_knots,
                       float x_scale, float* d_loss, float* d_dlatent, int C, int64_t B, void* d_dzF, int64_t dz_stride_bytes,
-                      float* d_part, int64_t gt_cs, void* stream);
+                      float* d_part, int64_t gt_cs, void* stream) {
+  int rc = l16_check(L, d_params, d_pack, C, B, "npp_light16_bwd");
+  if (rc) return rc;
+  if (!d_actF || !d_pred || !d_dzF || (d_gt ? (!d_latents || !d_spline || n_knots < 2 || (!d_part && (!d_loss || !d_dlatent))) : !d_dpred) ||
+      pack_stride_bytes % 16 || act_stride_bytes % 16 || dz_stride_bytes % 16 || act_stride_bytes < wfmt_array_base(L16A_TOTAL, B / kRowTile) ||
+      dz_stride_bytes < wfmt_array_base(L16D_TOTAL, B / kRowTile)) {
+    set_error("npp_light16_bwd: null argument (d_dpred, or d_gt with latents / spline / loss / dlatent) / strides");
+    return NPP_ERR_ARG;
+  }
+  L16Args a{};
+  a.L = *L; a.params = d_params; a.params_stride = params_stride; a.pack = (const bf16x8*)d_pack; a.pack_stride16 = pack_stride_bytes / 16;
+  a.actF = (char*)d_actF; a.act_stride = act_stride_bytes; a.dzF = (char*)d_dzF; a.dz_stride = dz_stride_bytes;
+  a.pred = (float*)d_pred; a.dpred = d_dpred; a.B = B;
+  a.lo = LightLossArgs{d_gt, d_latents, d_spline, n_knots, x_scale, d_loss, d_dlatent, d_part, gt_cs};
+  static SmemOnce once;
+  if (!smem_attr(once, (const void*)light16_bwd_kernel, kL16SmemB)) { set_error("npp_light16_bwd: smem attribute"); return NPP_ERR_LAUNCH; }
+  const int n_wg = (int)(B / kRowTile);
+  hipLaunchKernelGGL(light16_bwd_kernel, dim3((unsigned)((n_wg * C + 7) / 8 * 8)), dim3(kL16Threads), kL16SmemB, (hipStream_t)stream, a,
+                     l16_pack_desc(), n_wg, C);
+  return check_launch("npp_light16_bwd");
+}
 extern "C" int npp_light16_bwd(const npp_light_desc* L, const float* d_params, int64_t params_stride, const void* d_pack,
                                int64_t pack_stride_bytes, const void* d_actF, int64_t act_stride_bytes, const float* d_pred,
                                const float* d_dpred, const float* d_gt, const float* d_latents, const float* d_spline, int n_knots,
@@ -742,37 +663,28 @@ extern "C" int npp_light16_bwd_det(const npp_light_desc* L, const float* d_param
   return l16_bwd_go(L, d_params, params_stride, d_pack, pack_stride_bytes, d_actF, act_stride_bytes, d_pred, nullptr, d_gt, d_latents, d_spline,
                     n_knots, x_scale, nullptr, nullptr, C, B, d_dzF, dz_stride_bytes, d_part, gt_cs, stream);
 }
-static int l16_bwd_go(const npp_light_desc* L, const float* d_params, int64_t params_stride, const void* d_pack,
-                      int64_t pack_stride_bytes, const void* d_actF, int64_t act_stride_bytes, const float* d_pred,
-                      const float* d_dpred, const float* d_gt, const float* d_latents, const float* d_spline, int n_knots,
-                      float x_scale, float* d_loss, float* d_dlatent, int C, int64_t B, void* d_dzF, int64_t dz_stride_bytes,
-                      float* d_part, int64_t gt_cs, void* stream) {
-  int rc = l16_check(L, d_params, d_pack, C, B, "npp_light16_bwd");
-  if (rc) return rc;
-  if (!d_actF || !d_pred || !d_dzF || (d_gt ? (!d_latents || !d_spline || n_knots < 2 || (!d_part && (!d_loss || !d_dlatent))) : !d_dpred) ||
-      pack_stride_bytes % 16 || act_stride_bytes % 16 || dz_stride_bytes % 16 || act_stride_bytes < wfmt_array_base(L16A_TOTAL, B / kRowTile) ||
-      dz_stride_bytes < wfmt_array_base(L16D_TOTAL, B / kRowTile)) {
-    set_error("npp_light16_bwd: null argument (d_dpred, or d_gt with latents / spline / loss / dlatent) / strides");
-    return NPP_ERR_ARG;
-  }
-  L16Args a{};
-  a.L = *L; a.params = d_params; a.params_stride = params_stride; a.pack = (const bf16x8*)d_pack; a.pack_stride16 = pack_stride_bytes / 16;
-  a.actF = (char*)d_actF; a.act_stride = act_stride_bytes; a.dzF = (char*)d_dzF; a.dz_stride = dz_stride_bytes;
-  a.pred = (float*)d_pred; a.dpred = d_dpred; a.B = B;
-  a.gt = d_gt; a.latents = d_latents; a.spline = d_spline; a.n_knots = n_knots; a.x_scale = x_scale; a.loss = d_loss; a.dlatent = d_dlatent;
-  a.part = d_part; a.gt_cs = gt_cs;
-  static SmemOnce once;
-  if (!smem_attr(once, (const void*)light16_bwd_kernel, kL16SmemB)) { set_error("npp_light16_bwd: smem attribute"); return NPP_ERR_LAUNCH; }
-  const int n_wg = (int)(B / kRowTile);
-  hipLaunchKernelGGL(light16_bwd_kernel, dim3((unsigned)((n_wg * C + 7) / 8 * 8)), dim3(kL16Threads), kL16SmemB, (hipStream_t)stream, a,
-                     l16_pack_desc(), n_wg, C);
-  return check_launch("npp_light16_bwd");
-}
 
 static int l16_adam_go(const npp_light_desc* L, float* d_params, float* d_m, float* d_v, int64_t stride, int64_t n, int C,
                        const float* d_gslabs, int n_slabs, int64_t slab_stride, int64_t slab_cand_stride, void* d_pack,
                        int64_t pack_stride_bytes, float* d_lat, float* d_lat_m, float* d_lat_v, float* d_dlat, float* d_zero,
-                       float lr, float beta1, float beta2, float eps, int step, const float* d_part, int n_part, float* d_loss_cur, void* stream);
+                       float lr, float beta1, float beta2, float eps, int step, const float* d_part, int n_part, float* d_loss_cur, void* stream) {
+  int rc = l16_check(L, d_params, d_pack, C, kRowTile, "npp_light16_adam_pack");
+  if (rc) return rc;
+  const L16Pack pd = l16_pack_desc();
+  if (!d_m || !d_v || !d_gslabs || !d_lat || !d_lat_m || !d_lat_v || !d_dlat || n < 1 || n > stride || n > 0x7fffffffLL || step < 1 ||
+      n_slabs < 1 || slab_stride < n || slab_cand_stride < (int64_t)n_slabs * slab_stride || pack_stride_bytes < 16 * (int64_t)pd.total ||
+      pack_stride_bytes % 16) {
+    set_error("npp_light16_adam_pack: bad argument");
+    return NPP_ERR_ARG;
+  }
+  L16AdamArgs a{};
+  a.L = *L; a.p = d_params; a.m = d_m; a.v = d_v; a.stride = stride; a.n = (int32_t)n;
+  a.gslabs = d_gslabs; a.n_slabs = n_slabs; a.slab_stride = slab_stride; a.slab_cand_stride = slab_cand_stride;
+  a.pack = (__bf16*)d_pack; a.pack_stride16 = pack_stride_bytes / 16;
+  a.t = light_latent_args(d_lat, d_lat_m, d_lat_v, d_dlat, d_zero, lr, beta1, beta2, eps, step, d_part, n_part, d_loss_cur);
+  hipLaunchKernelGGL(light16_adam_pack_kernel, dim3((unsigned)((n + 255) / 256 + 1), (unsigned)C), dim3(256), 0, (hipStream_t)stream, a, pd);
+  return check_launch("npp_light16_adam_pack");
+}
 extern "C" int npp_light16_adam_pack(const npp_light_desc* L, float* d_params, float* d_m, float* d_v, int64_t stride, int64_t n, int C,
                                      const float* d_gslabs, int n_slabs, int64_t slab_stride, int64_t slab_cand_stride, void* d_pack,
                                      int64_t pack_stride_bytes, float* d_lat, float* d_lat_m, float* d_lat_v, float* d_dlat, float* d_zero,
@@ -790,28 +702,4 @@ extern "C" int npp_light16_adam_pack_det(const npp_light_desc* L, float* d_param
   if (!d_part || n_part < 1) { set_error("npp_light16_adam_pack_det: partial sums"); return NPP_ERR_ARG; }
   return l16_adam_go(L, d_params, d_m, d_v, stride, n, C, d_gslabs, n_slabs, slab_stride, slab_cand_stride, d_pack, pack_stride_bytes, d_lat, d_lat_m,
                      d_lat_v, d_dlat, d_zero, lr, beta1, beta2, eps, step, d_part, n_part, d_loss_cur, stream);
-}
-static int l16_adam_go(const npp_light_desc* L, float* d_params, float* d_m, float* d_v, int64_t stride, int64_t n, int C,
-                       const float* d_gslabs, int n_slabs, int64_t slab_stride, int64_t slab_cand_stride, void* d_pack,
-                       int64_t pack_stride_bytes, float* d_lat, float* d_lat_m, float* d_lat_v, float* d_dlat, float* d_zero,
-                       float lr, float beta1, float beta2, float eps, int step, const float* d_part, int n_part, float* d_loss_cur, void* stream) {
-  int rc = l16_check(L, d_params, d_pack, C, kRowTile, "npp_light16_adam_pack");
-  if (rc) return rc;
-  const L16Pack pd = l16_pack_desc();
-  if (!d_m || !d_v || !d_gslabs || !d_lat || !d_lat_m || !d_lat_v || !d_dlat || n < 1 || n > stride || n > 0x7fffffffLL || step < 1 ||
-      n_slabs < 1 || slab_stride < n || slab_cand_stride < (int64_t)n_slabs * slab_stride || pack_stride_bytes < 16 * (int64_t)pd.total ||
-      pack_stride_bytes % 16) {
-    set_error("npp_light16_adam_pack: bad argument");
-    return NPP_ERR_ARG;
-  }
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  L16AdamArgs a{};
-  a.L = *L; a.p = d_params; a.m = d_m; a.v = d_v; a.stride = stride; a.n = (int32_t)n;
-  a.gslabs = d_gslabs; a.n_slabs = n_slabs; a.slab_stride = slab_stride; a.slab_cand_stride = slab_cand_stride;
-  a.pack = (__bf16*)d_pack; a.pack_stride16 = pack_stride_bytes / 16;
-  a.lat = d_lat; a.lat_m = d_lat_m; a.lat_v = d_lat_v; a.dlat = d_dlat; a.zero = d_zero;
-  a.step_size = (float)((double)lr / bc1); a.b1 = beta1; a.b2 = beta2; a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2)); a.eps = eps;
-  a.part = d_part; a.n_part = n_part; a.loss_cur = d_loss_cur;
-  hipLaunchKernelGGL(light16_adam_pack_kernel, dim3((unsigned)((n + 255) / 256 + 1), (unsigned)C), dim3(256), 0, (hipStream_t)stream, a, pd);
-  return check_launch("npp_light16_adam_pack");
 }

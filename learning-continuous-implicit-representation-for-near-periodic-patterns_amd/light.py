@@ -6,8 +6,6 @@ the same kernels as the main loop, the score through the trunk / LPIPS / context
 The problem is tiny (2048 rows x 0.3 M parameters x 300 iterations per candidate) and launch-bound; candidates are
 independent, so they shard one per GPU exactly like images do (parallel.py).
 """
-import os
-
 import numpy as np
 import torch
 
@@ -33,6 +31,20 @@ def _stored_cols(c):
     columns meet zero inputs, get zero gradients and stay zero under Adam; state_dict() / grads() / load_state_dict() speak the
     reference's shapes."""
     return (c + 3) // 4 * 4
+
+
+def _blob_views(layout, params, grad):
+    """w, b, dw, db: {layer name: view} into a parameter blob and its gradient blob, one network's (n) or a stack's (C, n_pad): every
+    matrix stored (rows, _stored_cols(cols)), its bias behind it."""
+    w, b, dw, db = {}, {}, {}, {}
+    off = 0
+    for name, r, c in layout:
+        cs = _stored_cols(c)
+        for mats, vecs, t in ((w, b, params), (dw, db, grad)):
+            mats[name] = t.narrow(-1, off, r * cs).view(t.shape[:-1] + (r, cs))
+            vecs[name] = t.narrow(-1, off + r * cs, r)
+        off += r * cs + r
+    return w, b, dw, db
 
 
 class NPPNetLight:
@@ -63,14 +75,7 @@ class NPPNetLight:
         else:
             self.params, self.grad, self.m, self.v = (storage[k] for k in ("params", "grad", "m", "v"))
             assert all(t.shape == (n,) and t.is_contiguous() for t in (self.params, self.grad, self.m, self.v))
-        self.w, self.b, self.dw, self.db = {}, {}, {}, {}
-        off = 0
-        for name, r, c in self.layout:
-            cs = _stored_cols(c)
-            self.w[name], self.dw[name] = self.params[off:off + r * cs].view(r, cs), self.grad[off:off + r * cs].view(r, cs)
-            off += r * cs
-            self.b[name], self.db[name] = self.params[off:off + r], self.grad[off:off + r]
-            off += r
+        self.w, self.b, self.dw, self.db = _blob_views(self.layout, self.params, self.grad)
         if params is not None:
             self.load_state_dict(params)
         if storage is None:
@@ -228,12 +233,12 @@ class NPPNetLightBatch:
 
     def __init__(self, cands, freqs, res, params, W=256, D=4, device="cuda", lrate=5e-4, lrate_decay=500, fused=None, precision=None,
                  loss_type="robust_loss_adaptive"):
-        """fused (default: NPP_LIGHT_FUSED != 0 and the topology is the searched one, D = 4 / W = 256 / 42 + 20 input columns): forward and
-        data-gradient chains as ONE launch each over all candidates (csrc/npp_light.hip) instead of one launch per layer.
+        """fused (default: whenever the topology is the searched one, D = 4 / W = 256 / 42 + 20 input columns): forward and data-gradient
+        chains as ONE launch each over all candidates (csrc/npp_light.hip; 32 or 64 pixel rows per workgroup, whichever loads the chip
+        more evenly -- NPP_LIGHT_ROWS forces one) instead of one launch per layer.
         precision: "fp32" (exact fp32 MFMA everywhere) or "bf16" (csrc/npp_light16.hip: bf16 operands, fp32 accumulation, fp32 master
         weights and Adam -- the numeric contract of the main loop's MLP; fused topology, at most 16 candidates, batches of a multiple of
         64 rows; anything else falls back to fp32).  Default: "fp32"."""
-        import os
         self.device = ops.select_device(device)
         self.quad = ops.quad_coef(loss_type)              # --loss_type: 0 = adaptive; > 0: 'l2' / 'robust_loss' (no latent gradient)
         self.C, self.W, self.D = len(cands), int(W), int(D)
@@ -258,14 +263,7 @@ class NPPNetLightBatch:
             freqs_c = freqs[ci] if isinstance(freqs, list) else freqs
             self.nets.append(NPPNetLight(angles_deg, periods, freqs_c, res_c, params, W=W, D=D, device=self.device, lrate=lrate,
                                          lrate_decay=lrate_decay, storage=st, loss_type=loss_type))
-        self.w, self.b, self.dw, self.db = {}, {}, {}, {}
-        off = 0
-        for name, r, c in self.layout:
-            cs = _stored_cols(c)
-            self.w[name], self.dw[name] = self.params[:, off:off + r * cs].unflatten(1, (r, cs)), self.grad[:, off:off + r * cs].unflatten(1, (r, cs))
-            off += r * cs
-            self.b[name], self.db[name] = self.params[:, off:off + r], self.grad[:, off:off + r]
-            off += r
+        self.w, self.b, self.dw, self.db = _blob_views(self.layout, self.params, self.grad)
         n0 = self.nets[0]
         self.spline, self.n_knots, self.x_scale = n0.spline, n0.n_knots, n0.x_scale
         self._ws = {}
@@ -318,50 +316,70 @@ class NPPNetLightBatch:
                 # ride in the launch, or a candidate fitted alone and the same candidate in a stacked set differ in their last bits
                 # (light.rank_images: the images of a rank searched together give the bits of the serial loop).  1024 rows per slab.
                 ks = max(1, min(8, n_wg // 16))
+            # part: the backward blocks' loss / latent-gradient sums of the bit-reproducible launches (ops.light16_bwd_det)
             ws = dict(actF=u8(ab), dzF=u8(db), pred=torch.empty(C, B, 3, dtype=torch.float32, device=self.device),
-                      gslabs=torch.zeros(C, ks, self.n_pad, dtype=torch.float32, device=self.device))
+                      gslabs=torch.zeros(C, ks, self.n_pad, dtype=torch.float32, device=self.device),
+                      part=torch.zeros(C, n_wg, 8, dtype=torch.float32, device=self.device))
             if getattr(self, "_pack16", None) is None:
                 self._pack16 = u8(pb)
             self._ws[("bf16", B)] = ws
         return ws
 
-    def _train_step_bf16(self, x_pos, x_per, gt, idx=None):
-        """train_step() on the 16-bit chains: forward -> data gradients with the pixel loss folded in -> ONE grouped split-K
-        weight-gradient launch (partial sums by plain stores) -> Adam + bf16 re-pack: 4 launches for the whole candidate set."""
-        multi = gt.dim() == 3                               # multi-image set: x_pos (C, n, 42), gt (C, B, 3), idx (C, B)
-        B = gt.shape[1] if multi else gt.shape[0]
+    def _iteration_bf16(self, x_pos, x_per, gt, idx):
+        """An iteration of the candidate set on the 16-bit chains with the adaptive pixel loss: forward -> data gradients with the loss
+        folded in -> ONE grouped split-K weight-gradient launch (partial sums by plain stores) -> Adam + bf16 re-pack, 4 launches.
+        Arguments as train_step() (shared or per-candidate targets); they are checked and marshalled HERE, once:
+        -> run(idx_ptr, gt_ptr, lr, step, li) launches the four with other batch rows / targets of the same shapes (device addresses),
+        Adam's (lr, step) and loss words self._loss2[li] (the other set is cleared)."""
+        B = gt.shape[-2]
         ws = self._work16(B)
         if not self._pack16_valid:
             ops.light16_pack(self._desc, self.params, self._pack16)
-        ops.light16_fwd(self._desc, self.params, self._pack16, x_per.contiguous(), x_pos.contiguous(), ws["actF"], ws["pred"], idx=idx)
+        d, P, pk, actF, dzF, pred, gs, part = self._desc, self.params, self._pack16, ws["actF"], ws["dzF"], ws["pred"], ws["gslabs"], ws["part"]
+        det = ops.DETERMINISTIC         # bit-reproducible fit: the blocks' loss / latent-gradient sums by plain stores, added in block order by the Adam launch
+        state = (d, P, self.m, self.v, self.n_params, gs, pk, self.latents, self.lat_m, self.lat_v, self._dl_c, self._loss2[1], 0.0, 1)
+        fwd = ops.light16_fwd(d, P, pk, x_per, x_pos, actF, pred, idx=idx, bind=True)
+        if det:
+            bwd = ops.light16_bwd_det(d, P, pk, actF, pred, dzF, gt, self.latents, self.spline, self.n_knots, self.x_scale, part, bind=True)
+            adam = ops.light16_adam_pack_det(*state, part, self._loss2[0], bind=True)
+        else:
+            bwd = ops.light16_bwd(d, P, pk, actF, pred, None, dzF, bind=True,
+                                  loss_args=(gt, self.latents, self.spline, self.n_knots, self.x_scale, self._loss2[0], self._dl_c))
+            adam = ops.light16_adam_pack(*state, bind=True)
+        wgrad = ops.light16_wgrad(d, actF, dzF, B, gs, bind=True)
+        loss_p = [self._loss2[0].data_ptr(), self._loss2[1].data_ptr()]
+
+        # what changes from iteration to iteration, written in place (the loop is launch-bound: a microsecond of host time per launch shows)
+        f, b, a = fwd.args, bwd.args, adam.args
+        k_idx, k_gt, k_zero, k_lr, k_step = fwd.slots["idx"], bwd.slots["gt"], adam.slots["zero"], adam.slots["lr"], adam.slots["step"]
+        cur, k_cur = (a, adam.slots["loss_cur"]) if det else (b, bwd.slots["loss"])     # who adds to the iteration's loss words
+
+        def run(idx_ptr, gt_ptr, lr, step, li):
+            f[k_idx], b[k_gt], a[k_zero], a[k_lr], a[k_step], cur[k_cur] = idx_ptr, gt_ptr, loss_p[li ^ 1], lr, step, loss_p[li]
+            ops.check(fwd() or bwd() or wgrad() or adam(), "npp_light16_* (an iteration of the set)")
+        return run
+
+    def _train_step_bf16(self, x_pos, x_per, gt, idx=None):
+        """train_step() on the 16-bit chains: one _iteration_bf16 (a non-adaptive pixel loss: its own launch, d pred handed to the chain)."""
+        n0 = self.nets[0]
+        step, lr = n0.opt_step + 1, n0.lr
         loss = self._loss2[self._li]
-        part = None
-        if self.quad > 0:                                   # non-adaptive pixel loss: its own launch, d pred handed to the chain
-            assert not multi
+        if self.quad > 0:
+            assert gt.dim() == 2
+            ws = self._work16(gt.shape[0])
+            if not self._pack16_valid:
+                ops.light16_pack(self._desc, self.params, self._pack16)
+            ops.light16_fwd(self._desc, self.params, self._pack16, x_per.contiguous(), x_pos.contiguous(), ws["actF"], ws["pred"], idx=idx)
             dp = ws.setdefault("dpred", torch.empty_like(ws["pred"]))
             ops.pixel_loss_quad(ws["pred"], gt, None, self.quad, 1.0, loss, dp)
             ops.light16_bwd(self._desc, self.params, self._pack16, ws["actF"], ws["pred"], dp, ws["dzF"])
-        elif ops.DETERMINISTIC:
-            # bit-reproducible fit: the blocks' loss / latent-gradient sums by plain stores, added in block order by the Adam launch
-            part = ws.get("part")
-            if part is None:
-                part = ws["part"] = torch.zeros(self.C, B // 64, 8, dtype=torch.float32, device=self.device)
-            ops.light16_bwd_det(self._desc, self.params, self._pack16, ws["actF"], ws["pred"], ws["dzF"], gt, self.latents, self.spline,
-                                self.n_knots, self.x_scale, part)
-        else:
-            assert not multi
-            ops.light16_bwd(self._desc, self.params, self._pack16, ws["actF"], ws["pred"], None, ws["dzF"],
-                            loss_args=(gt, self.latents, self.spline, self.n_knots, self.x_scale, loss, self._dl_c))
-        ops.light16_wgrad(self._desc, ws["actF"], ws["dzF"], B, ws["gslabs"])
-        n0 = self.nets[0]
-        step, lr = n0.opt_step + 1, n0.lr
-        self._li ^= 1
-        if part is not None:
-            ops.light16_adam_pack_det(self._desc, self.params, self.m, self.v, self.n_params, ws["gslabs"], self._pack16, self.latents,
-                                      self.lat_m, self.lat_v, self._dl_c, self._loss2[self._li], lr, step, part, loss)
-        else:
+            ops.light16_wgrad(self._desc, ws["actF"], ws["dzF"], gt.shape[0], ws["gslabs"])
             ops.light16_adam_pack(self._desc, self.params, self.m, self.v, self.n_params, ws["gslabs"], self._pack16, self.latents, self.lat_m,
-                                  self.lat_v, self._dl_c, self._loss2[self._li], lr, step)
+                                  self.lat_v, self._dl_c, self._loss2[self._li ^ 1], lr, step)
+        else:
+            x_pos, x_per = x_pos.contiguous(), x_per.contiguous()
+            self._iteration_bf16(x_pos, x_per, gt, idx)(None if idx is None else idx.data_ptr(), gt.data_ptr(), lr, step, self._li)
+        self._li ^= 1
         self._pack16_valid, self._pack_valid = True, False
         for net in self.nets:
             net.opt_step = step
@@ -370,58 +388,20 @@ class NPPNetLightBatch:
 
     def fit_loop_bf16(self, x_pos_all, x_per_all, draws, gt_all, log=None):
         """draws.shape[0] iterations of _train_step_bf16 (iteration j: batch rows draws[j] (B int64) of the tables, targets gt_all[j] (B, 3)) with
-        the host's share stripped down: the four entry points are called with arguments marshalled ONCE (only the two row pointers, the loss
+        the host's share stripped down: the iteration's arguments are marshalled ONCE (_iteration_bf16; only the two row pointers, the loss
         word and Adam's (lr, step) change), the nets' clocks are advanced together at the end.  The same launches with the same arguments
         as the step-by-step path -- 4 x ~9 us of Python per iteration were a fifth of the set's wall time.  log: list that receives a
         copy of every iteration's loss words."""
-        import ctypes as C_
-        from ._lib import lib
         n_it, B = draws.shape
-        assert self.bf16 and B % 64 == 0 and draws.dtype == torch.int64 and draws.is_contiguous() and gt_all.is_contiguous()
-        assert gt_all.shape == (n_it, B, 3) and gt_all.dtype == torch.float32 and x_per_all.is_contiguous() and x_pos_all.is_contiguous()
-        ws = self._work16(B)
-        if not self._pack16_valid:
-            ops.light16_pack(self._desc, self.params, self._pack16)
-        Lb = lib()
-        vp = lambda t: C_.c_void_p(t.data_ptr())                                                # noqa: E731
-        desc, st = C_.byref(self._desc), ops._stream()
-        n_src, Cn = x_per_all.shape[1], self.C
-        assert x_per_all.shape == (Cn, n_src, 20) and x_pos_all.shape == (n_src, 42)
-        par, pst, pk, pks = vp(self.params), self.params.stride(0), vp(self._pack16), self._pack16.stride(0)
-        act, acs, dz, dzs, pred = vp(ws["actF"]), ws["actF"].stride(0), vp(ws["dzF"]), ws["dzF"].stride(0), vp(ws["pred"])
-        xper, xpos = vp(x_per_all), vp(x_pos_all)
-        lat, latm, latv, dl, spl = vp(self.latents), vp(self.lat_m), vp(self.lat_v), vp(self._dl_c), vp(self.spline)
-        m_, v_ = vp(self.m), vp(self.v)
-        gs = ws["gslabs"]
-        gsl, ks, ns = vp(gs), gs.shape[1], gs.shape[2]
-        loss_p = [vp(self._loss2[0]), vp(self._loss2[1])]
+        assert self.bf16 and self.quad == 0 and B % 64 == 0 and draws.is_contiguous() and gt_all.is_contiguous()
+        assert gt_all.shape == (n_it, B, 3) and gt_all.dtype == torch.float32
+        run = self._iteration_bf16(x_pos_all, x_per_all, gt_all[0], draws[0])
         d0, dstep, g0, gstep = draws.data_ptr(), draws.stride(0) * 8, gt_all.data_ptr(), gt_all.stride(0) * 4
         n0 = self.nets[0]
         step, lr, gstp, li = n0.opt_step, n0.lr, n0.global_step, self._li
-        fwd, bwd, wg, adam = Lb.npp_light16_fwd, Lb.npp_light16_bwd, Lb.npp_light16_wgrad, Lb.npp_light16_adam_pack
-        nk, xs, npar = self.n_knots, self.x_scale, self.n_params
-        det = ops.DETERMINISTIC                              # (round 6) the bit-reproducible launches: npp_light16_bwd_det / _adam_pack_det
-        if det:
-            part_t = ws.get("part")
-            if part_t is None:
-                part_t = ws["part"] = torch.zeros(Cn, B // 64, 8, dtype=torch.float32, device=self.device)
-            part, n_part = vp(part_t), B // 64
-            bwd_d, adam_d = Lb.npp_light16_bwd_det, Lb.npp_light16_adam_pack_det
         for j in range(n_it):
-            rc = fwd(desc, par, pst, pk, pks, xper, xpos, C_.c_void_p(d0 + j * dstep), n_src, Cn, B, act, acs, pred, st)
-            if det:
-                rc = rc or bwd_d(desc, par, pst, pk, pks, act, acs, pred, C_.c_void_p(g0 + j * gstep), 0, lat, spl, nk, xs, part, Cn, B, dz, dzs, st)
-            else:
-                rc = rc or bwd(desc, par, pst, pk, pks, act, acs, pred, None, C_.c_void_p(g0 + j * gstep), lat, spl, nk, xs, loss_p[li], dl, Cn, B, dz, dzs, st)
-            rc = rc or wg(desc, act, acs, dz, dzs, Cn, B, ks, gsl, ns, ks * ns, st)
             step += 1
-            if det:
-                rc = rc or adam_d(desc, par, m_, v_, pst, npar, Cn, gsl, ks, ns, ks * ns, pk, pks, lat, latm, latv, dl, loss_p[li ^ 1], lr, 0.9, 0.999,
-                                  1e-8, step, part, n_part, loss_p[li], st)
-            else:
-                rc = rc or adam(desc, par, m_, v_, pst, npar, Cn, gsl, ks, ns, ks * ns, pk, pks, lat, latm, latv, dl, loss_p[li ^ 1], lr, 0.9, 0.999, 1e-8, step, st)
-            if rc:
-                ops.check(rc, "npp_light16_* (fit_loop_bf16)")
+            run(d0 + j * dstep, g0 + j * gstep, lr, step, li)
             if log is not None:
                 log.append(self._loss2[li].clone())
             li ^= 1
@@ -441,14 +421,17 @@ class NPPNetLightBatch:
         if ws is None:
             C = self.C
             f = lambda *s_: torch.empty((C,) + s_, dtype=torch.float32, device=self.device)      # noqa: E731
-            ws = dict(stash=f(self._srow[7], B), dstash=f(self._drow[7], B), pred=f(B, 3), dpred=f(B, 3), draw=f(B, 3))
+            # part: the backward blocks' loss / latent-gradient sums of the bit-reproducible launches (ops.light_bwd_det)
+            ws = dict(stash=f(self._srow[7], B), dstash=f(self._drow[7], B), pred=f(B, 3), dpred=f(B, 3), draw=f(B, 3),
+                      part=torch.zeros(C, ops.light_part_blocks(C, B), 8, dtype=torch.float32, device=self.device))
             self._ws[("fused", B)] = ws
         return ws
 
     def _train_step_fused(self, x_pos, x_per, gt, idx=None):
         """train_step() on the fused chains: pack -> forward (gathers the iteration's rows itself when idx is given) -> data gradients
         with the pixel loss folded in -> gradient clear -> ONE grouped weight-gradient launch over the feature-major stashes
-        (NPP_LIGHT_GROUPED_WGRAD=0: seven) -> Adam: 6 launches for the whole candidate set."""
+        (grouped_wgrad False: seven) -> (loss words, the backward blocks' partial sums or None) for _adam: 6 launches for the whole
+        candidate set."""
         multi = gt.dim() == 3                              # multi-image set: x_pos (C, n, 42), gt (C, B, 3), idx (C, B)
         B = gt.shape[1] if multi else gt.shape[0]
         if multi and not (ops.DETERMINISTIC and self.fused_adam and self.quad == 0):
@@ -460,18 +443,15 @@ class NPPNetLightBatch:
             if self.fused_adam:
                 self.grad.zero_()
         ops.light_fwd(self._desc, self.params, self._pack, x_per.contiguous(), x_pos.contiguous(), S, ws["pred"], idx=idx)
-        loss = self._loss2[self._li]
+        loss, part = self._loss2[self._li], None
         if self.quad > 0:
             ops.pixel_loss_quad(ws["pred"], gt, None, self.quad, 1.0, loss, ws["dpred"])
             ops.light_bwd(self._desc, self.params, self._pack, S, ws["pred"], ws["dpred"], ws["draw"], D_)
         elif ops.DETERMINISTIC and self.fused_adam:
             # bit-reproducible fit: the blocks' loss / latent-gradient sums by plain stores, added in block order by the Adam launch
-            part = ws.get("part")
-            if part is None:
-                part = ws["part"] = torch.zeros(self.C, ops.light_part_blocks(self.C, B), 8, dtype=torch.float32, device=self.device)
+            part = ws["part"]
             ops.light_bwd_det(self._desc, self.params, self._pack, S, ws["pred"], ws["draw"], D_, gt, self.latents, self.spline, self.n_knots,
                               self.x_scale, part)
-            self._part = part
         else:
             ops.light_bwd(self._desc, self.params, self._pack, S, ws["pred"], None, ws["draw"], D_,
                           loss_args=(gt, self.latents, self.spline, self.n_knots, self.x_scale, loss, self._dl_c))
@@ -483,7 +463,7 @@ class NPPNetLightBatch:
                 wsc = ws["wgrad_scratch"] = (ops.light_wgrad_det_scratch(self.C, B, self.device)
                                              if ops.DETERMINISTIC and ops.tune("light_det") else None)
             ops.light_wgrad(self._desc, S, D_, self.grad, scratch=wsc)   # all seven layers, one launch
-            return loss
+            return loss, part
         W = self.W
         for i in range(4):                                   # periodic_linears.i: x = x_per (row-major) or snake(z_{i-1}) (feature-major)
             name = f"periodic_linears.{i}"
@@ -496,7 +476,7 @@ class NPPNetLightBatch:
                                       x_snake=True)
         ops.linear_bwd_weight_strided(D_[:, dr[5]:dr[5] + W // 2], S[:, sr[4]:sr[5]], self.dw["pos_linears.0"], self.db["pos_linears.0"], True, True)
         ops.linear_bwd_weight_strided(ws["draw"], S[:, sr[5]:sr[6]], self.dw["rgb_linear"], self.db["rgb_linear"], False, True, x_snake=True)
-        return loss
+        return loss, part
 
     def _work(self, B):
         ws = self._ws.get(B)
@@ -515,14 +495,10 @@ class NPPNetLightBatch:
         C, B = x_per.shape[0], (gt.shape[1] if gt.dim() == 3 else gt.shape[0])
         if gt.dim() == 3:                                  # multi-image set (ops.light_fwd / light_bwd_det multi forms; bf16: light16_*)
             assert self.fused and B % 32 == 0 and idx is not None
-            if self.bf16 and B % 64 == 0:
-                return self._train_step_bf16(x_pos, x_per, gt, idx)
-            return self._adam(self._train_step_fused(x_pos, x_per, gt, idx))
         if self.bf16 and B % 64 == 0:
             return self._train_step_bf16(x_pos, x_per, gt, idx)
         if self.fused and B % 32 == 0:
-            loss = self._train_step_fused(x_pos, x_per, gt, idx)
-            return self._adam(loss)
+            return self._adam(*self._train_step_fused(x_pos, x_per, gt, idx))
         if idx is not None:
             x_pos, x_per = x_pos[idx], x_per[:, idx]
         ws, W, D = self._work(B), self.W, self.D
@@ -562,14 +538,14 @@ class NPPNetLightBatch:
                 ops.linear_bwd_data_batched(dz, self.w[name], ws["dh"] if dz is ws["dz"] else ws["dz"], zy=ws["z"][i - 1], act=_SNAKE)
         return self._adam(loss)
 
-    def _adam(self, loss):
-        """Adam over the stacked blobs (the candidates share the step count and the LR clock); pad columns have zero gradient."""
+    def _adam(self, loss, part=None):
+        """Adam over the stacked blobs (the candidates share the step count and the LR clock); pad columns have zero gradient.
+        part: the partial sums ops.light_bwd_det left for the latent gradients and `loss`."""
         n0 = self.nets[0]
         step, lr = n0.opt_step + 1, n0.lr
         self._li ^= 1
         if self.fused_adam:
             # optimizer.step() + zero_grad() + the packs of the next forward, one launch (csrc/npp_light.hip)
-            part, self._part = getattr(self, "_part", None), None
             if part is not None:
                 ops.light_adam_pack_det(self._desc, self.params, self.m, self.v, self.grad, self.n_params, self._pack, self.latents, self.lat_m,
                                         self.lat_v, self._dl_c, self._loss2[self._li], lr, step, part, loss)
@@ -660,21 +636,31 @@ class ProposalRanker:
         self.percep = LPIPS(net="vgg", lin_weights=lpips_lin_weights, vgg_state_dict=vgg16_state_dict, device=self.device)
         self.cx = ContextualLoss(use_vgg=True, vgg_state_dict=vgg19_state_dict, device=self.device)
 
+    def _row_generator(self):
+        """() -> the next iteration's pixel rows (min(N_rand, known pixels) indices into i_train, without replacement): the stream of
+        np.random.RandomState(0) the reference draws from (native and GIL-free, host_rng), or with rng_mode "fast" NumPy's Generator."""
+        n_train = self.i_train.shape[0]
+        n_rand = min(self.N_rand, n_train)
+        if self.rng_mode == "fast":
+            g = np.random.default_rng(0)
+            return lambda: g.choice(n_train, n_rand, replace=False)
+        from .host_rng import NativeRandomState
+        g = NativeRandomState(0)
+        return lambda: g.choice(n_train, size=[n_rand], replace=False)
+
+    def _colours(self, rows):
+        """The image's colours (n, B, 3) at an (n, B) table of pixel rows (indices into i_train, on the device)."""
+        c = self.i_train_dev[rows.reshape(-1)].long()
+        return self.img[c[:, 0], c[:, 1]].reshape(*rows.shape, 3).contiguous()
+
     def _pixel_draws(self):
         """(N_iters, n_rand) int64 on the device: the pixel rows of every iteration.  search.py:92-93 reseeds NumPy with 0 before EVERY
         candidate, so all candidates of an image walk the same index sequence: drawn once (np.random.choice(n_train, [n_rand],
         replace=False) per iteration -- a full permutation of the known pixels each, 1.3 ms of host time per iteration on a
         676 x 494 image, three times the device time of the iteration) and uploaded once, instead of per candidate and iteration."""
         if self._draws is None:
-            n_train = self.i_train.shape[0]
-            n_rand = min(self.N_rand, n_train)
-            if self.rng_mode == "fast":
-                g = np.random.default_rng(0)
-                sel = [g.choice(n_train, n_rand, replace=False) for _ in range(self.N_iters)]
-            else:
-                from .host_rng import NativeRandomState                                              # np.random.RandomState(0)'s stream, GIL-free
-                g = NativeRandomState(0)
-                sel = [g.choice(n_train, size=[n_rand], replace=False) for _ in range(self.N_iters)]
+            draw = self._row_generator()
+            sel = [draw() for _ in range(self.N_iters)]
             self._draws = torch.from_numpy(np.ascontiguousarray(np.stack(sel), np.int64)).to(self.device)   # once per image: plain copy
         return self._draws
 
@@ -685,25 +671,16 @@ class ProposalRanker:
         candidate set.  The assembled table is cached for the image's later fits (_pixel_draws)."""
         if self._draws is not None:
             if self._gt_all is None:
-                c_all = self.i_train_dev[self._draws.reshape(-1)].long()
-                self._gt_all = self.img[c_all[:, 0], c_all[:, 1]].reshape(self._draws.shape[0], self._draws.shape[1], 3).contiguous()
+                self._gt_all = self._colours(self._draws)
             yield self._draws, self._gt_all
             return
         import queue
         import threading
-        n_train = self.i_train.shape[0]
-        n_rand = min(self.N_rand, n_train)
         q = queue.Queue()
 
         def produce():
             try:
-                if self.rng_mode == "fast":
-                    g = np.random.default_rng(0)
-                    draw = lambda: g.choice(n_train, n_rand, replace=False)                           # noqa: E731
-                else:
-                    from .host_rng import NativeRandomState                                          # np.random.RandomState(0)'s stream
-                    g = NativeRandomState(0)
-                    draw = lambda: g.choice(n_train, size=[n_rand], replace=False)                   # noqa: E731
+                draw = self._row_generator()
                 for it0 in range(0, self.N_iters, chunk):
                     q.put(np.ascontiguousarray(np.stack([draw() for _ in range(min(chunk, self.N_iters - it0))]), np.int64))
                 q.put(None)
@@ -718,8 +695,7 @@ class ProposalRanker:
             if isinstance(item, BaseException):
                 raise item
             d = torch.from_numpy(item).to(self.device)
-            c = self.i_train_dev[d.reshape(-1)].long()
-            gt = self.img[c[:, 0], c[:, 1]].reshape(d.shape[0], d.shape[1], 3).contiguous()
+            gt = self._colours(d)
             parts_d.append(d)
             parts_g.append(gt)
             yield d, gt
@@ -727,7 +703,7 @@ class ProposalRanker:
 
     def fit_candidate(self, angles_deg, periods, params=None, use_graph=None, fused=None):
         """search.py:85-147 for one candidate.
-        fused (default unless NPP_LIGHT_FUSED=0 / use_graph / a topology the chains are not built for): the fused forward and
+        fused (default unless use_graph / a topology or batch the chains are not built for): the fused forward and
         data-gradient chains with a candidate set of one (NPPNetLightBatch: 13 launches per iteration, 0.25 ms); else the
         layer-by-layer path below: ~40 small dependent launches on 2048 rows, 0.39 ms per iteration.
         use_graph=True: iterations 2 .. N replay ONE captured HIP graph (torch.cuda.CUDAGraph: the same
@@ -791,7 +767,7 @@ class ProposalRanker:
     def fit_candidates(self, cands, n_streams=8, batched=None):
         """fit_candidate() for several candidates at once.  The fits are independent and one fit's iteration is ~40 small dependent
         launches that leave the chip mostly idle (128 workgroups each), so:
-        batched (default; NPP_LIGHT_BATCH=0 turns it off): every launch carries ALL the candidates (NPPNetLightBatch, the candidate
+        batched (default): every launch carries ALL the candidates (NPPNetLightBatch, the candidate
         is a grid dimension of the dense-layer kernels) -- an iteration of the whole set costs about what one candidate's did;
         else: the candidates advance together, iteration by iteration, each on one of n_streams side streams (round 2; bounded by
         the host's enqueue rate: 9 x 40 launches per iteration).
@@ -809,8 +785,7 @@ class ProposalRanker:
         if batched:
             return self._fit_candidates_batched(cands)
         draws = self._pixel_draws()
-        c_all = self.i_train_dev[draws.reshape(-1)].long()
-        gt_all = self.img[c_all[:, 0], c_all[:, 1]].reshape(draws.shape[0], draws.shape[1], 3).contiguous()
+        gt_all = self._colours(draws)
         nets, tabs = [], []
         for angles_deg, periods in cands:
             net = NPPNetLight(angles_deg, periods, self.freqs, (self.H, self.W_img), default_light_init(self.Wn, self.D), W=self.Wn, D=self.D,
@@ -898,14 +873,20 @@ class ProposalRanker:
             t = torch.tensor(details, dtype=torch.float32, device=self.device).reshape(-1, 3)
             details = [tuple(r) for r in gather_unit_scalars(t, len(candidates)).cpu().tolist()]
             self.last_rank_collective = {"backend": dist.get_backend(), "ranks": dist.get_world_size(), "rows": len(details)}
-        d = np.array([x[0] for x in details])
-        order = np.argsort(d, kind="stable")[:min(topk, len(d))]
-        return d[order], order, details
+        return _ranking(details, topk)
+
+
+def _ranking(details, topk):
+    """Per-candidate (score, lpips, cx) -> (the topk smallest scores in order, their candidates, details) (search.py:215)."""
+    d = np.array([x[0] for x in details])
+    order = np.argsort(d, kind="stable")[:min(topk, len(d))]
+    return d[order], order, details
 
 
 def _serial_members(B, n):
     """The most chains (<= n) of B rows that one launch may carry with the block height -- hence the per-block partial sums -- of a
-    single chain's launch.  The rule itself lives in the library (light_rows_per_wg); this only asks it."""
+    single chain's launch.  The rule itself lives in the library (light_rows_per_wg: 32 or 64 rows per workgroup, NPP_LIGHT_ROWS forces
+    one); this only asks it."""
     alone = ops.light_part_blocks(1, B)
     c = 1
     while c < n and ops.light_part_blocks(c + 1, B) == alone:
@@ -936,7 +917,6 @@ def rank_images(rankers, cand_lists, topk=10):
     if not ops.DETERMINISTIC or ops.quad_coef(r0.loss_type) > 0:
         return [rk.rank(c, topk=topk) for rk, c in zip(rankers, cand_lists)]       # (the multi-image launches are the deterministic fused ones)
     bf16 = r0.precision == "bf16"
-    n_img = len(rankers)
     details = [[None] * len(c) for c in cand_lists]
     groups = {}
     for i, rk in enumerate(rankers):
@@ -959,11 +939,7 @@ def rank_images(rankers, cand_lists, topk=10):
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(min(8, len(members))) as pool:
             draws = dict(zip(members, pool.map(lambda i: rankers[i]._pixel_draws(), members)))
-        gts, xpos = {}, {}
-        for i in members:
-            rk = rankers[i]
-            c_all = rk.i_train_dev[draws[i].reshape(-1)].long()
-            gts[i] = rk.img[c_all[:, 0], c_all[:, 1]].reshape(rk.N_iters, B, 3)
+        gts, xpos = {i: rankers[i]._colours(draws[i]) for i in members}, {}
         n_max = max(rankers[i].i_train.shape[0] for i in members)
         lat = {i: None for i in members}
         act_prev = idx_all = gt_all = None
@@ -993,10 +969,5 @@ def rank_images(rankers, cand_lists, topk=10):
                 lat[i] = batch.latents[j].clone()
                 details[i][k] = rankers[i].score(batch.nets[j])
             del batch, x_pos, x_per
-    out = []
-    for i in range(n_img):
-        d = np.array([x[0] for x in details[i]])
-        order = np.argsort(d, kind="stable")[:min(topk, len(d))]
-        out.append((d[order], order, details[i]))
-    return out
+    return [_ranking(det, topk) for det in details]
 

@@ -869,42 +869,92 @@ def linear_bwd_weight_strided(dz, x, dw, db, feature_major_dz, feature_major_x, 
                                               dw.stride(1), dw.stride(0), _p(db), db.stride(0), _stream()), "npp_linear_bwd_weight_strided")
 
 
+# ---- f1: the fused NPP_Net_light chains (csrc/npp_light.hip exact fp32, csrc/npp_light16.hip bf16 operands) ---------------------------
+class BoundCall:
+    """A library entry point with its arguments checked and marshalled by the wrapper that built it (bind=True), not launched yet.
+    call() launches and returns the entry point's code for check(); before it, args[slots[name]] = value replaces an argument the
+    wrapper named (raw device addresses / scalars: their tensors are the caller's to keep valid).  A loop that repeats a launch
+    sequence pays the wrapper once (light.NPPNetLightBatch)."""
+    __slots__ = ("fn", "what", "args", "slots")
+
+    def __init__(self, what, args, slots):
+        self.fn, self.what, self.args, self.slots = getattr(lib(), what), what, list(args), slots
+
+    def __call__(self):
+        return self.fn(*self.args)
+
+
+def _go(what, args, bind=False, **slots):
+    """Launch entry point `what` -- or (bind) hand the call back; slots: argument positions that call may replace by name."""
+    if bind:
+        return BoundCall(what, args, slots)
+    check(getattr(lib(), what)(*args), what)
+
+
+def _light_fwd_inputs(x_per, x_pos, pred, idx):
+    """The forward inputs of C candidates: tables x_per (C, n, 20) and x_pos (n, 42) whose rows idx (B int64 on the device; None: n == B, row
+    r itself) are the batch -> pred (C, B, 3).  Multi-image form (x_pos (C, n, 42), idx (C, B)): every candidate is another image's fit
+    with its own tables and pixel rows.  -> (C, n, B, multi)"""
+    C, n = x_per.shape[:2]
+    B = pred.shape[1]
+    multi = x_pos.dim() == 3
+    assert x_per.is_contiguous() and x_pos.is_contiguous() and pred.is_contiguous()
+    assert x_per.shape == (C, n, 20) and x_pos.shape == ((C, n, 42) if multi else (n, 42)) and pred.shape == (C, B, 3)
+    if multi:
+        assert idx is not None and idx.dtype == torch.int64 and idx.is_contiguous() and idx.shape == (C, B)
+    else:
+        assert (idx is None and n == B) or (idx is not None and idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() == B)
+    return C, n, B, multi
+
+
+def _light_loss_args(loss_args, dpred, C, B):
+    """loss_args = (gt (B, 3), latents (C, 6), spline, n_knots, x_scale, loss (C), dlatent (C, 6)): the adaptive robust pixel loss evaluated
+    inside the backward launch (dpred unused), or None: dpred (C, B, 3) is the input.  -> the seven, None / 0 for a missing one"""
+    if loss_args is None:
+        assert dpred.is_contiguous()
+        return None, None, None, 0, 0.0, None, None
+    gt, lat, spl, nk, xs, loss, dlat = loss_args
+    assert gt.shape == (B, 3) and gt.is_contiguous() and lat.shape == (C, 6) and lat.is_contiguous() and dlat.shape == (C, 6) and dlat.is_contiguous()
+    assert loss.numel() == C and loss.is_contiguous()
+    return loss_args
+
+
+def _light_adam_state(params, others, lat4, zero):
+    """Stacked blobs (C, stride) sharing params' shape and strides, the latents and their moments / gradients (C, 6), the loss words (C)."""
+    C = params.shape[0]
+    assert all(t.shape == params.shape and t.stride() == params.stride() for t in others) and params.stride(1) == 1
+    assert all(t.shape == (C, 6) and t.is_contiguous() for t in lat4) and (zero is None or (zero.numel() == C and zero.is_contiguous()))
+    return C
+
+
+def _part_args(part, loss_cur, C):
+    """The two more arguments of the _det Adam launches: the backward blocks' sums part (C, blocks, 8) and the loss words (C) they are added to."""
+    assert part.is_contiguous() and part.shape[0] == C and part.shape[2] == 8
+    return _p(part), part.shape[1], _p(loss_cur)
+
+
 def light_pack(desc, params, pack):
     """MFMA-ordered weight copies of C stacked NPP_Net_light blobs (params (C, n) -> pack (C, npp_light_pack_floats()))."""
-    import ctypes
-    C = params.shape[0]
-    assert params.stride(1) == 1 and pack.stride(1) == 1 and pack.shape[0] == C
-    check(lib().npp_light_pack(ctypes.byref(desc), _p(params), params.stride(0), C, _p(pack), pack.stride(0), _stream()), "npp_light_pack")
+    n_c = params.shape[0]
+    assert params.stride(1) == 1 and pack.stride(1) == 1 and pack.shape[0] == n_c
+    _go("npp_light_pack", [C.byref(desc), _p(params), params.stride(0), n_c, _p(pack), pack.stride(0), _stream()])
 
 
 def light_fwd(desc, params, pack, x_per, x_pos, stash, pred, idx=None):
-    """Fused NPP_Net_light forward of C candidates: x_per (C, n, 20), x_pos (n, 42) -> pred (C, B, 3), stash (C, rows, B); batch row r is
-    table row idx[r] (idx: B int64 on the device) or r itself (idx None, n == B).
-    Multi-image form (x_pos (C, n, 42), idx (C, B)): every candidate is another image's fit with its own tables and pixel rows."""
-    import ctypes
-    C, n = x_per.shape[:2]
-    B = pred.shape[1]
-    assert x_per.is_contiguous() and x_pos.is_contiguous() and stash.is_contiguous() and pred.is_contiguous()
-    if x_pos.dim() == 3:
-        assert x_per.shape == (C, n, 20) and x_pos.shape == (C, n, 42) and pred.shape == (C, B, 3) and stash.shape[0] == C and stash.shape[2] == B
-        assert idx is not None and idx.dtype == torch.int64 and idx.is_contiguous() and idx.shape == (C, B)
-        check(lib().npp_light_fwd_multi(ctypes.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(x_per), _p(x_pos), _p(idx), n, C, B,
-                                        _p(stash), _p(pred), _stream()), "npp_light_fwd_multi")
-        return
-    assert x_per.shape == (C, n, 20) and x_pos.shape == (n, 42) and pred.shape == (C, B, 3) and stash.shape[0] == C and stash.shape[2] == B
-    assert (idx is None and n == B) or (idx is not None and idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() == B)
-    check(lib().npp_light_fwd(ctypes.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(x_per), _p(x_pos), _p(idx), n, C, B,
-                              _p(stash), _p(pred), _stream()), "npp_light_fwd")
+    """Fused NPP_Net_light forward of C candidates (_light_fwd_inputs) -> pred (C, B, 3), stash (C, rows, B)."""
+    n_c, n, B, multi = _light_fwd_inputs(x_per, x_pos, pred, idx)
+    assert stash.is_contiguous() and stash.shape[0] == n_c and stash.shape[2] == B
+    _go("npp_light_fwd_multi" if multi else "npp_light_fwd",
+        [C.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(x_per), _p(x_pos), _p(idx), n, n_c, B, _p(stash), _p(pred), _stream()])
 
 
-def light_adam_pack(desc, params, m, v, grad, n, pack, lat, lat_m, lat_v, dlat, zero, lr, step, b1=0.9, b2=0.999, eps=1e-8):
-    """Adam over C stacked blobs (C, stride) and their latents (C, 6) + gradient / loss-word clear + re-pack, one launch."""
-    import ctypes
-    C = params.shape[0]
-    assert all(t.shape == params.shape and t.stride() == params.stride() for t in (m, v, grad)) and params.stride(1) == 1
-    assert all(t.shape == (C, 6) and t.is_contiguous() for t in (lat, lat_m, lat_v, dlat)) and (zero is None or (zero.numel() == C and zero.is_contiguous()))
-    check(lib().npp_light_adam_pack(ctypes.byref(desc), _p(params), _p(m), _p(v), _p(grad), params.stride(0), n, C, _p(pack), pack.stride(0), _p(lat),
-                                    _p(lat_m), _p(lat_v), _p(dlat), _p(zero), lr, b1, b2, eps, step, _stream()), "npp_light_adam_pack")
+def light_bwd(desc, params, pack, stash, pred, dpred, draw, dstash, loss_args=None):
+    """Fused data-gradient chain: dpred (C, B, 3) -> draw (C, B, 3), dstash (C, rows, B); loss_args: _light_loss_args."""
+    n_c, B = pred.shape[:2]
+    assert all(t.is_contiguous() for t in (stash, pred, draw, dstash)) and dstash.shape[0] == n_c and dstash.shape[2] == B
+    gt, lat, spl, nk, xs, loss, dlat = _light_loss_args(loss_args, dpred, n_c, B)
+    _go("npp_light_bwd", [C.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(stash), _p(pred), _p(dpred), _p(gt), _p(lat),
+                          _p(spl), nk, xs, _p(loss), _p(dlat), n_c, B, _p(draw), _p(dstash), _stream()])
 
 
 def light_part_blocks(C, B):
@@ -912,41 +962,36 @@ def light_part_blocks(C, B):
 
 
 def light_bwd_det(desc, params, pack, stash, pred, draw, dstash, gt, lat, spline, n_knots, x_scale, part):
-    """light_bwd with the adaptive pixel loss folded in, its per-block sums to part (C, light_part_blocks(C, B), 8) by plain stores."""
-    import ctypes
-    C, B = pred.shape[:2]
-    assert all(t.is_contiguous() for t in (stash, pred, draw, dstash, part, gt, lat)) and part.shape == (C, light_part_blocks(C, B), 8)
-    if gt.dim() == 3:                                  # multi-image form: targets per candidate
-        assert gt.shape == (C, B, 3)
-        check(lib().npp_light_bwd_det_multi(ctypes.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(stash), _p(pred), _p(gt),
-                                            _p(lat), _p(spline), n_knots, x_scale, _p(part), C, B, _p(draw), _p(dstash), _stream()),
-              "npp_light_bwd_det_multi")
-        return
-    check(lib().npp_light_bwd_det(ctypes.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(stash), _p(pred), _p(gt), _p(lat),
-                                  _p(spline), n_knots, x_scale, _p(part), C, B, _p(draw), _p(dstash), _stream()), "npp_light_bwd_det")
+    """light_bwd with the adaptive pixel loss folded in, its per-block sums to part (C, light_part_blocks(C, B), 8) by plain stores.
+    gt (B, 3) shared, or (C, B, 3): targets per candidate (multi-image form)."""
+    n_c, B = pred.shape[:2]
+    assert all(t.is_contiguous() for t in (stash, pred, draw, dstash, part, gt, lat)) and part.shape == (n_c, light_part_blocks(n_c, B), 8)
+    assert gt.dim() == 2 or gt.shape == (n_c, B, 3)
+    _go("npp_light_bwd_det_multi" if gt.dim() == 3 else "npp_light_bwd_det",
+        [C.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(stash), _p(pred), _p(gt), _p(lat), _p(spline), n_knots, x_scale,
+         _p(part), n_c, B, _p(draw), _p(dstash), _stream()])
+
+
+def light_adam_pack(desc, params, m, v, grad, n, pack, lat, lat_m, lat_v, dlat, zero, lr, step, b1=0.9, b2=0.999, eps=1e-8, det=()):
+    """Adam over C stacked blobs (C, stride) and their latents (C, 6) + gradient / loss-word clear + re-pack, one launch."""
+    n_c = _light_adam_state(params, (m, v, grad), (lat, lat_m, lat_v, dlat), zero)
+    _go("npp_light_adam_pack_det" if det else "npp_light_adam_pack",
+        [C.byref(desc), _p(params), _p(m), _p(v), _p(grad), params.stride(0), n, n_c, _p(pack), pack.stride(0), _p(lat), _p(lat_m), _p(lat_v), _p(dlat),
+         _p(zero), lr, b1, b2, eps, step, *det, _stream()])
 
 
 def light_adam_pack_det(desc, params, m, v, grad, n, pack, lat, lat_m, lat_v, dlat, zero, lr, step, part, loss_cur, b1=0.9, b2=0.999, eps=1e-8):
     """light_adam_pack after light_bwd_det: the blocks' sums are added in block order (latent gradients, loss_cur (C))."""
-    import ctypes
-    C = params.shape[0]
-    assert part.is_contiguous() and part.shape[0] == C and part.shape[2] == 8
-    check(lib().npp_light_adam_pack_det(ctypes.byref(desc), _p(params), _p(m), _p(v), _p(grad), params.stride(0), n, C, _p(pack), pack.stride(0), _p(lat),
-                                        _p(lat_m), _p(lat_v), _p(dlat), _p(zero), lr, b1, b2, eps, step, _p(part), part.shape[1], _p(loss_cur), _stream()),
-          "npp_light_adam_pack_det")
+    light_adam_pack(desc, params, m, v, grad, n, pack, lat, lat_m, lat_v, dlat, zero, lr, step, b1, b2, eps, det=_part_args(part, loss_cur, params.shape[0]))
 
 
 def light_wgrad(desc, stash, dstash, grad, scratch=None):
     """All seven weight / bias gradients of the C candidates in one launch: grad (C, n) += ... (clear first).
     scratch: light_wgrad_det_scratch(C, B, device) -- the ordered-split form (npp_light_wgrad_det: chip-filling AND bit-reproducible)."""
-    import ctypes
-    C, B = stash.shape[0], stash.shape[2]
-    assert stash.is_contiguous() and dstash.is_contiguous() and grad.stride(1) == 1 and grad.shape[0] == C
-    if scratch is not None:
-        check(lib().npp_light_wgrad_det(ctypes.byref(desc), _p(stash), _p(dstash), C, B, _p(grad), grad.stride(0), _p(scratch),
-                                        scratch.numel() * 4, _stream()), "npp_light_wgrad_det")
-        return
-    check(lib().npp_light_wgrad(ctypes.byref(desc), _p(stash), _p(dstash), C, B, _p(grad), grad.stride(0), _stream()), "npp_light_wgrad")
+    n_c, B = stash.shape[0], stash.shape[2]
+    assert stash.is_contiguous() and dstash.is_contiguous() and grad.stride(1) == 1 and grad.shape[0] == n_c
+    det = [] if scratch is None else [_p(scratch), scratch.numel() * 4]
+    _go("npp_light_wgrad_det" if det else "npp_light_wgrad", [C.byref(desc), _p(stash), _p(dstash), n_c, B, _p(grad), grad.stride(0), *det, _stream()])
 
 
 def light_wgrad_det_scratch(C, B, device):
@@ -955,132 +1000,81 @@ def light_wgrad_det_scratch(C, B, device):
     return torch.zeros(n // 4, dtype=torch.float32, device=device)
 
 
-def light_bwd(desc, params, pack, stash, pred, dpred, draw, dstash, loss_args=None):
-    """Fused data-gradient chain: dpred (C, B, 3) -> draw (C, B, 3), dstash (C, rows, B).  loss_args = (gt (B, 3), latents (C, 6), spline,
-    n_knots, x_scale, loss (C), dlatent (C, 6)): the adaptive robust pixel loss is evaluated inside the launch instead (dpred unused)."""
-    import ctypes
-    C, B = pred.shape[:2]
-    assert all(t.is_contiguous() for t in (stash, pred, draw, dstash)) and dstash.shape[0] == C and dstash.shape[2] == B
-    if loss_args is None:
-        assert dpred.is_contiguous()
-        gt = lat = spl = loss = dlat = None
-        nk, xs = 0, 0.0
-    else:
-        gt, lat, spl, nk, xs, loss, dlat = loss_args
-        assert gt.shape == (B, 3) and gt.is_contiguous() and lat.shape == (C, 6) and lat.is_contiguous() and dlat.shape == (C, 6) and dlat.is_contiguous()
-        assert loss.numel() == C and loss.is_contiguous()
-    check(lib().npp_light_bwd(ctypes.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(stash), _p(pred), _p(dpred), _p(gt),
-                              _p(lat), _p(spl), nk, xs, _p(loss), _p(dlat), C, B, _p(draw), _p(dstash), _stream()), "npp_light_bwd")
-
-
-# ---- f1 on the 16-bit matrix pipe (csrc/npp_light16.hip) ------------------------------------------------------------------------
+# The 16-bit forms: packs and stashes are byte buffers (C, bytes) uint8.  bind=True: the BoundCall instead of its launch.
 def light16_sizes(B):
     """(pack bytes, forward-stash bytes, gradient-stash bytes) per candidate for batches of B rows (a multiple of 64)."""
     L = lib()
     return int(L.npp_light16_pack_bytes()), int(L.npp_light16_stash_bytes(B, 0)), int(L.npp_light16_stash_bytes(B, 1))
 
 
-def _bytes2d(t, name):
-    assert t.dtype == torch.uint8 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 16 == 0 and t.data_ptr() % 16 == 0, name
+def _bytes2d(C, **named):
+    for name, t in named.items():
+        assert t.dtype == torch.uint8 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 16 == 0 and t.data_ptr() % 16 == 0 and t.shape[0] == C, name
 
 
 def light16_pack(desc, params, pack):
     """bf16 MFMA-ordered copies (forward + transposed) of C stacked NPP_Net_light blobs: params (C, n) fp32 -> pack (C, bytes) uint8."""
-    import ctypes
-    C = params.shape[0]
-    _bytes2d(pack, "pack")
-    assert params.stride(1) == 1 and pack.shape[0] == C
-    check(lib().npp_light16_pack(ctypes.byref(desc), _p(params), params.stride(0), C, _p(pack), pack.stride(0), _stream()), "npp_light16_pack")
+    n_c = params.shape[0]
+    _bytes2d(n_c, pack=pack)
+    assert params.stride(1) == 1
+    _go("npp_light16_pack", [C.byref(desc), _p(params), params.stride(0), n_c, _p(pack), pack.stride(0), _stream()])
 
 
-def light16_fwd(desc, params, pack, x_per, x_pos, actF, pred, idx=None):
-    """light_fwd on bf16 operands: pred (C, B, 3) fp32 and the W-format forward stash actF (C, bytes) uint8."""
-    import ctypes
-    C, n = x_per.shape[:2]
-    B = pred.shape[1]
-    _bytes2d(pack, "pack")
-    _bytes2d(actF, "actF")
-    assert x_per.is_contiguous() and x_pos.is_contiguous() and pred.is_contiguous()
-    if x_pos.dim() == 3:                                   # multi-image set: per candidate its own positional table and pixel rows
-        assert x_per.shape == (C, n, 20) and x_pos.shape == (C, n, 42) and pred.shape == (C, B, 3) and actF.shape[0] == C
-        assert idx is not None and idx.dtype == torch.int64 and idx.is_contiguous() and idx.shape == (C, B)
-        check(lib().npp_light16_fwd_multi(ctypes.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(x_per), _p(x_pos), _p(idx), n,
-                                          C, B, _p(actF), actF.stride(0), _p(pred), _stream()), "npp_light16_fwd_multi")
-        return
-    assert x_per.shape == (C, n, 20) and x_pos.shape == (n, 42) and pred.shape == (C, B, 3) and actF.shape[0] == C
-    assert (idx is None and n == B) or (idx is not None and idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() == B)
-    check(lib().npp_light16_fwd(ctypes.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(x_per), _p(x_pos), _p(idx), n, C, B,
-                                _p(actF), actF.stride(0), _p(pred), _stream()), "npp_light16_fwd")
+def light16_fwd(desc, params, pack, x_per, x_pos, actF, pred, idx=None, bind=False):
+    """light_fwd on bf16 operands: pred (C, B, 3) fp32 and the W-format forward stash actF."""
+    n_c, n, B, multi = _light_fwd_inputs(x_per, x_pos, pred, idx)
+    _bytes2d(n_c, pack=pack, actF=actF)
+    return _go("npp_light16_fwd_multi" if multi else "npp_light16_fwd",
+               [C.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(x_per), _p(x_pos), _p(idx), n, n_c, B, _p(actF), actF.stride(0),
+                _p(pred), _stream()], bind, idx=7)
 
 
-def light16_bwd(desc, params, pack, actF, pred, dpred, dzF, loss_args=None):
-    """light_bwd on bf16 operands: the W-format gradient stash dzF (C, bytes) uint8; loss_args as light_bwd."""
-    import ctypes
-    C, B = pred.shape[:2]
-    _bytes2d(pack, "pack")
-    _bytes2d(actF, "actF")
-    _bytes2d(dzF, "dzF")
-    assert pred.is_contiguous() and dzF.shape[0] == C
-    if loss_args is None:
-        assert dpred.is_contiguous()
-        gt = lat = spl = loss = dlat = None
-        nk, xs = 0, 0.0
-    else:
-        gt, lat, spl, nk, xs, loss, dlat = loss_args
-        assert gt.shape == (B, 3) and gt.is_contiguous() and lat.shape == (C, 6) and lat.is_contiguous() and dlat.shape == (C, 6) and dlat.is_contiguous()
-        assert loss.numel() == C and loss.is_contiguous()
-    check(lib().npp_light16_bwd(ctypes.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(actF), actF.stride(0), _p(pred),
-                                _p(dpred), _p(gt), _p(lat), _p(spl), nk, xs, _p(loss), _p(dlat), C, B, _p(dzF), dzF.stride(0), _stream()),
-          "npp_light16_bwd")
+def light16_bwd(desc, params, pack, actF, pred, dpred, dzF, loss_args=None, bind=False):
+    """light_bwd on bf16 operands: the W-format gradient stash dzF; loss_args: _light_loss_args."""
+    n_c, B = pred.shape[:2]
+    _bytes2d(n_c, pack=pack, actF=actF, dzF=dzF)
+    assert pred.is_contiguous()
+    gt, lat, spl, nk, xs, loss, dlat = _light_loss_args(loss_args, dpred, n_c, B)
+    return _go("npp_light16_bwd", [C.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(actF), actF.stride(0), _p(pred), _p(dpred),
+                                   _p(gt), _p(lat), _p(spl), nk, xs, _p(loss), _p(dlat), n_c, B, _p(dzF), dzF.stride(0), _stream()], bind, gt=9, loss=14)
 
 
-def light16_bwd_det(desc, params, pack, actF, pred, dzF, gt, lat, spline, n_knots, x_scale, part):
+def light16_bwd_det(desc, params, pack, actF, pred, dzF, gt, lat, spline, n_knots, x_scale, part, bind=False):
     """light16_bwd with the pixel loss folded in and the blocks' loss / latent-gradient sums left in part (C, B / 64, 8) by plain stores
     (added in block order by light16_adam_pack_det): bit-reproducible.  gt (B, 3) shared, or (C, B, 3) per candidate (multi-image set)."""
-    import ctypes
-    C, B = pred.shape[:2]
-    _bytes2d(pack, "pack")
-    _bytes2d(actF, "actF")
-    _bytes2d(dzF, "dzF")
+    n_c, B = pred.shape[:2]
+    _bytes2d(n_c, pack=pack, actF=actF, dzF=dzF)
     multi = gt.dim() == 3
-    assert pred.is_contiguous() and dzF.shape[0] == C and gt.is_contiguous() and gt.shape == ((C, B, 3) if multi else (B, 3))
-    assert lat.shape == (C, 6) and lat.is_contiguous() and part.is_contiguous() and part.shape == (C, B // 64, 8) and part.dtype == torch.float32
-    check(lib().npp_light16_bwd_det(ctypes.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(actF), actF.stride(0), _p(pred),
-                                    _p(gt), 3 * B if multi else 0, _p(lat), _p(spline), n_knots, x_scale, _p(part), C, B, _p(dzF), dzF.stride(0),
-                                    _stream()), "npp_light16_bwd_det")
+    assert pred.is_contiguous() and gt.is_contiguous() and gt.shape == ((n_c, B, 3) if multi else (B, 3))
+    assert lat.shape == (n_c, 6) and lat.is_contiguous() and part.is_contiguous() and part.shape == (n_c, B // 64, 8) and part.dtype == torch.float32
+    return _go("npp_light16_bwd_det", [C.byref(desc), _p(params), params.stride(0), _p(pack), pack.stride(0), _p(actF), actF.stride(0), _p(pred), _p(gt),
+                                       3 * B if multi else 0, _p(lat), _p(spline), n_knots, x_scale, _p(part), n_c, B, _p(dzF), dzF.stride(0), _stream()],
+               bind, gt=8)
 
 
-def light16_adam_pack_det(desc, params, m, v, n, gslabs, pack, lat, lat_m, lat_v, dlat, zero, lr, step, part, loss_cur, b1=0.9, b2=0.999, eps=1e-8):
-    """light16_adam_pack after light16_bwd_det: the blocks' sums of `part` added in block order (latent gradients; loss_cur[c] += loss terms)."""
-    import ctypes
-    C, ks, ns = gslabs.shape
-    _bytes2d(pack, "pack")
-    assert params.stride(1) == 1 and params.shape[0] == C and part.is_contiguous() and part.shape[0] == C and part.shape[2] == 8
-    check(lib().npp_light16_adam_pack_det(ctypes.byref(desc), _p(params), _p(m), _p(v), params.stride(0), n, C, _p(gslabs), ks, ns, ks * ns, _p(pack),
-                                          pack.stride(0), _p(lat), _p(lat_m), _p(lat_v), _p(dlat), _p(zero), lr, b1, b2, eps, step, _p(part),
-                                          part.shape[1], _p(loss_cur), _stream()), "npp_light16_adam_pack_det")
-
-
-def light16_wgrad(desc, actF, dzF, B, gslabs):
+def light16_wgrad(desc, actF, dzF, B, gslabs, bind=False):
     """All seven weight / bias gradients of the C candidates in one launch of the grouped split-K kernel: gslabs (C, ksplit, n) fp32
     receives the ksplit partial sums (plain stores: no clearing needed, bit-reproducible)."""
-    import ctypes
-    C, ks, n = gslabs.shape
-    assert gslabs.is_contiguous() and gslabs.dtype == torch.float32 and actF.shape[0] == C and dzF.shape[0] == C
-    check(lib().npp_light16_wgrad(ctypes.byref(desc), _p(actF), actF.stride(0), _p(dzF), dzF.stride(0), C, B, ks, _p(gslabs), n, ks * n, _stream()),
-          "npp_light16_wgrad")
+    n_c, ks, n = gslabs.shape
+    assert gslabs.is_contiguous() and gslabs.dtype == torch.float32 and actF.shape[0] == n_c and dzF.shape[0] == n_c
+    return _go("npp_light16_wgrad", [C.byref(desc), _p(actF), actF.stride(0), _p(dzF), dzF.stride(0), n_c, B, ks, _p(gslabs), n, ks * n, _stream()], bind)
 
 
-def light16_adam_pack(desc, params, m, v, n, gslabs, pack, lat, lat_m, lat_v, dlat, zero, lr, step, b1=0.9, b2=0.999, eps=1e-8):
+def light16_adam_pack(desc, params, m, v, n, gslabs, pack, lat, lat_m, lat_v, dlat, zero, lr, step, b1=0.9, b2=0.999, eps=1e-8, bind=False, det=()):
     """Adam over C stacked blobs (gradient = the slabs summed in order) and their latents + loss-word clear + bf16 re-pack, one launch."""
-    import ctypes
-    C, ks, ns = gslabs.shape
-    _bytes2d(pack, "pack")
-    assert all(t.shape == params.shape and t.stride() == params.stride() for t in (m, v)) and params.stride(1) == 1 and params.shape[0] == C
-    assert all(t.shape == (C, 6) and t.is_contiguous() for t in (lat, lat_m, lat_v, dlat)) and (zero is None or (zero.numel() == C and zero.is_contiguous()))
-    check(lib().npp_light16_adam_pack(ctypes.byref(desc), _p(params), _p(m), _p(v), params.stride(0), n, C, _p(gslabs), ks, ns, ks * ns, _p(pack),
-                                      pack.stride(0), _p(lat), _p(lat_m), _p(lat_v), _p(dlat), _p(zero), lr, b1, b2, eps, step, _stream()),
-          "npp_light16_adam_pack")
+    n_c, ks, ns = gslabs.shape
+    _bytes2d(n_c, pack=pack)
+    assert _light_adam_state(params, (m, v), (lat, lat_m, lat_v, dlat), zero) == n_c
+    return _go("npp_light16_adam_pack_det" if det else "npp_light16_adam_pack",
+               [C.byref(desc), _p(params), _p(m), _p(v), params.stride(0), n, n_c, _p(gslabs), ks, ns, ks * ns, _p(pack), pack.stride(0), _p(lat), _p(lat_m),
+                _p(lat_v), _p(dlat), _p(zero), lr, b1, b2, eps, step, *det, _stream()], bind, zero=17, lr=18, step=22, loss_cur=25)
+
+
+def light16_adam_pack_det(desc, params, m, v, n, gslabs, pack, lat, lat_m, lat_v, dlat, zero, lr, step, part, loss_cur, b1=0.9, b2=0.999, eps=1e-8,
+                          bind=False):
+    """light16_adam_pack after light16_bwd_det: the blocks' sums of `part` added in block order (latent gradients; loss_cur[c] += loss terms)."""
+    return light16_adam_pack(desc, params, m, v, n, gslabs, pack, lat, lat_m, lat_v, dlat, zero, lr, step, b1, b2, eps, bind,
+                             det=_part_args(part, loss_cur, params.shape[0]))
 
 
 def act_bwd(dy, zy, act, dz):
