@@ -825,6 +825,35 @@ int npp_resize_bilinear(const float* d_x, int N, int h, int w, int H, int W, int
 int npp_shift_search(const float* d_act_chw, const float* d_mask_hw, int C, int h, int w,
                      const int32_t* d_shifts_xy, int n, int edge_searching, float* d_losses, void* stream);
 
+/* ---- segmentation task: the per-pixel half of the initial coarse segmentation ------------------ */
+/* loaders/loaders.py:162-205 runs SLIC superpixels, per-superpixel colour statistics, a Gaussian mixture and a graph cut before
+ * the fit; the per-pixel work is here, the per-superpixel work (a few hundred nodes) on the host (init_segment.py).  Every entry
+ * is bit-reproducible: member sums are integer sums.  Images are (H, W, 3) uint8 RGB; Lab planes are (3, H, W) fp32; labels are
+ * (H, W) int32 with 0 = outside the mask and k + 1 = centre / superpixel k; centres are (K, 5) fp32 rows (y, x, L, a, b).
+ * npp_slic_prepare (loaders.py:152, imsegm/superpixels.py:53-64 -> skimage.segmentation.slic(sigma = 1, convert2lab)): scale to
+ *   [0, 1] by (v - vmin) / (vmax - vmin), Gaussian blur sigma = 1 per channel (separable, reflect border, truncated at 4 sigma),
+ *   sRGB -> CIELAB (D65), divided by the compactness m = (sp_size * sp_regul)^1.5 (superpixels.py:59).  d_tmp_3hw: 3 H W floats.
+ * npp_slic_assign (the assignment step of skimage's _slic_cython): every mask pixel takes the centre minimising
+ *   D2 = |Lab_p - Lab_k|^2 + |p - c_k|^2 / S^2 among the centres within +-2S of it on both axes, lowest k on a tie; a mask pixel
+ *   with no centre in that window takes the nearest of all centres by the same D2.
+ * npp_slic_update (its update step): every centre becomes the mean (y, x, L, a, b) of its members; no members: unchanged.  The
+ *   Lab values enter their sums rounded to 2^-20.  d_scratch: npp_slic_update_scratch_bytes(K) bytes, no initial content required.
+ * npp_slic_features (imsegm/pipelines.py:253-278, descriptors.py:787-858: 'color': mean, median, meanGrad): per superpixel
+ *   1..N of ANY label image (no bounding window assumed; labels outside 1..N are skipped) the member count and a row of 11
+ *   floats: centroid (y, x), per-channel mean of the 0..255 values, exact per-channel median (256-bin histogram; the mean of the
+ *   two middle values for an even count, as np.median), per-channel mean of np.gradient(ch)[0] + np.gradient(ch)[1].  A label
+ *   without pixels gives count 0 and NaN.  H, W >= 2.  d_scratch: npp_slic_features_scratch_bytes(N) bytes, as above. */
+int npp_slic_prepare(const uint8_t* d_img_hw3, int H, int W, float vmin, float vmax, float m, float* d_tmp_3hw, float* d_lab_3hw,
+                     void* stream);
+int npp_slic_assign(const float* d_lab_3hw, const uint8_t* d_mask_hw, int H, int W, const float* d_centres_k5, int K, float S,
+                    int32_t* d_labels_hw, void* stream);
+int64_t npp_slic_update_scratch_bytes(int K);
+int npp_slic_update(const float* d_lab_3hw, const int32_t* d_labels_hw, int H, int W, float* d_centres_k5, int K, void* d_scratch,
+                    int64_t scratch_bytes, void* stream);
+int64_t npp_slic_features_scratch_bytes(int N);
+int npp_slic_features(const uint8_t* d_img_hw3, const int32_t* d_labels_hw, int H, int W, int N, int32_t* d_count_n, float* d_feat_n11,
+                      void* d_scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- host side: the reference's NumPy random stream, GIL-free ----------------------- */
 /* numpy.random.RandomState(seed) restated bit for bit for the three draws of an iteration (models/sampler.py:260,324;
  * NPP_completion/train.py:172): MT19937 with init_genrand seeding, uniform() from the 53-bit double, and

@@ -152,6 +152,12 @@ SYMBOLS = {
                                             _i32, _f32, _f32, _f32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "npp_selftest_mfma": (_i32, [_vp, _vp]),
     "npp_shift_search": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "npp_slic_prepare": (_i32, [_vp, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp]),
+    "npp_slic_assign": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _f32, _vp, _vp]),
+    "npp_slic_update_scratch_bytes": (_i64, [_i32]),
+    "npp_slic_update": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _i64, _vp]),
+    "npp_slic_features_scratch_bytes": (_i64, [_i32]),
+    "npp_slic_features": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "npp_rng_create": (_vp, [C.c_uint32]),
     "npp_rng_destroy": (None, [_vp]),
     "npp_rng_seed": (_i32, [_vp, C.c_uint32]),

@@ -229,13 +229,19 @@ def blur_with_mask(img, mask, sigma=3):
     return g(img * mask) / (g(mask) + 1e-6) * mask
 
 
-def load_npp_segmentation(datadir, p_topk=3, period_mask=None, non_period_mask=None):
+def load_npp_segmentation(datadir, p_topk=3, period_mask=None, non_period_mask=None, init_seg=None, nb_classes=3, sp_size=20,
+                          sp_regul=0.1, seed=0, device="cuda:0"):
     """loaders/loaders.py:141-239 -> dict(img, blur_img, period_mask (H,W,1), non_period_mask (H,W,1), valid_mask, shifts,
-    angles, periods, patch_size).  The INITIAL coarse segmentation the reference computes with its vendored imsegm package
-    (SLIC superpixels + GMM + graph cut, loaders.py:162-205) is outside this build: its result is an input
-    here -- `period_mask` / `non_period_mask` arrays, or `period_mask.png` / `non_period_mask.png` (white = member) next to
-    config.odgt.  Everything after it is reproduced: the masked Gaussian blur of the image the fit trains on (:157-159), the
-    top-k periodicity and the patch size rule (:232-236)."""
+    angles, periods, patch_size, init_seg_source).  The INITIAL coarse segmentation (SLIC superpixels + GMM + graph cut through the
+    reference's vendored imsegm package, loaders.py:162-205) comes from, in this order: the `period_mask` / `non_period_mask` arrays;
+    with init_seg None (the default) or "auto", `period_mask.png` / `non_period_mask.png` (white = member) next to config.odgt; with
+    init_seg "auto" when a PNG is missing, or always with "compute", init_segment.initial_segmentation(nb_classes, sp_size, sp_regul
+    as options/arg_config.py:210-216; seed, device) -- this build's deterministic statement of that step, whose pixel work runs on
+    `device`.  init_seg None without arrays or PNGs raises FileNotFoundError.  `init_seg_source` says which it was: "arrays", "files"
+    or "computed".  The rest follows the reference: the masked Gaussian blur of the image the fit trains on (:157-159), the top-k
+    periodicity and the patch size rule (:232-236)."""
+    if init_seg not in (None, "auto", "compute"):
+        raise ValueError(f"init_seg: None, 'auto' or 'compute', not {init_seg!r}")
     info = load_data(datadir)
     img = _imread_rgb(info["fpath_gt_img"])
     valid = _imread_gray(info["fpath_valid_mask"])
@@ -247,11 +253,22 @@ def load_npp_segmentation(datadir, p_topk=3, period_mask=None, non_period_mask=N
         path = os.path.join(datadir, name)
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path}: the initial periodic / non-periodic segmentation (imsegm in the reference, "
-                                    f"loaders/loaders.py:162-205) is not computed by this build; pass it or put {name} there")
+                                    f"loaders/loaders.py:162-205) is neither passed nor on disk; put {name} there or let it be "
+                                    "computed (init_seg='auto' / --init_segmentation auto)")
         return (_imread_gray(path) > 0.5).astype(np.float64)
-    pm, npm = get(period_mask, "period_mask.png"), get(non_period_mask, "non_period_mask.png")
+    names = ("period_mask.png", "non_period_mask.png")
+    have_files = all(os.path.exists(os.path.join(datadir, n)) for n in names)
+    if period_mask is None and non_period_mask is None and (init_seg == "compute" or (init_seg == "auto" and not have_files)):
+        from PIL import Image
+        from . import init_segment
+        img_u8 = np.array(Image.open(info["fpath_gt_img"]).convert("RGB"))             # loaders.py:152: the 8-bit image itself
+        r = init_segment.initial_segmentation(img_u8, valid, nb_classes, sp_size, sp_regul, seed, device)
+        period_mask, non_period_mask, source = r["period_mask"], r["non_period_mask"], "computed"
+    else:
+        source = "arrays" if period_mask is not None and non_period_mask is not None else "files"
+    pm, npm = get(period_mask, names[0]), get(non_period_mask, names[1])
     periods = info["selected_periods"][:p_topk]
     f = lambda a: np.asarray(a, np.float32)          # noqa: E731
     return dict(img=f(img), blur_img=f(blur), period_mask=f(pm * valid), non_period_mask=f(npm), valid_mask=f(valid),
                 shifts=info["selected_shifts"][:p_topk], angles=f(info["selected_angles"][:p_topk]), periods=f(periods),
-                patch_size=patch_size_from_period(periods[0]), info=info)
+                patch_size=patch_size_from_period(periods[0]), info=info, init_seg_source=source)

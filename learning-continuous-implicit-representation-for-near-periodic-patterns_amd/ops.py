@@ -1152,6 +1152,63 @@ def resize_bilinear(x, H, W, out=None, accumulate=False):
     return out
 
 
+# ---- segmentation task: the per-pixel half of the initial coarse segmentation (include/npp_hip.h npp_slic_*) ---------------
+# Scratch is allocated per call (torch's caching allocator hands the block back): nothing is kept between two image shapes.
+def slic_prepare(img_u8, vmin, vmax, m):
+    """(H,W,3) uint8 RGB -> (3,H,W) fp32 CIELAB / m of the min-max scaled, sigma = 1 blurred image (what SLIC clusters)."""
+    _req(img_u8, torch.uint8, "img_u8")
+    H, W, ch = img_u8.shape
+    if ch != 3:
+        raise ValueError("img_u8: expected (H, W, 3)")
+    tmp = torch.empty((3, H, W), dtype=torch.float32, device=img_u8.device)
+    lab = torch.empty((3, H, W), dtype=torch.float32, device=img_u8.device)
+    check(lib().npp_slic_prepare(_p(img_u8), H, W, float(vmin), float(vmax), float(m), _p(tmp), _p(lab), _stream()), "npp_slic_prepare")
+    return lab
+
+
+def slic_assign(lab, mask_u8, centres, S, labels=None):
+    """lab (3,H,W) fp32, mask (H,W) uint8, centres (K,5) fp32 rows (y, x, L, a, b), step S -> labels (H,W) int32: 0 outside the mask,
+    k + 1 for centre k."""
+    _req(lab, torch.float32, "lab")
+    H, W = lab.shape[1:]
+    _req(mask_u8, torch.uint8, "mask_u8", (H, W))
+    _req(centres, torch.float32, "centres", (centres.shape[0], 5))
+    if labels is None:
+        labels = torch.empty((H, W), dtype=torch.int32, device=lab.device)
+    else:
+        _req(labels, torch.int32, "labels", (H, W))
+    check(lib().npp_slic_assign(_p(lab), _p(mask_u8), H, W, _p(centres), centres.shape[0], float(S), _p(labels), _stream()), "npp_slic_assign")
+    return labels
+
+
+def slic_update(lab, labels, centres):
+    """In place: every centre becomes the mean (y, x, L, a, b) of the pixels labelled k + 1; a centre without members is kept."""
+    _req(lab, torch.float32, "lab")
+    H, W = lab.shape[1:]
+    _req(labels, torch.int32, "labels", (H, W))
+    _req(centres, torch.float32, "centres", (centres.shape[0], 5))
+    K = centres.shape[0]
+    nbytes = check(lib().npp_slic_update_scratch_bytes(K), "npp_slic_update_scratch_bytes")
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=lab.device)
+    check(lib().npp_slic_update(_p(lab), _p(labels), H, W, _p(centres), K, _p(ws), int(nbytes), _stream()), "npp_slic_update")
+    return centres
+
+
+def slic_features(img_u8, labels, N):
+    """Per superpixel 1..N of an (H,W) int32 label image over an (H,W,3) uint8 image -> count (N,) int32 and (N,11) fp32 rows:
+    centroid (y, x), mean x 3, median x 3, meanGrad x 3 (NaN for a label without pixels)."""
+    _req(img_u8, torch.uint8, "img_u8")
+    H, W = img_u8.shape[:2]
+    _req(labels, torch.int32, "labels", (H, W))
+    N = int(N)
+    nbytes = check(lib().npp_slic_features_scratch_bytes(N), "npp_slic_features_scratch_bytes")
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=img_u8.device)
+    count = torch.empty(N, dtype=torch.int32, device=img_u8.device)
+    feat = torch.empty((N, 11), dtype=torch.float32, device=img_u8.device)
+    check(lib().npp_slic_features(_p(img_u8), _p(labels), H, W, N, _p(count), _p(feat), _p(ws), int(nbytes), _stream()), "npp_slic_features")
+    return count, feat
+
+
 # ---- remapping variant: Gram-matrix style loss pieces (models/style_loss.py:37-74) ----------------------------
 _gram_ws = {}
 

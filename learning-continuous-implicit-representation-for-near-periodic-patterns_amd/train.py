@@ -32,6 +32,13 @@ def parse(argv=None):
     ap.add_argument("--lpips_thresh", type=float, default=0.3)
     ap.add_argument("--lpips_layers", type=int, default=1)
     ap.add_argument("--blur_thresh", type=float, default=50)
+    ap.add_argument("--init_segmentation", default="auto", choices=["file", "auto", "compute"],
+                    help="segmentation: where the initial periodic / non-periodic masks (loaders.py:162-205) come from.  file: "
+                         "period_mask.png / non_period_mask.png next to config.odgt; compute: npp_amd.init_segment (SLIC superpixels on "
+                         "the GPU, mixture model and graph cut on the host); auto: the files when both exist, else computed")
+    ap.add_argument("--nb_classes", type=int, default=3, help="classes of the initial segmentation (arg_config.py:210)")
+    ap.add_argument("--sp_size", type=int, default=20, help="superpixel size of the initial segmentation (arg_config.py:212)")
+    ap.add_argument("--sp_regul", type=float, default=0.1, help="superpixel regularisation of the initial segmentation (arg_config.py:214)")
     ap.add_argument("--contextual_weight", type=float, default=None)
     ap.add_argument("--style_weight", type=float, default=1.0)
     ap.add_argument("--datadir", required=True)
@@ -140,22 +147,25 @@ def _plan(argv=None):
     from .fit import CompletionFit
     remap = args.task == "remapping"
     seg = args.task == "segmentation"
-    if remap:
-        d = nio.load_npp_remapping(args.datadir, args.p_topk, args.blur_thresh)
-        d["mask"], d["masked_img"] = d["clear_mask"], d["img"]
-    elif seg:
-        d = nio.load_npp_segmentation(args.datadir, args.p_topk)
-        d["mask"], d["masked_img"] = d["period_mask"], d["blur_img"]
-    else:
-        # --normalize_type 2: tanh output; the reference rescales only the evaluation image (loaders.py:111), training stays on
-        # masked_img in [0, 1] (train.py:173) -- reproduced, not fixed
-        d = nio.load_npp_completion(args.datadir, args.p_topk, args.invalid_as_unknown, normalize_type=args.normalize_type)
     name = os.path.basename(os.path.normpath(args.datadir))
     expname = args.expname if not ((remap or seg) and args.expname == "completion") else args.task
     outroot = os.path.join(args.basedir, f"{expname}_top{args.p_topk}", name)
     if os.path.exists(outroot):                                                             # train.py:42-44: results are never overwritten
         print(f"{args.task.capitalize()}: file exists, exit!!")
         return None
+    if remap:
+        d = nio.load_npp_remapping(args.datadir, args.p_topk, args.blur_thresh)
+        d["mask"], d["masked_img"] = d["clear_mask"], d["img"]
+    elif seg:
+        # (the masks are computed here, not in _build: they are part of the loaded data, and no directory is needed for them)
+        d = nio.load_npp_segmentation(args.datadir, args.p_topk, init_seg=None if args.init_segmentation == "file" else args.init_segmentation,
+                                      nb_classes=args.nb_classes, sp_size=args.sp_size, sp_regul=args.sp_regul, seed=args.seed,
+                                      device=args.device)
+        d["mask"], d["masked_img"] = d["period_mask"], d["blur_img"]
+    else:
+        # --normalize_type 2: tanh output; the reference rescales only the evaluation image (loaders.py:111), training stays on
+        # masked_img in [0, 1] (train.py:173) -- reproduced, not fixed
+        d = nio.load_npp_completion(args.datadir, args.p_topk, args.invalid_as_unknown, normalize_type=args.normalize_type)
     plan = _Job()
     plan.args, plan.d, plan.outroot, plan.name, plan.remap, plan.seg, plan.fit = args, d, outroot, name, remap, seg, None
     return plan
@@ -169,6 +179,9 @@ def _build(plan, stacked=False):
     from .fit import CompletionFit
     args, d, outroot, name, remap, seg = plan.args, plan.d, plan.outroot, plan.name, plan.remap, plan.seg
     os.makedirs(outroot, exist_ok=True)
+    if seg:                                                  # loaders.py:208-212: white = non-periodic in the initial segmentation
+        nio.imsave(os.path.join(outroot, "segment_init.png"), np.repeat(np.asarray(d["non_period_mask"] > 0, np.float64), 3, 2))
+        print(f"initial segmentation ({d['init_seg_source']}): {float((d['period_mask'] > 0).mean()):.3f} of the image periodic")
     print("Loaded NPP", d["img"].shape, args.datadir)
     print("selected_angles: " + str(np.asarray(d["angles"]).tolist()))
     print("selected_periods: " + str(np.asarray(d["periods"]).tolist()))
