@@ -854,6 +854,24 @@ int64_t npp_slic_features_scratch_bytes(int N);
 int npp_slic_features(const uint8_t* d_img_hw3, const int32_t* d_labels_hw, int H, int W, int N, int32_t* d_count_n, float* d_feat_n11,
                       void* d_scratch, int64_t scratch_bytes, void* stream);
 
+/* ---- remapping task: blur detection (NPP_remapping/blur_detection.py:13-60) ------------------------------------------------ */
+/* The per-pixel work of get_blur_map; the normalisation and the percentile between the share and the morphology are the caller's
+ * (blur.py).  No entry keeps state in device memory between launches and none uses atomics: results are bit-reproducible.
+ * npp_rgb_to_gray_u8 (blur_detection.py:14, cv2.cvtColor(img, COLOR_RGB2GRAY) on uint8): (H, W, 3) -> (H, W),
+ *   (R 4899 + G 9617 + B 1868 + 8192) >> 14, OpenCV's 14-bit fixed point; exact.
+ * npp_blur_sv_share (blur_detection.py:32-46): per pixel (i, j), sum(s[:sv_num]) / (sum(s) + 1e-6) with s the singular values of
+ *   the 20 x 20 block new_img[i:i+20, j:j+20] of the padded image of :15-30, gathered through the reference's own index map
+ *   (rows 10 - i for i < 10, rows 2H - i for i > H + 9, counted from the end where that is negative; columns alike) and never
+ *   materialised.  float64 one-sided Jacobi, float64 out.  The window is fixed (win_size = 10); H, W > 10; sv_num in 1..20.
+ * npp_binary_morph (blur_detection.py:54-56, scipy.ndimage.binary_erosion / binary_dilation(iterations), default 4-connected
+ *   cross, border_value 0): (H, W) uint8 (non-zero = set) -> (H, W) uint8 0 / 1 after `iterations` (1..254) erosions (dilate = 0:
+ *   eats inwards from the image border) or dilations (dilate = 1), as ONE pass with the L1 ball of that radius.  d_tmp_hw: H W
+ *   bytes of its own, no initial content required; d_out_hw may be d_in_hw. */
+int npp_rgb_to_gray_u8(const uint8_t* d_img_hw3, int H, int W, uint8_t* d_gray_hw, void* stream);
+int npp_blur_sv_share(const uint8_t* d_gray_hw, int H, int W, int sv_num, double* d_share_hw, void* stream);
+int npp_binary_morph(const uint8_t* d_in_hw, int H, int W, int iterations, int dilate, uint8_t* d_tmp_hw, uint8_t* d_out_hw,
+                     void* stream);
+
 /* ---- host side: the reference's NumPy random stream, GIL-free ----------------------- */
 /* numpy.random.RandomState(seed) restated bit for bit for the three draws of an iteration (models/sampler.py:260,324;
  * NPP_completion/train.py:172): MT19937 with init_genrand seeding, uniform() from the 53-bit double, and

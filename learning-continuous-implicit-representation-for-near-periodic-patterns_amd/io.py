@@ -206,13 +206,19 @@ def get_blur_map(img_u8, win_size=10, sv_num=3, thresh=50):
     return blur, (~binary).astype(np.float64) * 255
 
 
-def load_npp_remapping(datadir, p_topk=3, blur_thresh=50):
-    """loaders/loaders.py:244-304 -> dict(img, clear_mask (H,W,1) in [0,1], valid_mask, shifts, angles, periods, patch_size)."""
+def load_npp_remapping(datadir, p_topk=3, blur_thresh=50, blur_device=None):
+    """loaders/loaders.py:244-304 -> dict(img, clear_mask (H,W,1) in [0,1], valid_mask, shifts, angles, periods, patch_size).
+    blur_device: None computes the clear / blurry mask on the host (get_blur_map); a device string ("cuda:0") computes it there
+    (npp_amd.blur.get_blur_map)."""
     from PIL import Image
     info = load_data(datadir)
     img_u8 = np.asarray(Image.open(info["fpath_gt_img"]).convert("RGB"))
     valid = _imread_gray(info["fpath_valid_mask"])
-    _, clear = get_blur_map(img_u8, thresh=blur_thresh)
+    if blur_device is None:
+        _, clear = get_blur_map(img_u8, thresh=blur_thresh)
+    else:
+        from . import blur as gpu_blur
+        _, clear = gpu_blur.get_blur_map(img_u8, thresh=blur_thresh, device=blur_device)
     clear = clear[:, :, None] * valid / 255.0                          # :263-274 (valid already / 255 here)
     periods = info["selected_periods"][:p_topk]
     return dict(img=(img_u8 / 255.0).astype(np.float32), clear_mask=clear.astype(np.float32), valid_mask=valid.astype(np.float32),

@@ -1209,6 +1209,43 @@ def slic_features(img_u8, labels, N):
     return count, feat
 
 
+# ---- remapping task: blur detection (include/npp_hip.h npp_rgb_to_gray_u8 / npp_blur_sv_share / npp_binary_morph) --------------
+def rgb_to_gray_u8(img_u8):
+    """(H,W,3) uint8 RGB -> (H,W) uint8 gray, OpenCV's 14-bit fixed point (== io.rgb_to_gray_u8, bit for bit)."""
+    _req(img_u8, torch.uint8, "img_u8")
+    if img_u8.dim() != 3 or img_u8.shape[2] != 3:
+        raise ValueError("img_u8: expected (H, W, 3)")
+    H, W = img_u8.shape[:2]
+    gray = torch.empty((H, W), dtype=torch.uint8, device=img_u8.device)
+    check(lib().npp_rgb_to_gray_u8(_p(img_u8), H, W, _p(gray), _stream()), "npp_rgb_to_gray_u8")
+    return gray
+
+
+def blur_sv_share(gray_u8, sv_num=3):
+    """(H,W) uint8 gray -> (H,W) float64: the share of the `sv_num` largest singular values of the 20 x 20 block around every pixel
+    (blur_detection.py:32-46, window 10, the reference's own border index map)."""
+    _req(gray_u8, torch.uint8, "gray_u8")
+    if gray_u8.dim() != 2:
+        raise ValueError("gray_u8: expected (H, W)")
+    H, W = gray_u8.shape
+    out = torch.empty((H, W), dtype=torch.float64, device=gray_u8.device)
+    check(lib().npp_blur_sv_share(_p(gray_u8), H, W, int(sv_num), _p(out), _stream()), "npp_blur_sv_share")
+    return out
+
+
+def binary_morph(mask_u8, iterations, dilate):
+    """(H,W) uint8 (non-zero = set) -> (H,W) uint8 0 / 1: scipy.ndimage.binary_dilation (dilate) or binary_erosion with their
+    defaults (4-connected cross, border_value 0) after `iterations` rounds.  The scratch is allocated per call."""
+    _req(mask_u8, torch.uint8, "mask_u8")
+    if mask_u8.dim() != 2:
+        raise ValueError("mask_u8: expected (H, W)")
+    H, W = mask_u8.shape
+    tmp = torch.empty((H, W), dtype=torch.uint8, device=mask_u8.device)
+    out = torch.empty((H, W), dtype=torch.uint8, device=mask_u8.device)
+    check(lib().npp_binary_morph(_p(mask_u8), H, W, int(iterations), int(bool(dilate)), _p(tmp), _p(out), _stream()), "npp_binary_morph")
+    return out
+
+
 # ---- remapping variant: Gram-matrix style loss pieces (models/style_loss.py:37-74) ----------------------------
 _gram_ws = {}
 

@@ -32,6 +32,9 @@ def parse(argv=None):
     ap.add_argument("--lpips_thresh", type=float, default=0.3)
     ap.add_argument("--lpips_layers", type=int, default=1)
     ap.add_argument("--blur_thresh", type=float, default=50)
+    ap.add_argument("--blur_detection", default="host", choices=["host", "gpu"],
+                    help="remapping: where the clear / blurry mask (NPP_remapping/blur_detection.py) is computed.  host: io.get_blur_map "
+                         "(one batched LAPACK SVD per image row); gpu: npp_amd.blur on --device (the same mask)")
     ap.add_argument("--init_segmentation", default="auto", choices=["file", "auto", "compute"],
                     help="segmentation: where the initial periodic / non-periodic masks (loaders.py:162-205) come from.  file: "
                          "period_mask.png / non_period_mask.png next to config.odgt; compute: npp_amd.init_segment (SLIC superpixels on "
@@ -154,7 +157,8 @@ def _plan(argv=None):
         print(f"{args.task.capitalize()}: file exists, exit!!")
         return None
     if remap:
-        d = nio.load_npp_remapping(args.datadir, args.p_topk, args.blur_thresh)
+        d = nio.load_npp_remapping(args.datadir, args.p_topk, args.blur_thresh,
+                                   blur_device=args.device if args.blur_detection == "gpu" else None)
         d["mask"], d["masked_img"] = d["clear_mask"], d["img"]
     elif seg:
         # (the masks are computed here, not in _build: they are part of the loaded data, and no directory is needed for them)
