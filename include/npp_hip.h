@@ -872,6 +872,23 @@ int npp_blur_sv_share(const uint8_t* d_gray_hw, int H, int W, int sv_num, double
 int npp_binary_morph(const uint8_t* d_in_hw, int H, int W, int iterations, int dilate, uint8_t* d_tmp_hw, uint8_t* d_out_hw,
                      void* stream);
 
+/* ---- quality report: SSIM and region-wise PSNR / MAE of an image against a ground truth (metrics.py) ------------------------- */
+/* Both images are (H, W, 3) fp32 in [0, 1], read as they lie; all arithmetic and every output is float64.  No entry keeps state in
+ * device memory between launches and none uses atomics: two calls give identical bits.
+ * npp_ssim_map (metrics.ssim_map; train.py --eval_metrics, evaluate.py): the SSIM index of Wang et al. -- 11 x 11 Gaussian window,
+ *   sigma 1.5, normalised to sum 1 and applied separably; K1 = 0.01, K2 = 0.03, data range 1; population variances E[xy] - mu_x mu_y --
+ *   at every pixel whose whole window lies inside the image, averaged over the three channels: d_map is (H - 10, W - 10), entry
+ *   (i, j) belongs to image pixel (i + 5, j + 5).  There it equals what "filter with reflection, crop 5" implementations give.
+ *   H, W >= 11, NPP_ERR_ARG (nothing launched) below.
+ * npp_region_sums (metrics.report / psnr / mae / ssim): per-block partial sums over an (H, W) fp32 weight mask w, written to
+ *   d_part[block][5], block < npp_region_sums_blocks(H, W) (a function of the shape only; at most 256): 0 sum w; 1 sum w |a - b|^2 and
+ *   2 sum w |a - b| over the three channels; 3 sum w over the pixels the map covers (rows 5 .. H - 6, columns 5 .. W - 6) and
+ *   4 sum w map there.  d_ssim_map may be NULL: 3 and 4 are then 0 and any H, W >= 1 is taken.  The caller adds the blocks in order. */
+int npp_ssim_map(const float* d_a_hw3, const float* d_b_hw3, int H, int W, double* d_map, void* stream);
+int npp_region_sums_blocks(int H, int W);
+int npp_region_sums(const float* d_a_hw3, const float* d_b_hw3, const float* d_weight_hw, const double* d_ssim_map, int H, int W,
+                    double* d_part, void* stream);
+
 /* ---- host side: the reference's NumPy random stream, GIL-free ----------------------- */
 /* numpy.random.RandomState(seed) restated bit for bit for the three draws of an iteration (models/sampler.py:260,324;
  * NPP_completion/train.py:172): MT19937 with init_genrand seeding, uniform() from the 53-bit double, and

@@ -161,6 +161,9 @@ SYMBOLS = {
     "npp_rgb_to_gray_u8": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "npp_blur_sv_share": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "npp_binary_morph": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "npp_ssim_map": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "npp_region_sums_blocks": (_i32, [_i32, _i32]),
+    "npp_region_sums": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "npp_rng_create": (_vp, [C.c_uint32]),
     "npp_rng_destroy": (None, [_vp]),
     "npp_rng_seed": (_i32, [_vp, C.c_uint32]),

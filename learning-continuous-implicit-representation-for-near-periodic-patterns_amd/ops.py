@@ -1246,6 +1246,45 @@ def binary_morph(mask_u8, iterations, dilate):
     return out
 
 
+# ---- quality report (include/npp_hip.h npp_ssim_map / npp_region_sums) ----------------------------------------------------------
+SSIM_WIN = 11           # window taps per axis; the map is (H - 10, W - 10)
+
+
+def _req_img_pair(a, b):
+    _req(a, torch.float32, "a")
+    if a.dim() != 3 or a.shape[2] != 3:
+        raise ValueError("a: expected (H, W, 3)")
+    _req(b, torch.float32, "b", a.shape)
+    return int(a.shape[0]), int(a.shape[1])
+
+
+def ssim_map(a, b):
+    """Two (H,W,3) fp32 images in [0, 1] -> (H-10, W-10) float64: the SSIM index (11 x 11 Gaussian window, sigma 1.5, K1 0.01, K2 0.03,
+    data range 1), channel mean, at the pixels whose whole window lies inside.  ValueError (from the launcher's own argument check;
+    nothing is launched) when H or W is below 11."""
+    H, W = _req_img_pair(a, b)
+    out = torch.empty((max(H - SSIM_WIN + 1, 0), max(W - SSIM_WIN + 1, 0)), dtype=torch.float64, device=a.device)
+    rc = lib().npp_ssim_map(_p(a), _p(b), H, W, _p(out), _stream())
+    if rc < 0 and (H < SSIM_WIN or W < SSIM_WIN):
+        raise ValueError(lib().npp_last_error_string().decode())
+    check(rc, "npp_ssim_map")
+    return out
+
+
+def region_sums(a, b, weight, smap=None):
+    """Per-block partial sums (blocks, 5) float64 of one (H,W) fp32 weight mask over two (H,W,3) fp32 images: weights, weighted squared
+    and absolute error over the channels, and -- with `smap`, the (H-10, W-10) map of ssim_map -- the weights of the pixels the map
+    covers and the weighted map.  Fixed block count and order: the caller's sum over the blocks is bit-reproducible."""
+    H, W = _req_img_pair(a, b)
+    _req(weight, torch.float32, "weight", (H, W))
+    if smap is not None:
+        _req(smap, torch.float64, "smap", (H - SSIM_WIN + 1, W - SSIM_WIN + 1))
+    nb = check(lib().npp_region_sums_blocks(H, W), "npp_region_sums_blocks")
+    part = torch.empty((nb, 5), dtype=torch.float64, device=a.device)
+    check(lib().npp_region_sums(_p(a), _p(b), _p(weight), _p(smap), H, W, _p(part), _stream()), "npp_region_sums")
+    return part
+
+
 # ---- remapping variant: Gram-matrix style loss pieces (models/style_loss.py:37-74) ----------------------------
 _gram_ws = {}
 

@@ -44,6 +44,28 @@ def my_share(items):
     return [items[i] for i in shard_units(len(items), rank, world)], rank, world
 
 
+def metrics_table(args, names):
+    """--train-args "--eval_metrics": one table over the images of this rank from the metrics.json each fit left in its result
+    directory (name, PSNR and SSIM of the unknown region).  Printed only when the flag is among the train arguments."""
+    import json
+    if "--eval_metrics" not in shlex.split(args.train_args) or not names:
+        return
+    from .train import parse as train_parse
+    a = train_parse(["--datadir", "."] + (["--task", args.task] if args.task != "completion" else []) + shlex.split(args.train_args))
+    expname = a.expname if not (args.task != "completion" and a.expname == "completion") else args.task     # train._plan's rule
+    width = max([len(n) for n in names] + [5])
+    print(f"{'image':<{width}}  {'PSNR unknown':>12}  {'SSIM unknown':>12}")
+    for n in names:
+        try:
+            with open(os.path.join(args.basedir, f"{expname}_top{args.p_topk}", n, "metrics.json")) as f:
+                u = json.load(f)["unknown"]
+            cells = ["n/a" if u[k] is None else fmt.format(u[k]) for k, fmt in (("psnr", "{:.2f} dB"), ("ssim", "{:.4f}"))]
+        except (OSError, ValueError, KeyError):
+            cells = ["-", "-"]                                     # no report: the fit failed or was found in place without one
+        print(f"{n:<{width}}  {cells[0]:>12}  {cells[1]:>12}")
+    sys.stdout.flush()
+
+
 def main(argv=None, search_main=None, train_main=None):
     args = parse(argv)
     if args.gpus and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -86,6 +108,7 @@ def main(argv=None, search_main=None, train_main=None):
             failed.append(name)
     print(f"[run rank {rank}/{world}] {len(mine) - len(failed)} of {len(mine)} images done in {time.time() - t_all:.1f} s"
           + (f"; failed: {failed}" if failed else ""), flush=True)
+    metrics_table(args, [os.path.basename(os.path.normpath(src)) for src in mine])
     return 1 if failed else 0
 
 
@@ -174,6 +197,7 @@ def _main_stacked(args, mine, det, common, rank, world, search_main):
             failed.append(n)
     print(f"[run rank {rank}/{world}] {args.task}: {len(names)} images searched in {t1 - t_all:.1f} s, fitted {args.stack}-stacked in "
           f"{time.time() - t1:.1f} s; {len(mine) - len(failed)} of {len(mine)} done" + (f"; failed: {failed}" if failed else ""), flush=True)
+    metrics_table(args, [os.path.basename(os.path.normpath(src)) for src in mine])
     return 1 if failed else 0
 
 

@@ -89,6 +89,10 @@ def parse(argv=None):
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--save_model", action="store_true",
                     help="after a successful fit, write the network as model.npz into the image's result directory (npp_amd.render reads it)")
+    ap.add_argument("--eval_metrics", action="store_true",
+                    help="every [EVAL] line also carries the SSIM of the known and the unknown region, and the last report (PSNR, SSIM, "
+                         "MAE over all / known / unknown, npp_amd.metrics.report of the image as pred_rgb_img.png holds it) is written "
+                         "as metrics.json into the image's result directory (npp_amd.evaluate reproduces it from the files)")
     return ap.parse_args(argv)
 
 
@@ -140,6 +144,8 @@ def _plan(argv=None):
                                 ) if bad]
     if refused:
         raise SystemExit(f"{refused}: ablation switches of options/arg_config.py that the fused loop is not built for (D = 8, snake, sigmoid / tanh output); other widths / depths / activations run through reference_api.NPP_Net (dense.py)")
+    if args.eval_metrics and args.normalize_type != 1:
+        raise SystemExit("--eval_metrics judges images in [0, 1] (SSIM's data range is 1): --normalize_type 1 only")
     seg_task = args.task == "segmentation"
     from . import weights
     names = ["vgg19"] + ([] if seg_task else ["vgg16"]) + (["alexnet"] if seg_task else [])    # remapping: VGG16 is the style trunk
@@ -227,7 +233,19 @@ def _build(plan, stacked=False):
     job = plan
     job.args, job.fit, job.d, job.outroot, job.seg, job.load, job.weights, job.nio = args, fit, d, outroot, seg, load, weights, nio
     job.writer, job.pending, job.t0, job.name = ThreadPoolExecutor(1), [], time.time(), name
+    job.metrics = None                                       # --eval_metrics: the report of the newest test set
     return job
+
+
+def _metrics_report(job, pred_dev, i):
+    """--eval_metrics: npp_amd.metrics.report of the rendered image as dump_testset writes it (8 bits, invalid pixels black), computed
+    where the render and the fit's copy of the ground truth lie -- nothing is copied to the host but the partial sums -- plus the
+    iteration."""
+    from . import metrics
+    d = job.d
+    rep = metrics.report(metrics.quantised(pred_dev, d["mask"], d["valid_mask"]), job.fit.img, d["mask"], d["valid_mask"], device=pred_dev.device)
+    rep["iteration"] = int(i)
+    return rep
 
 
 def _finish(job, failed):
@@ -242,6 +260,15 @@ def _finish(job, failed):
         except Exception as e:
             write_error = e
             print(f"[WARN] writing the model file failed: {e}")
+    if failed is None and job.args.eval_metrics:            # --eval_metrics: the newest report (the final image's when no test set fell due)
+        try:
+            from .evaluate import dumps
+            rep = job.metrics if job.metrics is not None else _metrics_report(job, job.fit.render_image(), job.args.N_iters - 1)
+            with open(os.path.join(job.outroot, "metrics.json"), "w") as f:
+                f.write(dumps(rep) + "\n")
+        except Exception as e:
+            write_error = write_error or e
+            print(f"[WARN] writing metrics.json failed: {e}")
     # first the writers: a queued dump_testset re-creates its directory (os.makedirs(..., exist_ok=True)), so nothing is
     # removed while one may still run
     for p in job.pending:
@@ -405,11 +432,17 @@ def _after_iteration(job, i):
     args, fit, d, outroot, seg, load, weights, nio, writer, pending, t0 = (job.args, job.fit, job.d, job.outroot, job.seg, job.load,
                                                                            job.weights, job.nio, job.writer, job.pending, job.t0)
     if i % args.i_testset == 0:
-        pred = fit.render_image().cpu().numpy()
+        pred_dev = fit.render_image()
+        pred = pred_dev.cpu().numpy()
         os.makedirs(os.path.join(outroot, f"testset_{i:06d}"), exist_ok=True)
         pending.append(writer.submit(nio.dump_testset, os.path.join(outroot, f"testset_{i:06d}"), pred, d["img"], d["masked_img"], d["mask"],
                                      d["valid_mask"]))
-        print(f"[EVAL] iter {i}: PSNR known {fit.psnr('known'):.2f} dB, unknown {fit.psnr('unknown'):.2f} dB")
+        line = f"[EVAL] iter {i}: PSNR known {fit.psnr('known'):.2f} dB, unknown {fit.psnr('unknown'):.2f} dB"
+        if args.eval_metrics:
+            job.metrics = _metrics_report(job, pred_dev, i)
+            line += ", SSIM known {} unknown {}".format(*("n/a" if job.metrics[r]["ssim"] is None else f"{job.metrics[r]['ssim']:.4f}"
+                                                           for r in ("known", "unknown")))
+        print(line)
         if seg:                                                                         # NPP_segmentation/train.py:337-406
             from . import segment
             alex = segment.AlexFeatures(load(args.alexnet), device=args.device)
