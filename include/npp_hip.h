@@ -103,13 +103,47 @@ int npp_pack_weights_host(const float* params, void* wf, void* wb, int K, int wi
 
 /* ---- exact-fp32 fused forward (BASELINE config c4: "fp32"): the same function as npp_mlp_fwd on v_mfma_f32_32x32x2_f32
  * (f32 operands and accumulation, 157 TFLOP/s peak; no bf16 rounding anywhere) -- the reference's own arithmetic type
- * (models/networks.py:56-95 via F.linear, models/embedder.py:11-56,102-148).  Inference only (train.py:270-331).
+ * (models/networks.py:56-95 via F.linear, models/embedder.py:11-56,102-148).  The render of train.py:270-331; the exact-fp32 TRAINING
+ * chain built on it follows below (npp_mlp_fwd32_train).
  * npp_pack32_bytes / npp_pack_weights32: the fp32 A-operand pack of the blob ([layer][group of 4 k-steps][tile][lane][4]).
  * out_act: 0 raw / 1 sigmoid / 2 tanh (models/helpers.py:55-58). */
 int64_t npp_pack32_bytes(int K, int width);
 int npp_pack_weights32(const float* d_params, void* d_w32, int K, int width, void* stream);
 int npp_mlp_fwd32(const int32_t* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_w32,
                   const float* d_params, float* d_out, int out_act, void* stream);
+
+/* ---- exact-fp32 training of the fused MLP (opt-in: NPPNet(precision="fp32"), python -m npp_amd.train --precision fp32) ----------
+ * The fit's three MLP launches in the reference's own arithmetic (PyTorch fp32: NPP_completion/train.py:183-254 -- render(),
+ * loss.backward(), optimizer.step()), so that a fit can be compared with the reference without the bf16 / 8-bit operand roundings
+ * of the default chain.  Arrays (csrc/npp_layout.h "exact-fp32 TRAINING chain"): feature-major fp32 [row][Bp], nothing rounded.
+ *
+ * npp_train_workspace32: byte sizes for a padded batch of Bp rows -- sizes[0] 0, sizes[1] the fp32 stash (pre-activations of the
+ *   snake layers, f1, z_s, f2, z_p and the 22 K warped coordinates: (11.5 W + 22 K) * 4 bytes per row; the 462 K embedding columns
+ *   are formed again from the warped coordinates by the weight-gradient launch), sizes[2] the fp32 pre-activation gradients
+ *   ((11.5 W + 4) * 4 bytes per row), sizes[3] the gradient slabs: the layout and stride of npp_train_workspace, so npp_adam_step_net
+ *   and npp_grad_reduce take them unchanged. */
+int npp_train_workspace32(int K, int width, int64_t Bp, int ksplit, int64_t sizes[4]);
+/* The transposed fp32 pack the data-gradient chain streams (models/networks.py:56-95 backwards: W^T of pos_linears, feature_linear2,
+ * the f1 columns of scale_linears, feature_linear1, layers 7..1 -- the h columns of the skip layer 5): bytes, and the pack launch. */
+int64_t npp_pack32_bwd_bytes(int K, int width);
+int npp_pack_weights32_bwd(const float* d_params, void* d_w32_bwd, int K, int width, void* stream);
+/* render() of the training iteration (NPP_completion/train.py:183-189; models/helpers.py:41-62): npp_mlp_fwd32 on the same rows, bit
+ * for bit, plus the stash the two launches below read. */
+int npp_mlp_fwd32_train(const int32_t* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_w32,
+                        const float* d_params, float* d_pred, void* d_stash, int out_act, void* stream);
+/* loss.backward() through models/networks.py:56-95 / :145-173 (NPP_completion/train.py:252): d_dpred (Bp, 3) = dL/dpred (rows beyond
+ * the real batch must be 0) -> the pre-activation gradients d_dz of every layer: sigmoid / tanh output (out_act as in npp_mlp_fwd32),
+ * pos_linears, the K > 1 scale branch, feature_linear1/2, the eight snake layers and the skip at layer 4.  No gradient into the
+ * embedding.  Deterministic: no atomics. */
+int npp_mlp_bwd32(const float* d_dpred, const float* d_pred, int64_t Bp, int K, int width, const void* d_w32_bwd,
+                  const float* d_params, const void* d_stash, void* d_dz, int out_act, void* stream);
+/* The weight and bias gradients of that backward (what autograd accumulates into .grad of every nn.Linear, networks.py:40-49) as
+ * ksplit slabs in the parameter-blob layout, contracted over the rows on the fp32 MFMA.  Row tile t of the T = Bp / 64 belongs to
+ * slab s with s T / ksplit <= t < (s + 1) T / ksplit; every slab is written in full (a slab without rows holds zeros), by one
+ * workgroup per output tile in row order: no float atomics, identical bits on every run.  cfg: the embedder of the forward (its
+ * Fourier frequencies are needed to form the embedding columns again). */
+int npp_mlp_wgrad32(const void* d_dz, const void* d_stash, const npp_embed_cfg* cfg, int64_t Bp, int K, int width, int ksplit,
+                    float* d_gslabs, void* stream);
 
 /* ---- a1+a2+a4: embedder -------------------------------------------------- */
 /* Replaces Embedder_periodic.embed + Embedder.embed + cat (models/embedder.py:140-148,

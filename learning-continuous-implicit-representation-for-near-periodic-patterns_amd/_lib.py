@@ -104,6 +104,12 @@ SYMBOLS = {
     "npp_pack32_bytes": (_i64, [_i32, _i32]),
     "npp_pack_weights32": (_i32, [_vp, _vp, _i32, _i32, _vp]),
     "npp_mlp_fwd32": (_i32, [_vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "npp_train_workspace32": (_i32, [_i32, _i32, _i64, _i32, C.POINTER(_i64)]),
+    "npp_pack32_bwd_bytes": (_i64, [_i32, _i32]),
+    "npp_pack_weights32_bwd": (_i32, [_vp, _vp, _i32, _i32, _vp]),
+    "npp_mlp_fwd32_train": (_i32, [_vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "npp_mlp_bwd32": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "npp_mlp_wgrad32": (_i32, [_vp, _vp, _cfgp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "npp_embed_fwd": (_i32, [_vp, _i64, _cfgp, _vp, _i32, _i32, _vp]),
     "npp_warp_fwd": (_i32, [_vp, _i64, _cfgp, _vp, _vp]),
     "npp_train_workspace": (_i32, [_i32, _i32, _i64, _i32, C.POINTER(_i64)]),

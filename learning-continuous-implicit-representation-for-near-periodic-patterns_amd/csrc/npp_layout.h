@@ -261,6 +261,37 @@ NPP_HD int col32(int K, int l, int ks, int h) {
   }
 }
 
+// ---- exact-fp32 TRAINING chain (npp_mlp_fwd32.hip forward with stash, npp_mlp_train32.hip backward + weight gradient) --------
+// Stash and pre-activation gradients are FEATURE-major fp32 arrays [row][Bp] (an accumulator register of a tile is 32 consecutive
+// pixel rows of one feature: a coalesced 128-byte store, and both operands of the weight-gradient GEMM are contiguous along the
+// rows it contracts).  Nothing in them is rounded.  Stash rows: the pre-activations z of the eight snake layers, f1, z_s, f2
+// (K > 1), z_p, then the 22 K warped coordinates v -- the 462 K embedding columns are NOT stashed: the weight-gradient launch forms
+// sin(f v + phase) again with the forward's own expression while it stages the operand (88 K bytes per row instead of 1848 K).
+constexpr int kS32F1 = 8 * kW, kS32ZS = 9 * kW, kS32F2 = 10 * kW, kS32ZP = 11 * kW, kS32V = 11 * kW + kW / 2;
+NPP_HD int stash32_rows(int K) { return kS32V + 22 * K; }
+// gradient rows: d z of layer l at the stash row of its z (f1 / f2 are linear: their gradient IS d z), then d raw (3 rows + 1 pad)
+constexpr int kD32Raw = kS32V, kD32Rows = kD32Raw + 4;
+// transposed fp32 pack of the data-gradient chain: virtual layers of make_bwd_desc, unit = [group g][output tile nt][lane],
+// element e = W_l[8 g + e + 4 (lane >> 5)][col0 + 32 nt + (lane & 31)]
+struct BDesc32 {
+  int32_t present[kNumBwd], layer[kNumBwd], col0[kNumBwd], groups[kNumBwd];
+  int64_t off16[kNumBwd];
+  int64_t total16;
+};
+NPP_HD BDesc32 make_bdesc32(int K) {
+  const BwdDesc b = make_bwd_desc(K);
+  BDesc32 d{};
+  int64_t off = 0;
+  for (int v = 0; v < kNumBwd; ++v) {
+    d.present[v] = b.present[v]; d.layer[v] = b.layer[v]; d.col0[v] = b.col0[v];
+    d.groups[v] = (v == BP1 || v == BP2) ? kW / 16 : kW / 8;
+    d.off16[v] = b.present[v] ? off : -1;
+    if (b.present[v]) off += (int64_t)d.groups[v] * kNT * 64;
+  }
+  d.total16 = off;
+  return d;
+}
+
 // ---- training stash for wgrad: "W-format" fragment arrays -----------------------------
 // Every layer input (actF) and every pre-activation gradient (dzF) is stored as the very
 // 16-byte fragments the fused kernels hold in registers: unit (k-step ks of 16 features,

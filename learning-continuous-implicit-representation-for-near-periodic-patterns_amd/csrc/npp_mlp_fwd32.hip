@@ -2,8 +2,10 @@
 // full-resolution coord grid, fp32").  Same function as npp_mlp_fwd.hip (models/embedder.py:102-148 + :11-56,
 // models/networks.py:56-95 / :145-173, models/helpers.py:55-56), same fused structure, but every contraction runs on
 // v_mfma_f32_32x32x2_f32: f32 operands, f32 accumulate, bit for bit a k-ordered fmaf chain (157 TFLOP/s peak, 1/16 of the bf16
-// rate) -- the reference's own arithmetic type, no bf16 rounding anywhere.  Inference only (the full-image render of
-// train.py:270-331); training keeps the bf16 chain (BASELINE c2).
+// rate) -- the reference's own arithmetic type, no bf16 rounding anywhere.  The render of train.py:270-331, and -- with STASH -- the
+// forward of the exact-fp32 fit (NPPNet(precision="fp32")): the same kernel also leaves the fp32 stash (npp_layout.h "exact-fp32
+// TRAINING chain") that npp_mlp_bwd32 / npp_mlp_wgrad32 (npp_mlp_train32.hip) read; the stores touch no arithmetic, so the prediction
+// of a stashing launch equals the render's bit for bit.  The default fit keeps the bf16 chain (BASELINE c2).
 //
 // Structure: one 256-thread workgroup = 64 pixel rows (two 32-column batch tiles), GEMMs transposed (Z^T = W X^T): the
 // weights are the A operand (lane l: W[32 nt + (l & 31)][k-step's feature l >> 5]), streamed from L2 as 16-byte loads that
@@ -41,6 +43,7 @@ struct Fwd32Args {
   // render paths (CM != kCoordI32): fp32 positions instead of coords, or the implicit canvas grid (pred then holds g.n rows)
   const float* coordsf;
   npp_grid g;
+  float* stash;              // STASH: (stash32_rows(K), Bp) fp32, feature-major
 };
 
 // B operands generated from the 22 warped coordinates of one proposal (sV[i][row], fp32): k-step q < 220 contracts
@@ -65,8 +68,23 @@ struct EmbSrc32 {
   }
 };
 
+// the pre-activations (or linear outputs) of this wave's tiles -> stash rows frow0 + feature: one 128-byte store per register and half
+template <int NTW>
+__device__ __forceinline__ void stash32_tiles(const f32x16 (&acc)[NTW][kNB], float* __restrict__ S, int frow0, int64_t Bp, int64_t row0,
+                                              int nt0, int b, int h) {
+#pragma unroll
+  for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+    for (int bt = 0; bt < kNB; ++bt) {
+      float* p = S + (int64_t)(frow0 + (nt0 + nt) * 32 + 4 * h) * Bp + row0 + bt * 32 + b;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) p[(int64_t)((r & 3) + 8 * (r >> 2)) * Bp] = acc[nt][bt][r];
+    }
+}
+
 // CM: coordinate mode (npp_common.h CoordMode) -- int32 pixel indices, fp32 positions or the implicit canvas grid
-template <bool MULTI, int CM = kCoordI32>
+// STASH: also write the training stash (A_.stash)
+template <bool MULTI, int CM = kCoordI32, bool STASH = false>
 __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedDev e_arg, NetDesc d, Desc32 d32) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* R = smem;
@@ -140,10 +158,18 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
 
   f32x16 acc[2][kNB];
   // ---- L0
+  // STASH: the 22 warped coordinates of proposal p (complete in sV behind a barrier) -> stash rows kS32V + 22 p + i
+  auto stash_warp = [&](int p) {
+    for (int i = tid; i < 22 * kRowTile; i += kT32)
+      A_.stash[(int64_t)(kS32V + 22 * p + i / kRowTile) * A_.Bp + row0 + (i % kRowTile)] = sV[i];
+  };
+  auto stash_z = [&](const f32x16 (&t)[2][kNB], int frow0) { stash32_tiles<2>(t, A_.stash, frow0, A_.Bp, row0, nt0, b, h); };
   gen_warp(0);
   bias32(acc, P + d.b_off[L0], nt0, h);
   wg_barrier();
+  if (STASH) stash_warp(0);
   part32<2, kNT>(acc, rsrc, w32(L0), GE, nt0, lane, emb);
+  if (STASH) stash_z(acc, 0);
   epi32<true, 2>(acc, R, nt0, b, h);               // nobody reads R yet
   wg_barrier();
   // ---- L1..L4 (in place: read R, barrier, write R)
@@ -151,6 +177,7 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
   for (int l = L1; l <= L4; ++l) {
     bias32(acc, P + d.b_off[l], nt0, h);
     part32<2, kNT>(acc, rsrc, w32(l), GA, nt0, lane, act);
+    if (STASH) stash_z(acc, l * kW);
     wg_barrier();
     epi32<true, 2>(acc, R, nt0, b, h);
     wg_barrier();
@@ -159,6 +186,7 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
   bias32(acc, P + d.b_off[L5], nt0, h);
   part32<2, kNT>(acc, rsrc, w32(L5), GE, nt0, lane, emb);
   part32<2, kNT>(acc, rsrc, w32(L5) + GE * U, GA, nt0, lane, act);
+  if (STASH) stash_z(acc, L5 * kW);
   wg_barrier();
   epi32<true, 2>(acc, R, nt0, b, h);
   wg_barrier();
@@ -166,6 +194,7 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
   for (int l = L6; l <= L7; ++l) {
     bias32(acc, P + d.b_off[l], nt0, h);
     part32<2, kNT>(acc, rsrc, w32(l), GA, nt0, lane, act);
+    if (STASH) stash_z(acc, l * kW);
     wg_barrier();
     epi32<true, 2>(acc, R, nt0, b, h);
     wg_barrier();
@@ -174,6 +203,7 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
   f32x16 f1[2][kNB];
   bias32(f1, P + d.b_off[LF1], nt0, h);
   part32<2, kNT>(f1, rsrc, w32(LF1), GA, nt0, lane, act);
+  if (STASH) stash_z(f1, kS32F1);
   wg_barrier();
   epi32<false, 2>(f1, R, nt0, b, h);
   wg_barrier();
@@ -187,14 +217,17 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
       wg_barrier();                                // every wave is done with the previous proposal's sV
       gen_warp(p);
       wg_barrier();
+      if (STASH) stash_warp(p);
       part32<2, kNT>(acc, rsrc, w32(LS) + (uint32_t)(GA + (p - 1) * GE) * U, GE, nt0, lane, emb);
     }
+    if (STASH) stash_z(acc, kS32ZS);
     wg_barrier();
     epi32<true, 2>(acc, R, nt0, b, h);             // a_s
     wg_barrier();
     // ---- F2 (linear) -> R (in place)
     bias32(acc, P + d.b_off[LF2], nt0, h);
     part32<2, kNT>(acc, rsrc, w32(LF2), GA, nt0, lane, act);
+    if (STASH) stash_z(acc, kS32F2);
     wg_barrier();
     epi32<false, 2>(acc, R, nt0, b, h);            // f2
     wg_barrier();
@@ -209,6 +242,7 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
     bias32(accp, P + d.b_off[LP], wave, h);
     part32<1, kNT / 2>(accp, rsrc, w32(LP), GA, wave, lane, act);
   }
+  if (STASH) stash32_tiles<1>(accp, A_.stash, kS32ZP, A_.Bp, row0, wave, b, h);
   epi32<true, 1>(accp, nullptr, wave, b, h);       // a_p stays in registers
 
   // ---- rgb_linear 128 -> 3 + output activation (models/helpers.py:55-58)
@@ -288,7 +322,7 @@ extern "C" int npp_pack_weights32(const float* d_params, void* d_w32, int K, int
   return check_launch("npp_pack_weights32");
 }
 
-template <int CM>
+template <int CM, bool STASH = false>
 static int fwd32_launch(const Fwd32Args& A, const npp_embed_cfg* cfg, int64_t n_wg, void* stream, const char* who) {
   const EmbedDev e = make_embed_dev(*cfg);
   const NetDesc d = make_desc(cfg->K);
@@ -297,12 +331,12 @@ static int fwd32_launch(const Fwd32Args& A, const npp_embed_cfg* cfg, int64_t n_
   hipStream_t s = (hipStream_t)stream;
   if (cfg->K > 1) {
     static SmemOnce once;
-    if (!smem_attr(once, (const void*)mlp_fwd32_kernel<true, CM>, kSmem32)) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL((mlp_fwd32_kernel<true, CM>), grid, block, kSmem32, s, A, e, d, d32);
+    if (!smem_attr(once, (const void*)mlp_fwd32_kernel<true, CM, STASH>, kSmem32)) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; }
+    hipLaunchKernelGGL((mlp_fwd32_kernel<true, CM, STASH>), grid, block, kSmem32, s, A, e, d, d32);
   } else {
     static SmemOnce once;
-    if (!smem_attr(once, (const void*)mlp_fwd32_kernel<false, CM>, kSmem32)) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL((mlp_fwd32_kernel<false, CM>), grid, block, kSmem32, s, A, e, d, d32);
+    if (!smem_attr(once, (const void*)mlp_fwd32_kernel<false, CM, STASH>, kSmem32)) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; }
+    hipLaunchKernelGGL((mlp_fwd32_kernel<false, CM, STASH>), grid, block, kSmem32, s, A, e, d, d32);
   }
   return NPP_OK;
 }
@@ -344,5 +378,19 @@ extern "C" int npp_mlp_fwd32_grid(const npp_grid* grid, const npp_embed_cfg* cfg
   const int64_t n_wg = (grid->n + kRowTile - 1) / kRowTile;
   Fwd32Args A{nullptr, n_wg * kRowTile, (const float*)d_w32, d_params, d_out, out_act, nullptr, *grid};
   if ((rc = fwd32_launch<kCoordGrid>(A, cfg, n_wg, stream, who))) return rc;
+  return check_launch(who);
+}
+
+// The forward of the exact-fp32 fit: npp_mlp_fwd32 plus the stash (d_stash: sizes[1] of npp_train_workspace32)
+extern "C" int npp_mlp_fwd32_train(const int32_t* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_w32,
+                                   const float* d_params, float* d_pred, void* d_stash, int out_act, void* stream) {
+  const char* who = "npp_mlp_fwd32_train";
+  int rc = check_embed_cfg(cfg, who);
+  if (rc) return rc;
+  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
+  if (Bp <= 0 || Bp % kRowTile || Bp / kRowTile > 0x7fffffffLL) { set_error("%s: Bp=%lld must be a positive multiple of %d", who, (long long)Bp, kRowTile); return NPP_ERR_ARG; }
+  if (!d_coords_yx || !d_w32 || !d_params || !d_pred || !d_stash || out_act < 0 || out_act > 2) { set_error("%s: bad argument", who); return NPP_ERR_ARG; }
+  Fwd32Args A{d_coords_yx, Bp, (const float*)d_w32, d_params, d_pred, out_act, nullptr, npp_grid{}, (float*)d_stash};
+  if ((rc = fwd32_launch<kCoordI32, true>(A, cfg, Bp / kRowTile, stream, who))) return rc;
   return check_launch(who);
 }

@@ -27,8 +27,12 @@ class CompletionFit:
                  vgg19_state_dict=None, vgg16_state_dict=None, lpips_lin_weights=None, rng_mode="reference",
                  prefetch=0, use_perceptual_loss=True, task="completion", clear_mask=None, style_weight=None,
                  vgg16_style_state_dict=None, masked_img=None, width=256, no_reg_sampling=False, use_patch_weight=False,
-                 no_pix_loss=False, use_contextual_loss=True, loss_type="robust_loss_adaptive", use_adaptive_perceptual_loss=True, normalize_type=1):
+                 no_pix_loss=False, use_contextual_loss=True, loss_type="robust_loss_adaptive", use_adaptive_perceptual_loss=True, normalize_type=1,
+                 precision="bf16"):
         """img (H,W,3) float in [0,1]; mask (H,W,1) 1 = known (loaders.py:92-101).
+        precision: the arithmetic of the coordinate MLP's training launches, 'bf16' (default) or 'fp32' (NPPNet(precision=...): the
+        exact fp32 chain, the reference's own arithmetic; the iteration then takes the unfolded launch sequence -- fold_launches =
+        False -- and the evaluation renders in fp32).  It is the MLP's precision only: the VGG trunks of the patch losses stay fp16.
         normalize_type: --normalize_type (arg_config.py:31): 1 = sigmoid output, 2 = tanh output (helpers.py:55-58).  The reference
         rescales ONLY its evaluation image to [-1, 1] under 2 (loaders.py:56,111); the loop still trains on masked_img in [0, 1]
         (train.py:173) -- reproduced as it is: pass `img` already rescaled if the evaluation should see it that way.
@@ -95,7 +99,10 @@ class CompletionFit:
         self.pixel_mask = None if pixel_mask is None else torch.from_numpy(pixel_mask[..., 0].copy()).to(self.device)
         self.net = NPPNet(angles_deg, periods, freqs, (self.H, self.W), params=params, device=self.device,
                           ksplit=ksplit, lrate=lrate, lrate_decay=lrate_decay, width=width, loss_type=loss_type,
-                          out_act=int(normalize_type))
+                          out_act=int(normalize_type), precision=precision)
+        self.precision = precision
+        if precision == "fp32":
+            self.fold_launches = False                             # npp_pixel_loss, npp_trunk_patch_in, npp_patch_compose_bwd, backward
         if task == "segmentation":
             self.net.lr_clock = False                              # NPP_segmentation/train.py:408 (see NPPNet.lr_clock)
         self.N_rand = int(min(N_rand, self.i_train.shape[0]))
@@ -448,7 +455,8 @@ class CompletionFit:
             self._s_lp.wait_stream(main)
             with torch.cuda.stream(self._s_lp):
                 dx_b = self.lpips_branch(xy, nk, self.lp_w * (nk if weight is not None else 1), self.patch_loss_buf)
-        cx.hip_trunk.final_next_pack = net.wb        # the backward chain that follows streams this pack: requested into L2 early
+        # the backward chain that follows streams this pack: requested into L2 early (bf16 chain only)
+        cx.hip_trunk.final_next_pack = net.wb if net.precision == "bf16" else None
         if self.use_contextual_loss:
             dx_a = cx.fused((2 * nk, 3, P, P), nk, self.cx_w, self.patch_loss_buf, weight=weight, x0_ready=True, x0_src=x0_src)   # train.py:238-239
         else:                                                                                       # ablation: no contextual term
@@ -529,7 +537,8 @@ class CompletionFit:
     @torch.no_grad()
     def render_image(self):
         """Full H x W grid through the fused forward: the 'fitted pixels/s' pass."""
-        return self.net.render(self.i_all_dev).reshape(self.H, self.W, 3)
+        render = self.net.render_fp32 if self.net.precision == "fp32" else self.net.render
+        return render(self.i_all_dev).reshape(self.H, self.W, 3)
 
     def save_model(self, path, **meta):
         """The fitted network as a model file (modelfile.py), for render.py / NPPNet.load: weights, adaptive latents, embedder

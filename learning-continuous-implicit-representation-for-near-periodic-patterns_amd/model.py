@@ -54,13 +54,23 @@ class NPPNet:
     """
 
     def __init__(self, angles_deg, periods, freqs, res, params=None, device="cuda", ksplit=None,
-                 lrate=5e-4, lrate_decay=500, offsets=(0.0, -1.0, 1.0, 0.5, -0.5), width=NPP_WIDTH, loss_type="robust_loss_adaptive", out_act=1):
-        """loss_type: --loss_type of options/arg_config.py:34 (models/mse_calculator.py:19-23): 'robust_loss_adaptive' (default), 'l2',
+                 lrate=5e-4, lrate_decay=500, offsets=(0.0, -1.0, 1.0, 0.5, -0.5), width=NPP_WIDTH, loss_type="robust_loss_adaptive", out_act=1,
+                 precision="bf16"):
+        """precision: the arithmetic of the MLP's TRAINING launches.  'bf16' (default): the fused bf16 chain with its 8-bit / 16-bit
+        stash.  'fp32': the exact chain -- forward with an fp32 stash, data-gradient chain and weight gradients on
+        v_mfma_f32_32x32x2_f32 (npp_mlp_fwd32_train / npp_mlp_bwd32 / npp_mlp_wgrad32), the reference's own arithmetic type; Adam is
+        npp_adam_step_net on the fp32 master weights either way.  An fp32 net renders (render_image / psnr of a fit) through
+        render_fp32, render() stays the bf16 chain on packs refreshed when the weights have changed, and npp_tune("stash8") has
+        no effect on it.
+        loss_type: --loss_type of options/arg_config.py:34 (models/mse_calculator.py:19-23): 'robust_loss_adaptive' (default), 'l2',
         'robust_loss' (the two non-adaptive forms leave the adaptive latents untouched: no gradient reaches them)."""
         self.loss_type, self.quad = loss_type, ops.quad_coef(loss_type)
         if out_act not in (1, 2):
             raise ValueError("out_act: 1 (sigmoid, --normalize_type 1) or 2 (tanh, --normalize_type 2: images in [-1, 1]; helpers.py:55-58)")
         self.out_act = int(out_act)
+        if precision not in ("bf16", "fp32"):
+            raise ValueError(f"precision {precision!r}: 'bf16' (fused bf16 chain) or 'fp32' (exact fp32 training chain)")
+        self.precision = precision
         self.cfg = EmbedCfg.make(angles_deg, periods, freqs, res, offsets)
         self.K = int(self.cfg.K)
         self.width = int(width)      # 256 (BASELINE configs) or 512 (the reference's default --netwidth): one fused library each
@@ -91,6 +101,9 @@ class NPPNet:
         self.wb = torch.zeros(ops.pack_bytes(self.K, 1, self.width), dtype=torch.uint8, device=self.device)
         self._ws = {}
         self.fused_repack = True    # False: Adam and the weight re-pack as two launches (comparator of the fused adam_pack launch)
+        if precision == "fp32":
+            self.fused_repack = False   # npp_adam_step_net on the fp32 master weights, then the fp32 packs are rebuilt
+            self._w32b, self._wf_stamp = None, None
         if params is not None:
             self.load_state_dict(params)
 
@@ -125,13 +138,30 @@ class NPPNet:
         return out
 
     def repack(self):
+        if self.precision == "fp32":
+            # both fp32 packs now; the bf16 packs of render() lazily (_wf_pack)
+            self._w32_stamp = None
+            self._w32_pack()
+            self._w32b = ops.pack_weights32_bwd(self.params, self.K, self._w32b, self.width)
+            return
         ops.pack_weights(self.params, self.K, self.wf, self.wb, self.width)
+
+    def _wf_pack(self):
+        """The bf16 forward pack render() / render_at / render_grid read.  A bf16 net keeps it current in its Adam launch; an fp32 net
+        rebuilds it (and wb) here when the parameters have changed since it was made, as _w32_pack does."""
+        if self.precision == "fp32":
+            stamp = (self.opt_step, self.params._version)
+            if self._wf_stamp != stamp:
+                ops.pack_weights(self.params, self.K, self.wf, self.wb, self.width)
+                self._wf_stamp = stamp
+        return self.wf
 
     # ---- workspaces -----------------------------------------------------------------
     def workspace(self, Bp):
         ws = self._ws.get(Bp)
         if ws is None:
-            s = ops.train_workspace(self.K, Bp, self.ksplit, self.width)
+            fp32 = self.precision == "fp32"      # actT / dzT then hold the fp32 stash / pre-activation gradients
+            s = (ops.train_workspace32 if fp32 else ops.train_workspace)(self.K, Bp, self.ksplit, self.width)
             dev = self.device
             ws = {
                 "actT": torch.empty(s[1], dtype=torch.uint8, device=dev),
@@ -153,7 +183,7 @@ class NPPNet:
         if bp != n:
             pad = torch.zeros((bp - n, 2), dtype=torch.int32, device=coords.device)
             coords = torch.cat([coords, pad], 0)
-        pred = ops.mlp_fwd(coords.contiguous(), self.cfg, self.wf, self.params, width=self.width, out_act=self.out_act)
+        pred = ops.mlp_fwd(coords.contiguous(), self.cfg, self._wf_pack(), self.params, width=self.width, out_act=self.out_act)
         return pred[:n]
 
     def render_fp32(self, coords):
@@ -190,7 +220,7 @@ class NPPNet:
         bp = ops.pad_rows(n)
         if bp != n:
             c = torch.cat([c, c.new_zeros((bp - n, 2))], 0)
-        w = self._w32_pack() if precision == "fp32" else self.wf
+        w = self._w32_pack() if precision == "fp32" else self._wf_pack()
         return getattr(ops, fn + "_coordf")(c.contiguous(), self.cfg, w, self.params, out_act=self.out_act, width=self.width)[:n]
 
     def render_grid(self, size, origin=(0.0, 0.0), scale=(1.0, 1.0), precision="bf16", chunk_rows=1 << 22):
@@ -208,7 +238,7 @@ class NPPNet:
         y0, x0 = _pair(origin)
         total = Hc * Wc
         out = torch.empty((total, 3), dtype=torch.float32, device=self.device)
-        w = self._w32_pack() if precision == "fp32" else self.wf
+        w = self._w32_pack() if precision == "fp32" else self._wf_pack()
         launch = getattr(ops, fn + "_grid")
         for s0 in range(0, total, int(chunk_rows)):
             n = min(int(chunk_rows), total - s0)
@@ -250,6 +280,8 @@ class NPPNet:
     def forward_train(self, coords_padded):
         """Forward with stashes; coords must already be padded to a multiple of 64 rows."""
         ws = self.workspace(coords_padded.shape[0])
+        if self.precision == "fp32":
+            return ops.mlp_fwd32_train(coords_padded, self.cfg, self._w32_pack(), self.params, ws["pred"], ws["actT"], self.out_act, self.width)
         ops.mlp_fwd(coords_padded, self.cfg, self.wf, self.params, ws["pred"], ws["actT"], self.width, out_act=self.out_act)
         return ws["pred"]
 
@@ -257,6 +289,14 @@ class NPPNet:
         """loss.backward() through the MLP: consumes ws['dpred'] (rows beyond the batch 0).  patch = (dx_a, dx_b, fmask, rmask,
         row0, n_p, k, P, comp): the patch rows' dL/dpred is formed inside the launch from the patch losses' image gradients."""
         ws = self._ws[Bp]
+        if self.precision == "fp32":
+            if patch is not None:
+                raise ValueError("precision='fp32': the patch-folded backward launch has no fp32 form (use npp_patch_compose_bwd, then backward(Bp))")
+            if self._w32b is None:
+                self.repack()
+            ops.mlp_bwd32(ws["dpred"], ws["pred"], self.K, self._w32b, self.params, ws["actT"], ws["dzT"], self.width, out_act=self.out_act)
+            ops.mlp_wgrad32(ws["dzT"], ws["actT"], self.cfg, Bp, self.K, self.ksplit, ws["gslabs"], self.width)
+            return
         if patch is not None:
             ops.mlp_bwd_patch(ws["dpred"], ws["pred"], self.K, self.wb, self.params, ws["actT"], ws["dzT"], *patch, width=self.width, out_act=self.out_act)
         else:

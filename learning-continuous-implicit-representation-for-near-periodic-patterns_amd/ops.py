@@ -311,6 +311,48 @@ def mlp_fwd32(coords_yx, cfg, w32, params, out=None, out_act=1, width=NPP_WIDTH)
     return out
 
 
+# ---- exact-fp32 training chain (include/npp_hip.h "exact-fp32 training of the fused MLP") ------------------------------------
+def train_workspace32(K, Bp, ksplit, width=NPP_WIDTH):
+    """Byte sizes [0, fp32 stash, fp32 pre-activation gradients, gradient slabs] of the exact-fp32 fit for Bp padded rows."""
+    sizes = (C.c_int64 * 4)()
+    check(lib(width).npp_train_workspace32(K, width, Bp, ksplit, sizes), "npp_train_workspace32", width)
+    return [int(s) for s in sizes]
+
+
+def pack_weights32_bwd(params, K, w32b=None, width=NPP_WIDTH):
+    """fp32 blob -> the transposed fp32 pack of npp_mlp_bwd32."""
+    _req(params, torch.float32, "params")
+    n = int(check(lib(width).npp_pack32_bwd_bytes(K, width), "npp_pack32_bwd_bytes", width))
+    if w32b is None:
+        w32b = torch.empty(n, dtype=torch.uint8, device=params.device)
+    check(lib(width).npp_pack_weights32_bwd(_p(params), _p(w32b), K, width, _stream()), "npp_pack_weights32_bwd", width)
+    return w32b
+
+
+def mlp_fwd32_train(coords_yx, cfg, w32, params, pred, stash, out_act=1, width=NPP_WIDTH):
+    """mlp_fwd32 (bit for bit) that also writes the fp32 training stash; coords (Bp,2) int32, Bp % 64 == 0."""
+    _req(coords_yx, torch.int32, "coords")
+    _req(pred, torch.float32, "pred", (coords_yx.shape[0], 3))
+    check(lib(width).npp_mlp_fwd32_train(_p(coords_yx), coords_yx.shape[0], C.byref(cfg), width, _p(w32), _p(params), _p(pred),
+                                         _p(stash), int(out_act), _stream()), "npp_mlp_fwd32_train", width)
+    return pred
+
+
+def mlp_bwd32(dpred, pred, K, w32b, params, stash, dz, width=NPP_WIDTH, out_act=1):
+    """loss.backward() through the MLP in exact fp32: dpred (Bp,3) (rows beyond the batch 0) -> the pre-activation gradients dz."""
+    _req(dpred, torch.float32, "dpred")
+    _req(pred, torch.float32, "pred", dpred.shape)
+    check(lib(width).npp_mlp_bwd32(_p(dpred), _p(pred), dpred.shape[0], K, width, _p(w32b), _p(params), _p(stash), _p(dz),
+                                   int(out_act), _stream()), "npp_mlp_bwd32", width)
+
+
+def mlp_wgrad32(dz, stash, cfg, Bp, K, ksplit, gslabs, width=NPP_WIDTH):
+    """Weight / bias gradients of mlp_bwd32 into ksplit slabs (every slab written in full, fixed row-tile assignment, no atomics)."""
+    _req(gslabs, torch.float32, "gslabs")
+    check(lib(width).npp_mlp_wgrad32(_p(dz), _p(stash), C.byref(cfg), Bp, K, width, ksplit, _p(gslabs), _stream()),
+          "npp_mlp_wgrad32", width)
+
+
 def mlp_fwd_coordf(coords, cfg, wf, params, out=None, out_act=1, width=NPP_WIDTH):
     """Fused bf16 render on fp32 positions: coords (Bp,2) float32 [y, x], Bp % 64 == 0 -> (Bp,3)."""
     _req(coords, torch.float32, "coords")

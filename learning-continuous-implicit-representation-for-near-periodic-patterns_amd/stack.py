@@ -34,6 +34,9 @@ class StackedFit:
     def __init__(self, fits, ksplit=None):
         if not fits:
             raise ValueError("StackedFit needs at least one CompletionFit")
+        for f in fits:                  # (before any device work)
+            if f.net.precision != "bf16":
+                raise ValueError(f"StackedFit: precision='bf16' fits only (got precision={f.net.precision!r}: the exact-fp32 training chain has no stacked launches)")
         f0 = fits[0]
         self.fits, self.M = list(fits), len(fits)
         self.device = f0.device
