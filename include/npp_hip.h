@@ -947,6 +947,57 @@ int npp_sampler_set_patch(void* sampler, int patch_size, int n_samples, int64_t*
 int npp_sampler_draw(void* sampler, void* rng, int topk, double invalid_ratio, int32_t* source, int32_t* k,
                      int32_t* cen_n2, double* real_cen_ntopk2, float* weights_ntopk);
 
+/* ---- rng_mode="device": the sampler's decisions drawn on the GPU -------------------------------------------------------
+ * The same decisions as npp_sampler_draw (models/sampler.py:242-354) plus the N_rand pixel rows of
+ * NPP_completion/train.py:172, drawn from Philox4x32-10 keyed by the fit's seed instead of np.random's stream: a draw is a
+ * pure function of (seed, draw index t, inputs), for M images in one launch, with no state in device memory.
+ *   patch source      word 0 of counter (0, 0, t, 0) times 2^-32, through the comparisons of sampler.py:324-331
+ *   n of N, no repeat positions 0..n-1 of a keyed permutation of [0, N): a cycle-walking balanced Feistel network, eight
+ *                     rounds F = word 0 of counter (R, round, t, stream); stream 1 = the n_p fake-patch centres (from the
+ *                     bounds-filtered pool), stream 2 = the pixel rows (from i_train)
+ *   lattice half      GridPatchSampler.draw(): 400 candidates, bounds test, unknown count from the summed-area table,
+ *                     zero distance -> 10000, k = min over patches of min(count - 1, topk), stable order by distance then
+ *                     candidate index, weights inv / sum(inv) in float64 rounded to float
+ * npp_dev_image: the per-image constants (built once per patch size); every pointer is device memory for the launches and
+ * host memory for the *_host twins, which run the same arithmetic (csrc/npp_dev_sampler.h) on the CPU. */
+#define NPP_DEV_SRC_VAL 0
+#define NPP_DEV_SRC_TRAIN 1
+#define NPP_DEV_SRC_SAME 2
+#define NPP_DEV_MAX_IMAGES 64      /* images per launch: the draw indices ride in the kernel arguments */
+typedef struct npp_dev_image {
+  const int32_t* sat;              /* (H+1) x (W+1) summed-area table of the known mask */
+  const int32_t* pool_val;         /* bounds-filtered pools, (row, col) pairs (GridPatchSampler.pool_val / pool_train) */
+  const int32_t* pool_train;
+  int64_t n_pool_val, n_pool_train;
+  int64_t n_train;                 /* population of the pixel draw (rows of i_train) */
+  double shifts[4];                /* the two lattice shifts as (dy, dx), (dy, dx) (sampler.py:35) */
+  double invalid_ratio;
+  uint32_t seed_lo, seed_hi;       /* Philox key = (seed & 0xffffffff, seed >> 32) */
+  int32_t H, W, P, pad;            /* P = 2 * (patch_size / 2) */
+} npp_dev_image;
+
+/* int32 words of one image's record: [0] source, [1] k (0 = no valid real patch: the iteration is skipped; -1 = the drawn
+ * pool holds fewer than n_p pixels), [2] n_p, [3] t, then the (row, col) centres of the n_p fake patches followed by the n_p k
+ * real ones -- what npp_patch_gather / npp_batch_assemble take -- and from word 4 + 2 n_p (1 + topk) the n_p k float weights
+ * (n_p ones on 'same' draws, sampler.py:338). */
+int64_t npp_dev_sampler_record_words(int n_p, int topk);
+/* The decision launch: one workgroup per image, one wave per fake patch in turn (400 candidates, four table look-ups each,
+ * wave-level stable selection), the minimum over the patches and the compact record behind a barrier.  h_t: M draw indices in
+ * HOST memory (passed by value).  d_rec (M, rec_stride) int32, rec_stride >= npp_dev_sampler_record_words(). */
+int npp_dev_sampler_decide(const npp_dev_image* d_imgs, int M, const uint32_t* h_t, int n_p, int topk, int32_t* d_rec,
+                           int64_t rec_stride, void* stream);
+int npp_dev_sampler_decide_host(const npp_dev_image* imgs, int M, const uint32_t* t, int n_p, int topk, int32_t* rec,
+                                int64_t rec_stride);
+/* The pixel-row launch: d_pix[m * pix_stride + j] = position j of image m's stream-2 permutation of [0, n_train), the int64
+ * indices npp_batch_assemble reads, in sample order.  n_pix <= n_train of every image. */
+int npp_dev_sampler_pixels(const npp_dev_image* d_imgs, int M, const uint32_t* h_t, int64_t n_pix, int64_t* d_pix,
+                           int64_t pix_stride, void* stream);
+int npp_dev_sampler_pixels_host(const npp_dev_image* imgs, int M, const uint32_t* t, int64_t n_pix, int64_t* pix,
+                                int64_t pix_stride);
+/* The generator and the permutation on their own (host): out[4] = Philox4x32-10(ctr, key); out[j] = position j, j < n. */
+int npp_dev_philox4x32_10(const uint32_t* ctr4, const uint32_t* key2, uint32_t* out4);
+int npp_dev_perm_host(uint64_t seed, uint32_t t, uint32_t stream, int64_t N, int64_t n, int64_t* out);
+
 /* ---- diagnostics ---------------------------------------------------------- */
 /* Checks the MFMA operand / accumulator lane maps this library relies on (incl. the
  * accumulator-as-next-operand chain) with exact integer data.  d_scratch >= 1 MiB. */

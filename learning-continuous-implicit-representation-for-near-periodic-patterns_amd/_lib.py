@@ -86,6 +86,13 @@ class Grid(C.Structure):
                 ("sy", C.c_float), ("sx", C.c_float)]
 
 
+class DevImage(C.Structure):
+    """npp_dev_image (include/npp_hip.h): the per-image constants of the rng_mode="device" launches."""
+    _fields_ = [("sat", C.c_void_p), ("pool_val", C.c_void_p), ("pool_train", C.c_void_p), ("n_pool_val", C.c_int64),
+                ("n_pool_train", C.c_int64), ("n_train", C.c_int64), ("shifts", C.c_double * 4), ("invalid_ratio", C.c_double),
+                ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32), ("P", C.c_int32), ("pad", C.c_int32)]
+
+
 _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 _cfgp = C.POINTER(EmbedCfg)
 _gridp = C.POINTER(Grid)
@@ -181,6 +188,13 @@ SYMBOLS = {
     "npp_sampler_destroy": (None, [_vp]),
     "npp_sampler_set_patch": (_i32, [_vp, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
     "npp_sampler_draw": (_i32, [_vp, _vp, _i32, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp]),
+    "npp_dev_sampler_record_words": (_i64, [_i32, _i32]),
+    "npp_dev_sampler_decide": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i64, _vp]),
+    "npp_dev_sampler_decide_host": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i64]),
+    "npp_dev_sampler_pixels": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _vp]),
+    "npp_dev_sampler_pixels_host": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64]),
+    "npp_dev_philox4x32_10": (_i32, [_vp, _vp, _vp]),
+    "npp_dev_perm_host": (_i32, [C.c_uint64, C.c_uint32, C.c_uint32, _i64, _i64, _vp]),
     "npp_linear_fwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),
     "npp_linear_bwd_data": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp]),
     "npp_linear_bwd_weight": (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _vp]),

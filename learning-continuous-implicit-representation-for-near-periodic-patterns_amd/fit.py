@@ -19,6 +19,18 @@ from .sampler import GridPatchSampler
 from .losses import ContextualLoss, LPIPS
 
 
+def _hand_over(v, stream):
+    """The tensors of a batch materialised on the sampler stream are read on `stream`: the allocator must not recycle them before."""
+    if isinstance(v, torch.Tensor):
+        v.record_stream(stream)
+    elif isinstance(v, dict):
+        for x in v.values():
+            _hand_over(x, stream)
+    elif isinstance(v, (list, tuple)):
+        for x in v:
+            _hand_over(x, stream)
+
+
 class CompletionFit:
     def __init__(self, img, mask, angles_deg, periods, freqs, params, device="cuda", N_rand=8192,
                  ksplit=None, seed=0, lrate=5e-4, lrate_decay=500, valid_mask=None, shifts=None,
@@ -51,9 +63,17 @@ class CompletionFit:
         (O(size)): same distribution, different stream.
         prefetch: > 0 runs the host half of the sampler (draw_batch) that many iterations ahead on a producer thread --
         it never reads network state, so the stream and the results are unchanged; with the native generator the draws
-        overlap the training loop instead of preceding it."""
-        if rng_mode not in ("reference", "numpy", "fast"):
-            raise ValueError("rng_mode must be 'reference', 'numpy' or 'fast'")
+        overlap the training loop instead of preceding it.
+        "device" draws on the GPU (dev_sampler.DeviceDraws; models/sampler.py:242-354 and train.py:172 as two launches on the
+        sampler stream): Philox4x32-10 keyed by `seed`, every draw a pure function of (seed, draw index) -- its own stream, the
+        same distribution; no host arithmetic per draw, so no producer thread (prefetch must be 0)."""
+        if rng_mode not in ("reference", "numpy", "fast", "device"):
+            raise ValueError("rng_mode must be 'reference', 'numpy', 'fast' or 'device'")
+        if rng_mode == "device" and int(prefetch) > 0:
+            raise ValueError("rng_mode='device' with prefetch > 0: the draws run on the GPU, there is no producer thread to run ahead "
+                             "(pass prefetch=0)")
+        if rng_mode == "device" and no_reg_sampling:
+            raise ValueError("rng_mode='device' with no_reg_sampling=True: the random-patch ablation is not built for the device draws")
         if task not in ("completion", "remapping", "segmentation"):
             raise ValueError("task must be 'completion', 'remapping' or 'segmentation'")
         # False: the folded launches as separate ones (npp_pixel_loss, npp_patch_compose_bwd: the comparator of
@@ -106,11 +126,13 @@ class CompletionFit:
         if task == "segmentation":
             self.net.lr_clock = False                              # NPP_segmentation/train.py:408 (see NPPNet.lr_clock)
         self.N_rand = int(min(N_rand, self.i_train.shape[0]))
+        self.rng_mode, self.seed = rng_mode, int(seed)
         if rng_mode == "reference":
             from .host_rng import NativeRandomState
             self.rng = NativeRandomState(seed)
         else:
-            self.rng = np.random.RandomState(seed)
+            self.rng = np.random.RandomState(self.seed & 0xFFFFFFFF if rng_mode == "device" else seed)   # (device: a 64-bit key, no host stream)
+        self._dev_draws = None                                    # rng_mode "device": the two launches (dev_sampler.DeviceDraws), on first use
         self.fast_rng = np.random.default_rng(seed) if rng_mode == "fast" else None
         self._prefetch, self._producer, self._queue, self._stop = int(prefetch), None, None, False
         self._ahead, self._s_smp, self.side_sampler = None, None, True   # device half of the sampler one iteration ahead (step_full)
@@ -235,6 +257,8 @@ class CompletionFit:
         sampler found no valid real patch: the iteration is skipped BEFORE zero_grad and
         global_step is not advanced (train.py:160-161)."""
         assert self.patch_sampler is not None, "construct CompletionFit with shifts=... for the patch losses"
+        if self.rng_mode == "device":
+            return self._step_full_device()
         if self._prefetch > 0:
             if self._producer is None:
                 self._start_producer()
@@ -273,6 +297,46 @@ class CompletionFit:
         self.step_from(batch)
         return True
 
+    def _step_full_device(self):
+        """step_full() of rng_mode "device": the draws are launches on the sampler stream.  Iteration i + 1 is materialised there
+        (record read, crop gather, pixel rows, row assembly) right behind the launches of iteration i, and the decision of
+        iteration i + 2 is enqueued behind that -- so the host's read of (source, k) waits on work enqueued a whole iteration
+        earlier and the main stream never waits for a draw that has not long run."""
+        cur = self._ahead if self._ahead is not None else self._materialise_device()
+        self._ahead = None
+        d, batch, ev = cur
+        self.last_draw = d
+        self.iteration += 1
+        try:
+            if batch is not None:
+                torch.cuda.current_stream(self.device).wait_event(ev)
+                self.step_from(batch)
+            else:
+                self.skipped += 1
+        finally:
+            self._ahead = self._materialise_device()              # (the draw index has advanced whatever happened to this iteration)
+        return batch is not None
+
+    def device_draws(self):
+        if self._dev_draws is None:
+            from .dev_sampler import DeviceDraws
+            self._dev_draws = DeviceDraws([self])
+        return self._dev_draws
+
+    def _materialise_device(self):
+        """The next draw + its batch on the sampler stream -> (d, batch | None, event), then the decision launch of the draw after
+        it (unless a patch-size decay comes first)."""
+        dd = self.device_draws()
+        main = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(dd.stream):
+            d = self.draw_batch()
+            b = self.materialise_batch(d)
+            ev = torch.cuda.Event()
+            ev.record(dd.stream)
+            dd.launch_ahead()
+        _hand_over(b, main)
+        return d, b, ev
+
     def _next_draw(self):
         d = self._queue.get()
         if isinstance(d, BaseException):
@@ -292,17 +356,7 @@ class CompletionFit:
             b = self.materialise_batch(d)
             ev = torch.cuda.Event()
             ev.record(self._s_smp)
-
-        def hand_over(v):
-            if isinstance(v, torch.Tensor):
-                v.record_stream(main)
-            elif isinstance(v, dict):
-                for x in v.values():
-                    hand_over(x)
-            elif isinstance(v, (list, tuple)):
-                for x in v:
-                    hand_over(x)
-        hand_over(b)
+        _hand_over(b, main)
         return d, b, ev
 
     def decay_due(self):
@@ -325,6 +379,20 @@ class CompletionFit:
         reference's RNG order.  One call per loop iteration, including the ones that end up skipped."""
         if self.decay_due():
             self.apply_decay()
+        if self.rng_mode == "device":
+            # the record of the decision launch (enqueued by the previous materialisation, or now) and, for a draw that is not
+            # skipped, the pixel-row launch -- both on the sampler stream; the caller's stream waits for them
+            dd = self.device_draws()
+            cur = torch.cuda.current_stream(self.device)
+            d = dd.take()[0]
+            d["n_p"] = self.patch_num
+            if d["k"] > 0:
+                with torch.cuda.stream(dd.stream):
+                    pix = torch.empty((1, self.N_rand), dtype=torch.int64, device=self.device)
+                    d["pix"] = dd.pixels([d], pix)[0]
+            if cur != dd.stream:
+                cur.wait_stream(dd.stream)
+            return d
         self._draw_iter += 1
         d = self.patch_sampler.draw(topk=self.topk, invalid_ratio=self.invalid_ratio)
         d["n_p"] = self.patch_num
@@ -340,12 +408,15 @@ class CompletionFit:
         if d["k"] == 0:
             return None
         # ONE host -> device transfer per iteration: [pixel-row indices (int64) | patch centres (int32)] through one pinned block
-        pix = np.ascontiguousarray(d["pix"], np.int64)
-        cen = self.patch_sampler.centres_i32(d)
-        blob = np.concatenate([pix.view(np.uint8).reshape(-1), cen.view(np.uint8).reshape(-1)])
-        blob_dev = ops.h2d(blob, self.device)
-        pix_dev = blob_dev[:pix.nbytes].view(torch.int64)
-        cen_dev = blob_dev[pix.nbytes:].view(torch.int32).reshape(-1, 2)
+        if d.get("device"):                                       # rng_mode "device": both are where the launches wrote them
+            pix_dev, cen_dev = d["pix"], d["cen_dev"]
+        else:
+            pix = np.ascontiguousarray(d["pix"], np.int64)
+            cen = self.patch_sampler.centres_i32(d)
+            blob = np.concatenate([pix.view(np.uint8).reshape(-1), cen.view(np.uint8).reshape(-1)])
+            blob_dev = ops.h2d(blob, self.device)
+            pix_dev = blob_dev[:pix.nbytes].view(torch.int64)
+            cen_dev = blob_dev[pix.nbytes:].view(torch.int32).reshape(-1, 2)
         _, _, _, _, _, source, k, weight = self.patch_sampler.materialise(d, want_coords=False, want_tuple=False, cen_dev=cen_dev,
                                                                           crops_out=None if out is None else (out["crops"], out["cmasks"]))
         # coordinates of all rows (N_rand pixel rows, then the fake patches' rows, zero padding) + the pixel rows' colours:
@@ -356,7 +427,10 @@ class CompletionFit:
         allc, gt, pm = ops.batch_assemble(self.i_train_dev, pix_dev, self.patch_sampler.last_cen_dev, P, bp,
                                           self.masked_img, self.pixel_mask,
                                           out=None if out is None else (out["coords"], out["gt"], out.get("pmask")))
-        w_dev = ops.h2d(np.ascontiguousarray(d["weights"], np.float32), self.device) if (self.use_patch_weight and d["weights"] is not None) else None
+        w_dev = None
+        if self.use_patch_weight and d["weights"] is not None:
+            # (device draws: the record's weights, copied out of the record ring on the sampler stream)
+            w_dev = d["w_dev"].clone() if d.get("device") else ops.h2d(np.ascontiguousarray(d["weights"], np.float32), self.device)
         return dict(coords=allc, n_pix=n_pix, n=n, bp=bp, gt=gt, source=source, k=k, P=P, n_p=d["n_p"],
                     raw=self.patch_sampler.last_raw, pmask=pm, weight=w_dev)
 
@@ -492,8 +566,14 @@ class CompletionFit:
         net = self.net
         sd = {"net": {k: getattr(net, k).detach().cpu().clone() for k in ("params", "m", "v", "latents", "lat_m", "lat_v")},
               "net_steps": (net.global_step, net.opt_step, net.lr), "iteration": self.iteration, "draw_iter": self._draw_iter,
+              "rng_mode": self.rng_mode,
               "skipped": getattr(self, "skipped", 0), "rng": self.rng.get_state(),
               "fast_rng": None if self.fast_rng is None else self.fast_rng.bit_generator.state}
+        if self.rng_mode == "device":
+            # t, the index of the next draw the LOOP takes: a draw materialised ahead (step_full) is not part of the state -- it is a
+            # pure function of (seed, t) and is drawn again.  (The patch-size decay it may have applied already is: decayed_at.)
+            sd["t"] = sd["draw_iter"] = self._draw_iter - (1 if self._ahead is not None else 0)
+            sd["decayed_at"] = getattr(self, "_decayed_at", None)
         if self.patch_sampler is not None:
             sd["patch"] = (self.patch_size, self.patch_num)
             lp = self.percepLoss
@@ -508,6 +588,8 @@ class CompletionFit:
     def load_state_dict(self, sd):
         if self._producer is not None:
             raise RuntimeError("load_state_dict() with an active producer thread")
+        if self.rng_mode == "device" and sd.get("rng_mode") != "device":
+            raise ValueError("load_state_dict: a rng_mode='device' fit continues a device-mode fit's sequence only")
         net = self.net
         for k, v in sd["net"].items():
             getattr(net, k).copy_(v.to(self.device))
@@ -515,6 +597,8 @@ class CompletionFit:
         net.repack()
         net._clean = False
         self.iteration, self._draw_iter, self.skipped = sd["iteration"], sd["draw_iter"], sd["skipped"]
+        if self.rng_mode == "device":
+            self._draw_iter, self._ahead, self._decayed_at = sd["t"], None, sd.get("decayed_at")
         self.rng.set_state(sd["rng"])
         if self.fast_rng is not None and sd["fast_rng"] is not None:
             self.fast_rng.bit_generator.state = sd["fast_rng"]

@@ -532,6 +532,47 @@ def batch_assemble(i_train, pix, cen, P, bp, img_hwc, pmask_hw=None, out=None):
     return coords, gt, pm
 
 
+def dev_sampler_record_words(n_p, topk):
+    return int(check(lib().npp_dev_sampler_record_words(int(n_p), int(topk)), "npp_dev_sampler_record_words"))
+
+
+def dev_philox4x32_10(ctr, key):
+    """Philox4x32-10 of one counter (4 words) under one key (2 words) -> 4 uint32: the generator of rng_mode="device", on the host."""
+    c, k, out = (np.ascontiguousarray(v, np.uint32) for v in (ctr, key, np.zeros(4)))
+    check(lib().npp_dev_philox4x32_10(c.ctypes.data_as(C.c_void_p), k.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)),
+          "npp_dev_philox4x32_10")
+    return out
+
+
+def dev_sampler_decide(imgs, M, ts, n_p, topk, rec):
+    """The decision launch of rng_mode="device" for M images (npp_dev_sampler_decide): imgs = the npp_dev_image array in device
+    memory (uint8), ts = the M draw indices (host, uint32), rec (M, stride) int32 = the records, written in place."""
+    _req(imgs, torch.uint8, "imgs")
+    _req(rec, torch.int32, "rec")
+    ts = np.ascontiguousarray(ts, np.uint32)
+    if ts.shape != (M,) or rec.dim() != 2 or rec.shape[0] != M:
+        raise ValueError("dev_sampler_decide: one draw index and one record per image")
+    check(lib().npp_dev_sampler_decide(_p(imgs), M, ts.ctypes.data_as(C.c_void_p), int(n_p), int(topk), _p(rec), rec.shape[1], _stream()),
+          "npp_dev_sampler_decide")
+    return rec
+
+
+def dev_sampler_pixels(imgs, M, ts, n_pix, pix, n_train_min):
+    """The pixel-row launch of rng_mode="device" (npp_dev_sampler_pixels): pix (M, >= n_pix) int64, written in place -- the
+    indices npp_batch_assemble reads.  n_train_min: the smallest population of the M images (n_pix beyond it is refused like
+    np.random.choice(replace=False) refuses it)."""
+    if n_pix > n_train_min:
+        raise ValueError("Cannot take a larger sample than population when 'replace=False'")
+    _req(imgs, torch.uint8, "imgs")
+    _req(pix, torch.int64, "pix")
+    ts = np.ascontiguousarray(ts, np.uint32)
+    if ts.shape != (M,) or pix.dim() != 2 or pix.shape[0] != M:
+        raise ValueError("dev_sampler_pixels: one draw index and one row of indices per image")
+    check(lib().npp_dev_sampler_pixels(_p(imgs), M, ts.ctypes.data_as(C.c_void_p), int(n_pix), _p(pix), pix.shape[1], _stream()),
+          "npp_dev_sampler_pixels")
+    return pix
+
+
 _cx_ws = {}
 
 

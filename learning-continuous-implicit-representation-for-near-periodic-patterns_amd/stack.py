@@ -37,6 +37,10 @@ class StackedFit:
         for f in fits:                  # (before any device work)
             if f.net.precision != "bf16":
                 raise ValueError(f"StackedFit: precision='bf16' fits only (got precision={f.net.precision!r}: the exact-fp32 training chain has no stacked launches)")
+        modes = {f.rng_mode for f in fits}
+        if "device" in modes and len(modes) > 1:
+            raise ValueError(f"StackedFit: rng_mode='device' for every image of a stack or for none (got {sorted(modes)}): the device draws "
+                             "are one launch for all images")
         f0 = fits[0]
         self.fits, self.M = list(fits), len(fits)
         self.device = f0.device
@@ -102,6 +106,18 @@ class StackedFit:
                 st["pmask"] = torch.ones((M, self.n_pix), dtype=f32, device=dev)
         self._wset, self._ahead = 0, None
         self._s_smp = torch.cuda.Stream(dev)
+        # rng_mode "device": ONE decision launch and ONE pixel-row launch per iteration for all M images on the sampler stream
+        # (dev_sampler.DeviceDraws), each image with its own seed and draw index -- it draws what its stand-alone fit draws
+        self._dev = None
+        if modes == {"device"}:
+            from .dev_sampler import DeviceDraws
+            for f in fits:
+                if f._ahead is not None:              # a stand-alone draw materialised ahead: a pure function of (seed, t), drawn again here
+                    f._draw_iter, f._ahead = f._draw_iter - 1, None
+            self._s_smp.wait_stream(torch.cuda.current_stream(dev))
+            self._dev = DeviceDraws(fits, stream=self._s_smp)
+            for st in self._sets:
+                st["pix"] = torch.zeros((M, self.n_pix), dtype=torch.int64, device=dev)
         nxy = 2 * self.n_p * self.kmax
         self.xy = torch.zeros((M, nxy, 3, self.P, self.P), dtype=f32, device=dev)
         self.dxb = torch.zeros((M, nxy, 3, self.P, self.P), dtype=f32, device=dev)
@@ -131,7 +147,8 @@ class StackedFit:
         import os
         from concurrent.futures import ThreadPoolExecutor
         workers = min(M, max(1, (os.cpu_count() or 2) - 1))
-        self._pool = ThreadPoolExecutor(workers, thread_name_prefix="npp-stack-draw") if (self.parallel_draws and workers > 1) else None
+        self._pool = ThreadPoolExecutor(workers, thread_name_prefix="npp-stack-draw") if (
+            self.parallel_draws and workers > 1 and self._dev is None) else None     # (device draws: nothing to run on the host)
         self.batch_lpips, self._lp_in = True, None        # (False: every 'same' image's LPIPS branch on its own -- the tests' comparator)
         self.iteration = 0
         self.last_sources = None
@@ -159,6 +176,8 @@ class StackedFit:
 
     def _host_draws(self):
         """The M host draws of one iteration, started now: -> futures (thread pool) or the finished draws."""
+        if self._dev is not None:
+            return self._dev                              # the decisions are in flight on the sampler stream (or launched by _draw)
         if self._pool is not None:
             return [self._pool.submit(f.draw_batch) for f in self.fits]
         return [f.draw_batch() for f in self.fits]
@@ -182,7 +201,18 @@ class StackedFit:
         # (0.4 ms each) took longer than the stacked iteration they feed (4.7 ms per iteration against 3.5 ms of device time)
         if draws is None:
             draws = self._host_draws()
-        draws = [d.result() if hasattr(d, "result") else d for d in draws]
+        if self._dev is not None:
+            # the records of the decision launch enqueued an iteration ago ((source, k) per image from pinned memory), then the
+            # pixel rows of all M images in one launch
+            draws = self._dev.take()
+            with torch.cuda.stream(self._s_smp):
+                self._dev.pixels(draws, st["pix"])
+            for i, (f, d) in enumerate(zip(self.fits, draws)):
+                d["n_p"] = f.patch_num
+                if d["k"] > 0:
+                    d["pix"] = st["pix"][i]
+        else:
+            draws = [d.result() if hasattr(d, "result") else d for d in draws]
         with torch.cuda.stream(self._s_smp):
             for i, (f, d) in enumerate(zip(self.fits, draws)):
                 f.last_draw = d
@@ -196,6 +226,8 @@ class StackedFit:
                 out.append(b)
             ev = torch.cuda.Event()
             ev.record(self._s_smp)
+            if self._dev is not None:
+                self._dev.launch_ahead()                  # the next iteration's decisions (not across a patch-size decay)
         st["filled"] = ev
         st["gen"] = out.gen = st.get("gen", 0) + 1
         return out

@@ -77,9 +77,11 @@ def parse(argv=None):
     ap.add_argument("--i_print", type=int, default=500)
     ap.add_argument("--invalid_as_unknown", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--rng_mode", default="reference", choices=["reference", "numpy", "fast"],
-                    help="reference: NumPy's stream from the native generator; numpy: NumPy itself; fast: O(size) draws, other stream")
-    ap.add_argument("--prefetch", type=int, default=8, help="iterations of sampler draws prepared ahead on a producer thread")
+    ap.add_argument("--rng_mode", default="reference", choices=["reference", "numpy", "fast", "device"],
+                    help="reference: NumPy's stream from the native generator; numpy: NumPy itself; fast: O(size) draws, other stream; "
+                         "device: the draws run as two GPU launches (Philox4x32-10 of seed and draw index; no producer thread)")
+    ap.add_argument("--prefetch", type=int, default=8, help="iterations of sampler draws prepared ahead on a producer thread "
+                                                            "(not with --rng_mode device, which has no host draws to prepare)")
     ap.add_argument("--vgg19", default=None, help="torchvision vgg19 state_dict (.pth) for the contextual loss trunk")
     ap.add_argument("--vgg16", default=None, help="torchvision vgg16 state_dict (.pth) for the LPIPS trunk")
     ap.add_argument("--lpips_lin", default=None, help="lpips weights/v0.1/vgg.pth (the five 1x1 lin layers)")
@@ -217,7 +219,7 @@ def _build(plan, stacked=False):
                             # VGG16FeatureExtractor; LPIPS is off there, NPP_remapping/train.py:253-261)
                             vgg16_state_dict=None if remap else load(args.vgg16),
                             vgg16_style_state_dict=load(args.vgg16) if remap else None,
-                            lpips_lin_weights=lin, rng_mode=args.rng_mode, prefetch=0 if stacked else args.prefetch,
+                            lpips_lin_weights=lin, rng_mode=args.rng_mode, prefetch=0 if (stacked or args.rng_mode == "device") else args.prefetch,
                             task=args.task, clear_mask=d["clear_mask"] if remap else None,
                             masked_img=None if remap else d.get("masked_img"),
                             contextual_weight=args.contextual_weight if args.contextual_weight is not None else (0.01 if remap else (0.005 if seg else 1e-3)),
@@ -312,7 +314,7 @@ def stack_key(job):
     if f.patch_sampler is None or f.use_patch_weight or not f.use_contextual_loss or f.net.out_act != 1 or f.net.precision != "bf16":
         return None
     return (a.task, f.style is not None, f.style_w, f.pixel_mask is not None, f.net.K, f.net.width, f.N_rand, f.patch_size, f.patch_num, f.topk, f.net.quad, f.pix_w, f.use_comp, f.cx_w, f.lp_w,
-            f.lp_robust, f.use_perceptual_loss, a.N_iters, a.i_testset, a.i_print, a.patch_size_decay, str(f.device))
+            f.lp_robust, f.use_perceptual_loss, f.rng_mode, a.N_iters, a.i_testset, a.i_print, a.patch_size_decay, str(f.device))
 
 
 def plan_key(plan):
