@@ -551,6 +551,46 @@ int npp_trunk_grad_in_pf(const float* d_df_nchw, const void* d_y, int N_total, i
 int npp_trunk_export(const void* d_act, int N_total, int n_run, int C, int H, int W,
                      float* d_out_nchw, int is_f16, void* stream);
 
+/* ---- the same trunks in exact fp32 (trunk_precision = "fp32"; csrc/npp_conv32.hip) ------------------------------
+ * The diagnostic twin of the launches above: the stacks of externel_lib/contextual_loss/modules/vgg.py:30-36,
+ * externel_lib/lpips/pretrained_networks.py:119-134 and models/style_loss.py:11-14 in the arithmetic torch runs them in on
+ * the reference's side -- fp32 operands, one rounding per product, fp32 accumulation (v_mfma_f32_32x32x2_f32: a k-ordered
+ * fmaf chain).  All tensors are plain fp32 NCHW: a layer's stored output IS the feature tap the loss heads read
+ * (npp_cx_fwd_bwd, npp_lpips_layers, npp_gram_fwd), its ReLU gate and the pool's arg-max source.  Implicit GEMM: no column
+ * matrix is formed (npp_im2col + npp_linear_fwd would need 9 x the activation per layer and direction).  No float atomics and
+ * a fixed summation order (channel chunks of 8, then tap, then channel): two runs give equal bits, and an image's result does
+ * not depend on the other images of its batch.  N_total / n_run as in npp_conv3x3: only the leading n_run images are computed.
+ * Channel counts: 3 (image layer only), 64, 128, 256, 512; any H, W >= 1.  No weight gradients (vgg.py:26-28). */
+
+/* torch Conv2d weight (Cout, Cin, 3, 3) fp32 -> fp32 MFMA A-operand packs, zero padded to 32 output x 8 input channels:
+ * which = 0 forward pack, 1 data-gradient pack (transposed, taps flipped).  Either output of npp_conv32_pack may be NULL. */
+int64_t npp_conv32_pack_bytes(int Cin, int Cout, int which);
+int npp_conv32_pack(const float* d_w, int Cin, int Cout, float* d_pack_fwd, float* d_pack_bwd, void* stream);
+
+/* One 3x3 / pad 1 / stride 1 convolution launch, d_x (N_total, Cin, H, W) -> d_y (N_total, Cout, H, W):
+ *  mode 0  y = relu(conv(x', w) + bias)          nn.Conv2d + nn.ReLU (vgg.py:30-36, pretrained_networks.py:119-134); with
+ *                                                in_scale / in_shift (Cin = 3): x' = x * in_scale[c] + in_shift[c] applied on
+ *                                                load, BEFORE the zero padding -- contextual.py:56-61, lpips.py:96-98,136-143
+ *                                                (not folded into w and bias: torch pads the normalised image with zeros)
+ *  mode 1  y = (conv_transpose(x') + add) * [gate > 0]   the autograd node of the same layer: x = dL/d(pre-activation) of this
+ *                                                layer (Cin = its output channels), d_pack its data-gradient pack, d_gate the
+ *                                                stored output of the layer below (NULL: none -- into a pooled tensor), d_add
+ *                                                (nullable) a tap gradient on that tensor; both (N_total, Cout, H, W)
+ *  mode 2  y = conv_transpose(x') * out_scale[c]  dL/dimage of the image layer (Cout = 3)
+ * d_in_gate (modes 1 / 2, nullable): x' = x * [in_gate > 0] on load -- x is then dL/d(OUTPUT) of this layer and d_in_gate its
+ * stored output (the tapped top layer's own ReLU). */
+int npp_conv32(const float* d_x, int N_total, int n_run, int H, int W, int Cin, int Cout, const float* d_pack, int mode,
+               const float* d_bias, const float in_scale[3], const float in_shift[3], const float* d_in_gate,
+               const float* d_gate, const float* d_add, const float out_scale[3], float* d_y, void* stream);
+
+/* nn.MaxPool2d(2, 2) on fp32 NCHW, (N_total, C, H, W) -> (N_total, C, H/2, W/2) (odd sizes floor like torch), and its backward
+ * dz = (route(dy) + add) * [x > 0 if gate]: the gradient goes to the first maximum of each window in row-major order (as
+ * npp_maxpool2_bwd); d_add (nullable) is a tap gradient on x; gate != 0 applies the ReLU gate of the pooled layer.  One thread
+ * per element of x: no atomics.  models/style_loss.py:11-14 taps the pooled tensors themselves. */
+int npp_maxpool2_fwd32(const float* d_x, int N_total, int n_run, int H, int W, int C, float* d_y, void* stream);
+int npp_maxpool2_bwd32(const float* d_dy, const float* d_x, const float* d_add, int N_total, int n_run, int H, int W, int C,
+                       int gate, float* d_dz, void* stream);
+
 /* ---- stacked launches: M independent images of one shape in every launch (round 4) ---------------------------
  * The reference fits its images one after the other (run_completion.sh:8-14: one `python train.py` per directory);
  * the fits are independent -- own weights, own Adam state, own random stream -- so M of them can ride

@@ -272,6 +272,12 @@ SYMBOLS = {
     "npp_robust_elem_workspace_bytes": (_i64, [_i32]),
     "npp_robust_elem": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _f32, C.POINTER(C.c_float), _vp, _vp, _vp, _vp, _vp, _vp]),
     "npp_trunk_export": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "npp_conv32_pack_bytes": (_i64, [_i32, _i32, _i32]),
+    "npp_conv32_pack": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "npp_conv32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp,
+                          _vp, _vp, C.POINTER(C.c_float), _vp, _vp]),
+    "npp_maxpool2_fwd32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "npp_maxpool2_bwd32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "npp_im2col": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "npp_maxpool_nhwc": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "npp_lpips_spatial_layer": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),

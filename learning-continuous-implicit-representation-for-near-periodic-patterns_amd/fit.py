@@ -40,11 +40,14 @@ class CompletionFit:
                  prefetch=0, use_perceptual_loss=True, task="completion", clear_mask=None, style_weight=None,
                  vgg16_style_state_dict=None, masked_img=None, width=256, no_reg_sampling=False, use_patch_weight=False,
                  no_pix_loss=False, use_contextual_loss=True, loss_type="robust_loss_adaptive", use_adaptive_perceptual_loss=True, normalize_type=1,
-                 precision="bf16"):
+                 precision="bf16", trunk_precision="fp16"):
         """img (H,W,3) float in [0,1]; mask (H,W,1) 1 = known (loaders.py:92-101).
         precision: the arithmetic of the coordinate MLP's training launches, 'bf16' (default) or 'fp32' (NPPNet(precision=...): the
         exact fp32 chain, the reference's own arithmetic; the iteration then takes the unfolded launch sequence -- fold_launches =
-        False -- and the evaluation renders in fp32).  It is the MLP's precision only: the VGG trunks of the patch losses stay fp16.
+        False -- and the evaluation renders in fp32).  It is the MLP's precision only.
+        trunk_precision: the arithmetic of the VGG trunks of the patch losses, 'fp16' (default: losses.HipTrunk) or 'fp32'
+        (losses.HipTrunk32, exact fp32 convolutions; independent of `precision`).  A diagnostic mode: the iteration forms the fp32
+        batch with npp_patch_compose_fwd, runs the pixel loss as its own launch and the LPIPS branch launch by launch (lp_graph = False).
         normalize_type: --normalize_type (arg_config.py:31): 1 = sigmoid output, 2 = tanh output (helpers.py:55-58).  The reference
         rescales ONLY its evaluation image to [-1, 1] under 2 (loaders.py:56,111); the loop still trains on masked_img in [0, 1]
         (train.py:173) -- reproduced as it is: pass `img` already rescaled if the evaluation should see it that way.
@@ -74,6 +77,9 @@ class CompletionFit:
                              "(pass prefetch=0)")
         if rng_mode == "device" and no_reg_sampling:
             raise ValueError("rng_mode='device' with no_reg_sampling=True: the random-patch ablation is not built for the device draws")
+        if trunk_precision not in ("fp16", "fp32"):
+            raise ValueError("trunk_precision must be 'fp16' or 'fp32'")
+        self.trunk_precision = trunk_precision
         if task not in ("completion", "remapping", "segmentation"):
             raise ValueError("task must be 'completion', 'remapping' or 'segmentation'")
         # False: the folded launches as separate ones (npp_pixel_loss, npp_patch_compose_bwd: the comparator of
@@ -155,18 +161,19 @@ class CompletionFit:
                 img=self.masked_img[None], mask=self.mask[None], N_samples=self.patch_num, patch_size=self.patch_size,
                 height=self.H, width=self.W, pool_train=self.i_train, pool_val=self.i_val, selected_shifts=shifts,
                 no_reg_sampling=bool(no_reg_sampling), rng=self.rng, fast_rng=self.fast_rng)
-            self.contextualLoss = ContextualLoss(use_vgg=True, vgg_state_dict=vgg19_state_dict, device=self.device).to(self.device)
+            self.contextualLoss = ContextualLoss(use_vgg=True, vgg_state_dict=vgg19_state_dict, device=self.device,
+                                                 trunk_precision=trunk_precision).to(self.device)
             self.percepLoss = LPIPS(net="vgg", lin_weights=lpips_lin_weights, vgg_state_dict=vgg16_state_dict,
-                                    device=self.device)
+                                    device=self.device, trunk_precision=trunk_precision)
             self.style, self.style_w = None, 0.0
             if style_weight is not None or task == "remapping":
                 from .losses import StyleLoss
-                self.style = StyleLoss(vgg_state_dict=vgg16_style_state_dict, device=self.device)
+                self.style = StyleLoss(vgg_state_dict=vgg16_style_state_dict, device=self.device, trunk_precision=trunk_precision)
                 self.style_w = 1.0 if style_weight is None else float(style_weight)        # arg_config.py: style_weight 1
             self.last_source, self.skipped = None, 0
             self._xy, self._xy_key, self._xy_bufs = None, None, {}
             # the LPIPS branch of a 'same' iteration as ONE captured HIP graph (lpips_branch); lp_graph = False keeps the launches
-            self._lp_graphs, self.lp_graph = {}, True
+            self._lp_graphs, self.lp_graph = {}, trunk_precision == "fp16"
             self._s_lp = torch.cuda.Stream(self.device)
             self.patch_loss_buf = torch.zeros(1, dtype=torch.float32, device=self.device)
 
@@ -181,7 +188,7 @@ class CompletionFit:
         # -- incl. the stream (the heads' accumulators are per stream) and the trunk's choice of kernel forms
         key = (xy.data_ptr(), loss_buf.data_ptr(), int(nk), float(scale), self.lp_robust, lp._lat.data_ptr(), lp._dlat.data_ptr(),
                lp.lins[0].data_ptr(), lp.grouped_heads, lp.flat_tap_grads, int(lp.hip_trunk.fuse_pairs), lp.hip_trunk.fold_pool_bwd,
-               lp.hip_trunk.fold_pool_fwd, ops._stream().value)
+               lp.hip_trunk.fold_pool_fwd, ops._stream().value) if self.lp_graph else None
         ent = self._lp_graphs.get(key) if self.lp_graph else None
         if ent is not None and ent[0] is not None:
             ent[0].replay()
@@ -492,7 +499,11 @@ class CompletionFit:
         xy = self._xy if (with_lp or self.style is not None) else None      # fp32 batch only when another trunk reads it
         sc, sh = cx.input_norm()
         main = torch.cuda.current_stream(self.device)
-        fold = self.fold_launches
+        t32 = self.trunk_precision == "fp32"
+        fold = self.fold_launches and not t32                    # (the bf16 MLP keeps its patch-folded backward launch: fold_bwd below)
+        fold_bwd = self.fold_launches
+        if t32:
+            xy = self._xy                                         # the fp32 batch is what the fp32 trunks read
         net.zero_grad()
         if self.percepLoss.touched:
             self.percepLoss.zero_latent_grads()
@@ -514,7 +525,10 @@ class CompletionFit:
         # Iterations whose other consumers need no fp32 copy of the batch ('val' / 'train' without a style term): the patch plumbing
         # and the pixel loss ride inside the trunk's first launch (ops.conv_pair_fwd_patch) -- no npp_trunk_patch_in launch at all
         x0_src = None
-        if fold and xy is None and self.use_contextual_loss and cx.hip_trunk.can_compose_input(P, P):
+        if t32:                                                   # npp_patch_compose_fwd -> the fp32 batch; no flat trunk input
+            ops.patch_compose_fwd(pred[n_pix:n], raw["fake"], raw["fmask"], raw["real"], raw["rmask"], n_p, k, P, comp, xy)
+            self.patch_loss_buf.zero_()
+        elif fold and xy is None and self.use_contextual_loss and cx.hip_trunk.can_compose_input(P, P):
             x0_src = dict(patch=(pred[n_pix:n], raw["fake"], raw["fmask"], raw["real"], raw["rmask"], n_p, k, P, comp),
                           zero=self.patch_loss_buf, loss=net.pixel_loss_args(bp, n_pix, b["gt"], mask=b.get("pmask"), weight=self.pix_w))
         else:
@@ -531,7 +545,9 @@ class CompletionFit:
                 dx_b = self.lpips_branch(xy, nk, self.lp_w * (nk if weight is not None else 1), self.patch_loss_buf)
         # the backward chain that follows streams this pack: requested into L2 early (bf16 chain only)
         cx.hip_trunk.final_next_pack = net.wb if net.precision == "bf16" else None
-        if self.use_contextual_loss:
+        if self.use_contextual_loss and t32:
+            dx_a = cx.fused(xy, nk, self.cx_w, self.patch_loss_buf, weight=weight)
+        elif self.use_contextual_loss:
             dx_a = cx.fused((2 * nk, 3, P, P), nk, self.cx_w, self.patch_loss_buf, weight=weight, x0_ready=True, x0_src=x0_src)   # train.py:238-239
         else:                                                                                       # ablation: no contextual term
             dx_a = torch.zeros((2 * nk, 3, P, P), dtype=torch.float32, device=self.device)
@@ -544,7 +560,7 @@ class CompletionFit:
         self.last_patch_loss = self.patch_loss_buf
         lr_used = net.lr
         # npp_patch_compose_bwd folded into the backward launch: dL/dpred of the patch rows is formed (and written) there
-        if fold:
+        if fold_bwd:
             net.backward(bp, patch=(dx_a, dx_b, raw["fmask"], raw["rmask"], n_pix, n_p, k, P, comp))
             net.optimizer_step(bp)
         else:

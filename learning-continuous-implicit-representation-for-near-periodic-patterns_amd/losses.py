@@ -93,6 +93,35 @@ class _Trunk(nn.Module):
             p.requires_grad = False     # vgg.py:26-28, pretrained_networks.py:116-118
 
 
+def _shared_layers(owner, cfg, taps, state_dict, seed, device, pack):
+    """The layer list of one (layer list, weights, device) with its device weights and MFMA packs, built once per process and trunk
+    class (owner._packs; pack(weight, is_image_layer) -> (forward pack, data-gradient pack)) -> (layers, state_dict)."""
+    key = (tuple(cfg), ("weights", id(state_dict)) if state_dict is not None else ("seed", int(seed)), str(device))
+    with owner._packs_lock:
+        hit = owner._packs.get(key)
+        if hit is not None and hit[1] is not state_dict:
+            hit = None
+        if hit is None:
+            ref = _Trunk(cfg, taps, state_dict, seed)          # same layer construction / init as the comparator
+            layers = []                                        # ("conv", feat_idx_of_relu, cin, cout, w, b, pf, pb) | ("pool",)
+            for i, m in enumerate(ref.features):
+                if isinstance(m, nn.Conv2d):
+                    w = m.weight.detach().to(device, torch.float32).contiguous()
+                    b = m.bias.detach().to(device, torch.float32).contiguous()
+                    pf, pb = pack(w, len(layers) == 0)
+                    layers.append(dict(kind="conv", relu_idx=i + 1, cin=w.shape[1], cout=w.shape[0], w=w, b=b, pf=pf, pb=pb))
+                elif isinstance(m, nn.MaxPool2d):
+                    layers.append(dict(kind="pool", idx=i))
+            # The uploads and pack launches above ran on THIS thread's current stream; other threads (run.search_all:
+            # one stream per host thread) take the entry from the cache and launch on theirs with no event between the two.
+            # Publish only what has completed (once per weight set and process).
+            torch.cuda.current_stream(device).synchronize()
+            if len(owner._packs) >= 12:
+                owner._packs.pop(next(iter(owner._packs)))          # evict the oldest entry only (instances keep their own references)
+            hit = owner._packs[key] = (layers, state_dict)
+    return hit
+
+
 class _HipTrunkFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, trunk, n_grad, scale, shift):
@@ -125,29 +154,7 @@ class HipTrunk:
     def __init__(self, cfg, taps, state_dict=None, seed=1234, device="cuda"):
         self.device = torch.device(device)
         self.taps = tuple(taps)
-        key = (tuple(cfg), ("weights", id(state_dict)) if state_dict is not None else ("seed", int(seed)), str(self.device))
-        with HipTrunk._packs_lock:
-            hit = HipTrunk._packs.get(key)
-            if hit is not None and hit[1] is not state_dict:
-                hit = None
-            if hit is None:
-                ref = _Trunk(cfg, taps, state_dict, seed)          # same layer construction / init as the comparator
-                layers = []                                        # ("conv", feat_idx_of_relu, cin, cout, w, b, pf, pb) | ("pool",)
-                for i, m in enumerate(ref.features):
-                    if isinstance(m, nn.Conv2d):
-                        w = m.weight.detach().to(self.device, torch.float32).contiguous()
-                        b = m.bias.detach().to(self.device, torch.float32).contiguous()
-                        pf, pb = ops.conv_pack(w, in_natural=(len(layers) == 0))
-                        layers.append(dict(kind="conv", relu_idx=i + 1, cin=w.shape[1], cout=w.shape[0], w=w, b=b, pf=pf, pb=pb))
-                    elif isinstance(m, nn.MaxPool2d):
-                        layers.append(dict(kind="pool", idx=i))
-                # The uploads and npp_conv_pack launches above ran on THIS thread's current stream; other threads (run.search_all:
-                # one stream per host thread) take the entry from the cache and launch on theirs with no event between the two.
-                # Publish only what has completed (once per weight set and process).
-                torch.cuda.current_stream(self.device).synchronize()
-                if len(HipTrunk._packs) >= 12:
-                    HipTrunk._packs.pop(next(iter(HipTrunk._packs)))          # evict the oldest entry only (instances keep their own references)
-                hit = HipTrunk._packs[key] = (layers, state_dict)
+        hit = _shared_layers(HipTrunk, cfg, taps, state_dict, seed, self.device, lambda w, first: ops.conv_pack(w, in_natural=first))
         self.layers = [dict(L) for L in hit[0]]                    # (own dicts: the per-instance tap flags below; the tensors are shared)
         for j, L in enumerate(self.layers):                         # gradient taps are supported on the top layer and before pools
             if L["kind"] == "conv" and L["relu_idx"] in self.taps:
@@ -372,6 +379,100 @@ class HipTrunk:
                 cur, j, state = g, j - 1, "gp"
 
 
+class HipTrunk32:
+    """HipTrunk in exact fp32 (trunk_precision="fp32"): the same stacks on csrc/npp_conv32.hip -- fp32 operands, fp32 MFMA, plain
+    fp32 NCHW tensors.  A layer's stored output is at once the feature tap, the ReLU gate and the pool's arg-max source, so the
+    taps _forward returns are those tensors themselves (freshly allocated per call; the others live in per-shape buffers).
+    Same constructor and calling convention as HipTrunk; gradient taps may sit on any tapped layer."""
+
+    _packs, _packs_lock = {}, __import__("threading").Lock()
+
+    def __init__(self, cfg, taps, state_dict=None, seed=1234, device="cuda"):
+        self.device = torch.device(device)
+        self.taps = tuple(taps)
+        self.layers = _shared_layers(HipTrunk32, cfg, taps, state_dict, seed, self.device, lambda w, first: ops.conv32_pack(w))[0]
+        self._buf, self._gen, self._n_keep, self._acts = {}, 0, None, []
+        self.final_next_pack = None        # (HipTrunk's L2 prefetch hint: accepted, unused)
+
+    def _flat(self, tag, shape):
+        key = (tag,) + tuple(shape)
+        t = self._buf.get(key)
+        if t is None:
+            t = self._buf[key] = torch.empty(tuple(shape), dtype=torch.float32, device=self.device)
+        return t
+
+    def __call__(self, x, n_grad=0, scale=(1.0, 1.0, 1.0), shift=(0.0, 0.0, 0.0)):
+        need = n_grad > 0 and x.requires_grad
+        return list(_HipTrunkFunction.apply(x, self, n_grad if need else 0, tuple(scale), tuple(shift)))
+
+    def _tapped(self, L):
+        return (L["relu_idx"] if L["kind"] == "conv" else L["idx"]) in self.taps
+
+    def _forward(self, x, scale, shift, n_run=None, n_keep=None):
+        """x (N,3,H,W) fp32 -> the fp32 taps (N,C,h,w); only the leading n_run images are computed (rows >= n_run undefined).
+        n_keep: the leading images a _backward() may follow for (None: all)."""
+        N, _, H, W = x.shape
+        nr = N if n_run is None else int(n_run)
+        self._n_keep = nr if n_keep is None else min(int(n_keep), nr)
+        self._gen += 1
+        self._acts, outs, cur, c = [], [], x, 3
+        for j, L in enumerate(self.layers):
+            if L["kind"] == "conv":
+                c = L["cout"]
+            else:
+                H, W = H // 2, W // 2
+            y = torch.empty((N, c, H, W), dtype=torch.float32, device=self.device) if self._tapped(L) else self._flat(("a", j), (N, c, H, W))
+            if L["kind"] == "conv":                                   # the input normalisation rides on the image layer's loads
+                ops.conv32(cur, nr, c, L["pf"], 0, y, bias=L["b"], in_norm=(scale, shift) if j == 0 else None)
+            else:
+                ops.maxpool2_fwd32(cur, nr, y)
+            if self._tapped(L):
+                outs.append(y)
+            self._acts.append(y)
+            cur = y
+        return outs
+
+    def _backward(self, gtaps, n, scale, xshape, zero_rest=True):
+        """dL/dx for the first n images from the fp32 tap gradients (n, C, h, w).  zero_rest=False leaves images >= n of the
+        returned tensor uninitialised (callers that only read [:n])."""
+        dimg = (torch.zeros if zero_rest else torch.empty)(xshape, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return dimg
+        if self._n_keep is not None and n > self._n_keep:
+            raise RuntimeError(f"HipTrunk32: backward for {n} images after a forward that kept the layer outputs of {self._n_keep}")
+        tapped = [j for j, L in enumerate(self.layers) if self._tapped(L)]
+        tap_of = {j: g for j, g in zip(tapped, gtaps) if g is not None}
+        if not tap_of:
+            return dimg
+        flip = [0]
+
+        def gbuf(like):
+            flip[0] ^= 1
+            return self._flat(("g", flip[0]), like.shape)
+
+        # Reverse walk.  g = dL/d(output of layer j); `gated`: g is already dL/d(pre-activation) (the ReLU gate of layer j applied by
+        # the launch that produced it).  Layers above the highest tapped one receive no gradient.
+        j = max(tap_of)
+        g, gated = tap_of[j], False
+        while True:
+            L = self.layers[j]
+            if L["kind"] == "pool":                                   # route into the conv layer below, add its tap, gate
+                if j == 0 or self.layers[j - 1]["kind"] != "conv":
+                    raise NotImplementedError("HipTrunk32: a pool that does not follow a convolution layer")
+                dz = gbuf(self._acts[j - 1])
+                ops.maxpool2_bwd32(g, self._acts[j - 1], n, dz, add=tap_of.get(j - 1), gate=True)
+                g, j, gated = dz, j - 1, True
+                continue
+            own = None if gated else self._acts[j]                   # the tapped top layer's own ReLU gate, on load
+            if j == 0:                                                # dL/dimage, times the input scale
+                ops.conv32(g, n, 3, L["pb"], 2, dimg, in_gate=own, out_scale=scale)
+                return dimg
+            below_conv = self.layers[j - 1]["kind"] == "conv"
+            out = gbuf(self._acts[j - 1])
+            ops.conv32(g, n, L["cin"], L["pb"], 1, out, in_gate=own, gate=self._acts[j - 1] if below_conv else None, add=tap_of.get(j - 1))
+            g, j, gated = out, j - 1, below_conv
+
+
 class _CXFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, fx, fy, band_width, weight):
@@ -392,19 +493,29 @@ def contextual_loss(x, y, band_width=0.5, weight=None, loss_type="cosine"):
     return _CXFunction.apply(x, y, float(band_width), weight)
 
 
+def _trunk_class(trunk_precision):
+    """trunk_precision of the loss classes: "fp16" (default) = HipTrunk, "fp32" = HipTrunk32 (the exact-fp32 diagnostic mode)."""
+    if trunk_precision not in ("fp16", "fp32"):
+        raise ValueError(f"trunk_precision must be 'fp16' or 'fp32', got {trunk_precision!r}")
+    return HipTrunk if trunk_precision == "fp16" else HipTrunk32
+
+
 _CX_FLAT = True     # False: the separate cx_dx_finish + npp_trunk_grad_in launches (comparator of tests/test_gpu_parity.py)
 
 
 class ContextualLoss(nn.Module):
     _MEAN, _STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)        # contextual.py:41-46
 
-    def __init__(self, band_width=0.5, loss_type="cosine", use_vgg=False, vgg_layer="relu3_4", vgg_state_dict=None, device="cuda"):
+    def __init__(self, band_width=0.5, loss_type="cosine", use_vgg=False, vgg_layer="relu3_4", vgg_state_dict=None, device="cuda",
+                 trunk_precision="fp16"):
         super().__init__()
+        trunk = _trunk_class(trunk_precision)
+        self.trunk_precision = trunk_precision
         assert band_width > 0, "band_width parameter must be positive."
         assert loss_type == "cosine" and vgg_layer == "relu3_4"
         self.band_width = band_width
         if use_vgg:
-            self.hip_trunk = HipTrunk(_VGG19, taps=(17,), state_dict=vgg_state_dict, device=device)
+            self.hip_trunk = trunk(_VGG19, taps=(17,), state_dict=vgg_state_dict, device=device)
 
     def forward(self, x, y, weight=None):
         if hasattr(self, "hip_trunk"):
@@ -425,6 +536,12 @@ class ContextualLoss(nn.Module):
         SHAPE of the batch, whose normalised flat form was already written into hip_trunk.input_buffer()."""
         t = self.hip_trunk
         sc, sh = self.input_norm()
+        if self.trunk_precision == "fp32":                  # fp32 taps and tap gradients: the core's fp32-tensor form
+            if x0_ready or x0_src is not None:
+                raise ValueError("ContextualLoss.fused: the fp32 trunk takes the fp32 batch itself (no flat input, no composed patches)")
+            f = t._forward(xy, sc, sh, n_keep=n)[0]
+            _, dfx = ops.cx_fwd_bwd(f[:n], f[n:], self.band_width, weight, scale, loss_buf, True)
+            return t._backward([dfx], n, sc, tuple(xy.shape), zero_rest=False)
         f = t._forward(xy, sc, sh, x0_ready, n_keep=n, x0_src=x0_src)[0]
         shape = tuple(xy) if x0_ready else tuple(xy.shape)
         if weight is None and _CX_FLAT:
@@ -477,11 +594,12 @@ class LPIPS(nn.Module):
 
     _SHIFT, _SCALE = (-.030, -.088, -.188), (.458, .448, .450)          # lpips.py:136-143 ScalingLayer
 
-    def __init__(self, net="vgg", lin_weights=None, vgg_state_dict=None, device="cuda"):
+    def __init__(self, net="vgg", lin_weights=None, vgg_state_dict=None, device="cuda", trunk_precision="fp16"):
         super().__init__()
         assert net in ("vgg", "vgg16")
         dev = torch.device(device)
-        self.hip_trunk = HipTrunk(_VGG16, taps=(3, 8, 15, 22, 29), state_dict=vgg_state_dict, seed=4321, device=dev)
+        self.trunk_precision = trunk_precision
+        self.hip_trunk = _trunk_class(trunk_precision)(_VGG16, taps=(3, 8, 15, 22, 29), state_dict=vgg_state_dict, seed=4321, device=dev)
         self.register_buffer("shift", torch.tensor(self._SHIFT)[None, :, None, None])
         self.register_buffer("scale", torch.tensor(self._SCALE)[None, :, None, None])
         if lin_weights is None:          # weights/v0.1/vgg.pth is not redistributed here: fixed-seed non-negative stand-ins
@@ -530,7 +648,11 @@ class LPIPS(nn.Module):
         # (Measured and dropped, round 4: the five heads -- 15-25 us each, 100 us in a row behind the trunk -- on a helper stream beside
         # the deeper layers of the forward pass: the 'same' iteration went 0.791 -> 0.811 ms; the branch is not what the device waits for.)
         feats = t._forward(xy, sc, sh, n_keep=n)
-        if self.grouped_heads:                                  # the five heads in ONE launch (they are independent: 100 us in a row before)
+        if self.trunk_precision == "fp32":                      # fp32 tap gradients (the flat forms are fp16 / bf16 layouts)
+            dfs = [torch.empty((n,) + tuple(f.shape[1:]), dtype=torch.float32, device=f.device) for f in feats]
+            ops.lpips_layers([f[:n] for f in feats], [f[n:] for f in feats], self.lins, self.latents if use_robust else None, self.spline,
+                             self.n_knots, self.x_scale, scale, loss_buf, dfs, self.dlatents, dflats=None)
+        elif self.grouped_heads:                                  # the five heads in ONE launch (they are independent: 100 us in a row before)
             N = xy.shape[0]
             # the taps right before a pool hand their gradient over as the flat bf16 tensor the backward pass adds in (no fp32
             # tensor, no npp_trunk_grad_in launch each); the top tap's goes through the ReLU gate of its own layer as before
@@ -554,7 +676,7 @@ class LPIPS(nn.Module):
         (N fixes the buffers' geometry); groups = [(o, n, lp, loss_buf)]: samples [o, o + n) of both halves belong to the LPIPS object
         lp -- its latents, its latent gradients, its own batch mean (scale / n) accumulated into loss_buf[0].  The heads run one launch
         per group, each writing its samples' rows of the shared flat tap-gradient tensors.  Returns dL/dxy ([:XL] defined)."""
-        if not (self.grouped_heads and self.flat_tap_grads and self.flat_top_tap):
+        if not (self.grouped_heads and self.flat_tap_grads and self.flat_top_tap) or self.trunk_precision != "fp16":
             raise RuntimeError("LPIPS.fused_groups: the grouped heads with flat tap gradients only")
         a = 2.0 if normalize else 1.0
         sc = [a / s for s in self._SCALE]
@@ -620,9 +742,10 @@ class StyleLoss:
     Trunk: HipTrunk (weights unpinned like the other trunks); everything after it: npp_gram_* / npp_robust_elem."""
     chns = [64, 128, 256]
 
-    def __init__(self, vgg_state_dict=None, device="cuda", seed=777):
+    def __init__(self, vgg_state_dict=None, device="cuda", seed=777, trunk_precision="fp16"):
         self.device = torch.device(device)
-        self.hip_trunk = HipTrunk(_VGG16_STYLE, taps=(4, 9, 16), state_dict=vgg_state_dict, seed=seed, device=self.device)
+        self.trunk_precision = trunk_precision
+        self.hip_trunk = _trunk_class(trunk_precision)(_VGG16_STYLE, taps=(4, 9, 16), state_dict=vgg_state_dict, seed=seed, device=self.device)
         # AdaptiveLossFunction(num_dims = chn ** 2) per level (style_loss.py:23-27): [latent_alpha(D) | latent_scale(D)]
         (self._lat, self._dlat, self._lat_m, self._lat_v), (self.latents, self.dlatents, self.lat_m, self.lat_v) = _latent_blobs(
             [torch.cat([torch.full((c * c,), 2.3841858e-07), torch.zeros(c * c)]) for c in self.chns], self.device)

@@ -833,6 +833,69 @@ def trunk_export(act, N_total, n_run, c, H, W, is_f16=False):
     return out
 
 
+# ---- the trunks in exact fp32 (csrc/npp_conv32.hip): plain fp32 NCHW tensors --------------------------------
+def conv32_pack(weight):
+    """torch Conv2d weight (Cout,Cin,3,3) fp32 -> (forward pack, data-gradient pack), fp32 MFMA operands."""
+    _req(weight, torch.float32, "weight")
+    cout, cin = weight.shape[:2]
+    assert tuple(weight.shape[2:]) == (3, 3)
+    nf = int(check(lib().npp_conv32_pack_bytes(cin, cout, 0), "npp_conv32_pack_bytes"))
+    nb = int(check(lib().npp_conv32_pack_bytes(cin, cout, 1), "npp_conv32_pack_bytes"))
+    pf = torch.empty(nf // 4, dtype=torch.float32, device=weight.device)
+    pb = torch.empty(nb // 4, dtype=torch.float32, device=weight.device)
+    check(lib().npp_conv32_pack(_p(weight), cin, cout, _p(pf), _p(pb), _stream()), "npp_conv32_pack")
+    return pf, pb
+
+
+def _f3(v):
+    return None if v is None else (C.c_float * 3)(*[float(t) for t in v])
+
+
+def conv32(x, n_run, cout, pack, mode, y, bias=None, in_norm=None, in_gate=None, gate=None, add=None, out_scale=None):
+    """npp_conv32 on x (N, Cin, H, W) -> y (N, Cout, H, W), the leading n_run images.  mode 0: relu(conv + bias), in_norm =
+    (scale, shift) of the image layer; 1: data gradient (gate / add: the layer below's stored output / tap gradient);
+    2: the image layer's data gradient times out_scale.  in_gate: the layer's own stored output (x is dL/d(its output))."""
+    _req(x, torch.float32, "x")
+    N, cin, H, W = x.shape
+    if n_run > N:
+        raise ValueError(f"x: {N} images, n_run = {n_run}")
+    for t, name in ((y, "y"), (in_gate, "in_gate"), (gate, "gate"), (add, "add")):
+        if t is not None:
+            _req(t, torch.float32, name)
+            if tuple(t.shape[1:]) != ((cin, H, W) if name == "in_gate" else (cout, H, W)) or t.shape[0] < n_run:
+                raise ValueError(f"{name}: shape {tuple(t.shape)} does not cover {n_run} images of this launch")
+    sc, sh = (None, None) if in_norm is None else in_norm
+    check(lib().npp_conv32(_p(x), N, n_run, H, W, cin, cout, _p(pack), mode, _p(bias), _f3(sc), _f3(sh), _p(in_gate), _p(gate), _p(add),
+                           _f3(out_scale), _p(y), _stream()), "npp_conv32")
+    return y
+
+
+def maxpool2_fwd32(x, n_run, y=None):
+    _req(x, torch.float32, "x")
+    N, c, H, W = x.shape
+    if y is None:
+        y = torch.empty((N, c, H // 2, W // 2), dtype=torch.float32, device=x.device)
+    _req(y, torch.float32, "y", (N, c, H // 2, W // 2))
+    check(lib().npp_maxpool2_fwd32(_p(x), N, n_run, H, W, c, _p(y), _stream()), "npp_maxpool2_fwd32")
+    return y
+
+
+def maxpool2_bwd32(dy, x, n_run, dz, add=None, gate=True):
+    """dz = (route(dy) + add) * [x > 0 if gate] on the leading n_run images; x: the pool's fp32 input (N, C, H, W)."""
+    _req(x, torch.float32, "x")
+    N, c, H, W = x.shape
+    _req(dy, torch.float32, "dy")
+    if tuple(dy.shape[1:]) != (c, H // 2, W // 2) or dy.shape[0] < n_run:
+        raise ValueError(f"dy: shape {tuple(dy.shape)} is not the pooled gradient of {n_run} images of {tuple(x.shape)}")
+    _req(dz, torch.float32, "dz", x.shape)
+    if add is not None:
+        _req(add, torch.float32, "add")
+        if tuple(add.shape[1:]) != (c, H, W) or add.shape[0] < n_run:
+            raise ValueError(f"add: shape {tuple(add.shape)} does not cover {n_run} images of {tuple(x.shape)}")
+    check(lib().npp_maxpool2_bwd32(_p(dy), _p(x), _p(add), N, n_run, H, W, c, int(bool(gate)), _p(dz), _stream()), "npp_maxpool2_bwd32")
+    return dz
+
+
 # ---- a10: patch plumbing (train.py:200-236) -----------------------------------------------------------
 def patch_compose_fwd(pred_rows, fake, fmask, real, rmask, n_p, k, P, comp, xy=None):
     """-> xy (2*n_p*k, 3, P, P) = [x | y] (see include/npp_hip.h)."""

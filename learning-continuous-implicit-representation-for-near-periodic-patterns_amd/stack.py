@@ -37,6 +37,9 @@ class StackedFit:
         for f in fits:                  # (before any device work)
             if f.net.precision != "bf16":
                 raise ValueError(f"StackedFit: precision='bf16' fits only (got precision={f.net.precision!r}: the exact-fp32 training chain has no stacked launches)")
+            if getattr(f, "trunk_precision", "fp16") != "fp16":
+                raise ValueError(f"StackedFit: trunk_precision='fp16' fits only (got trunk_precision={f.trunk_precision!r}: the exact-fp32 "
+                                 "trunks have no stacked launches)")
         modes = {f.rng_mode for f in fits}
         if "device" in modes and len(modes) > 1:
             raise ValueError(f"StackedFit: rng_mode='device' for every image of a stack or for none (got {sorted(modes)}): the device draws "

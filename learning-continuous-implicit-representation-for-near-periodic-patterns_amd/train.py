@@ -90,7 +90,11 @@ def parse(argv=None):
                          "runs only -- the losses then differ from the reference's)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"],
                     help="arithmetic of the coordinate MLP's training launches: bf16 (default: the fused bf16 chain) or fp32 (the exact "
-                         "fp32 chain -- the reference's own arithmetic, ~1/16 of the MFMA rate; the VGG trunks stay fp16)")
+                         "fp32 chain -- the reference's own arithmetic, ~1/16 of the MFMA rate; the MLP only, see --trunk_precision)")
+    ap.add_argument("--trunk_precision", default="fp16", choices=["fp16", "fp32"],
+                    help="arithmetic of the VGG trunks of the patch losses: fp16 (default: fp16 activations, bf16 gradients) or fp32 (exact "
+                         "fp32 convolutions -- with --precision fp32 the whole iteration runs in the reference's arithmetic; a diagnostic "
+                         "mode, not stacked)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--save_model", action="store_true",
                     help="after a successful fit, write the network as model.npz into the image's result directory (npp_amd.render reads it)")
@@ -228,7 +232,8 @@ def _build(plan, stacked=False):
                             use_comp=args.use_comp, no_reg_sampling=args.no_reg_sampling, use_patch_weight=args.use_patch_weight,
                             no_pix_loss=args.no_pix_loss, use_contextual_loss=args.use_contextual_loss, width=args.netwidth,
                             loss_type=args.loss_type, use_adaptive_perceptual_loss=args.use_adaptive_perceptual_loss,
-                            normalize_type=args.normalize_type, precision=args.precision)
+                            normalize_type=args.normalize_type, precision=args.precision,
+                            trunk_precision=args.trunk_precision)
     except BaseException:
         import shutil
         shutil.rmtree(outroot, ignore_errors=True)          # (nothing was fitted: a re-run must not take the directory for a result)
@@ -311,7 +316,8 @@ def main(argv=None):
 def stack_key(job):
     """Fits that can share one launch sequence (stack.StackedFit): same network shape, batch shape, loss switches and schedule."""
     a, f = job.args, job.fit
-    if f.patch_sampler is None or f.use_patch_weight or not f.use_contextual_loss or f.net.out_act != 1 or f.net.precision != "bf16":
+    if (f.patch_sampler is None or f.use_patch_weight or not f.use_contextual_loss or f.net.out_act != 1 or f.net.precision != "bf16"
+            or f.trunk_precision != "fp16"):
         return None
     return (a.task, f.style is not None, f.style_w, f.pixel_mask is not None, f.net.K, f.net.width, f.N_rand, f.patch_size, f.patch_num, f.topk, f.net.quad, f.pix_w, f.use_comp, f.cx_w, f.lp_w,
             f.lp_robust, f.use_perceptual_loss, f.rng_mode, a.N_iters, a.i_testset, a.i_print, a.patch_size_decay, str(f.device))
