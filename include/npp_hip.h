@@ -963,6 +963,32 @@ int npp_region_sums_blocks(int H, int W);
 int npp_region_sums(const float* d_a_hw3, const float* d_b_hw3, const float* d_weight_hw, const double* d_ssim_map, int H, int W,
                     double* d_part, void* stream);
 
+/* ---- quality report: LPIPS of whole images (metrics.LPIPSMetric; csrc/npp_lpips_map.hip) --------------------------------------- */
+/* The head of LPIPS.forward(use_robust = False) on the fp32 features of ONE image pair, in float64 throughout (the fp32 features are
+ * exact inputs; every sum has a fixed order; no atomics, nothing kept between launches: two calls give identical bits).
+ * npp_lpips_tap_map (externel_lib/lpips/lpips.py:104-119, lpips/__init__.py:42-44 normalize_tensor, the NetLinLayer's 1 x 1
+ *   convolution): d_map[p] = sum_c lin[c] (a_c(p) / (|a(p)| + 1e-10) - b_c(p) / (|b(p)| + 1e-10))^2 at the h w positions of a tap of C
+ *   channels, two passes over the channels (norms, then differences).  layout: NPP_LPIPS_NCHW -- features (C, h, w); the launcher
+ *   takes one lane per position (NPP_LPIPS_NCHW_LANE) from 16384 positions on and splits the channels over the lanes of a wave
+ *   (NPP_LPIPS_NCHW_SPLIT) below; either form can be asked for by its own code -- or NPP_LPIPS_NHWC: position-major (h, w, C), one wave
+ *   per position.  No transposing copy in either case.
+ * npp_lpips_compose (lpips.py:19-23 upsample, :117, :126-128): d_out (H, W) = sum over the n_taps <= 8 maps d_maps[k] (hs[k], ws[k]),
+ *   in tap order, of their bilinear resize to (H, W) with align_corners = False (source index max(0, (o + 0.5) h / H - 0.5), the +1
+ *   neighbour clamped).  d_maps / hs / ws are HOST arrays (of device pointers / sizes), read before the call returns.  One launch.
+ * npp_map_region_sums (the region mean of the distance map; with a tap's map and no weights, lpips.py:15-16 spatial_average): per-block
+ *   partial sums (sum w, sum w map) over an (H, W) fp32 weight mask -- NULL: all ones -- written to d_part[block][2], block <
+ *   npp_map_region_sums_blocks(H, W) (a function of the shape only; at most 256).  The caller adds the blocks in order.
+ * Every launcher checks on the host first -- null pointers, C < 1, empty maps, an unknown layout code: NPP_ERR_ARG, nothing launched. */
+#define NPP_LPIPS_NCHW 0
+#define NPP_LPIPS_NHWC 1
+#define NPP_LPIPS_NCHW_LANE 2
+#define NPP_LPIPS_NCHW_SPLIT 3
+int npp_lpips_tap_map(const float* d_f0, const float* d_f1, int C, int h, int w, int layout, const float* d_lin, double* d_map,
+                      void* stream);
+int npp_lpips_compose(const double* const* d_maps, const int* hs, const int* ws, int n_taps, int H, int W, double* d_out, void* stream);
+int npp_map_region_sums_blocks(int H, int W);
+int npp_map_region_sums(const double* d_map, const float* d_weight_hw, int H, int W, double* d_part, void* stream);
+
 /* ---- host side: the reference's NumPy random stream, GIL-free ----------------------- */
 /* numpy.random.RandomState(seed) restated bit for bit for the three draws of an iteration (models/sampler.py:260,324;
  * NPP_completion/train.py:172): MT19937 with init_genrand seeding, uniform() from the 53-bit double, and

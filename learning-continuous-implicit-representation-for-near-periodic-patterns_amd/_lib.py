@@ -282,6 +282,10 @@ SYMBOLS = {
     "npp_maxpool_nhwc": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "npp_lpips_spatial_layer": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "npp_resize_bilinear": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "npp_lpips_tap_map": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "npp_lpips_compose": (_i32, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i32, _i32, _i32, _vp, _vp]),
+    "npp_map_region_sums_blocks": (_i32, [_i32, _i32]),
+    "npp_map_region_sums": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
 }
 
 _LIBS = {}

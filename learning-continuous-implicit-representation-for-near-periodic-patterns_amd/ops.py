@@ -1431,6 +1431,57 @@ def region_sums(a, b, weight, smap=None):
     return part
 
 
+# ---- quality report: LPIPS of whole images (include/npp_hip.h npp_lpips_tap_map / npp_lpips_compose / npp_map_region_sums) -----
+LPIPS_LAYOUTS = {"nchw": 0, "nhwc": 1, "nchw_lane": 2, "nchw_split": 3}      # NPP_LPIPS_*
+
+
+def lpips_tap_map(f0, f1, lin, layout="nchw"):
+    """One tap's distance map (h, w) float64 from the fp32 features of the two images -- (C, h, w) for the "nchw" layouts ("nchw": the
+    launcher picks one lane per position or split channels by the number of positions; "nchw_lane" / "nchw_split" ask for one), (h, w,
+    C) for "nhwc" -- and the tap's lin vector (C,) (lpips.py:104-119, plain head, before the upsampling)."""
+    _req(f0, torch.float32, "f0")
+    if f0.dim() != 3:
+        raise ValueError("f0: expected the features of one image, (C, h, w) or (h, w, C)")
+    _req(f1, torch.float32, "f1", f0.shape)
+    if layout not in LPIPS_LAYOUTS:
+        raise ValueError(f"layout: one of {sorted(LPIPS_LAYOUTS)}, got {layout!r}")
+    (h, w, Cc) = f0.shape if layout == "nhwc" else (f0.shape[1], f0.shape[2], f0.shape[0])
+    _req(lin, torch.float32, "lin", (Cc,))
+    d = torch.empty((h, w), dtype=torch.float64, device=f0.device)
+    check(lib().npp_lpips_tap_map(_p(f0), _p(f1), Cc, h, w, LPIPS_LAYOUTS[layout], _p(lin), _p(d), _stream()), "npp_lpips_tap_map")
+    return d
+
+
+def lpips_compose(maps, H, W):
+    """The (H, W) float64 distance map of LPIPS(spatial=True): the taps' maps [(h_k, w_k) float64] resized bilinearly
+    (align_corners=False) and summed in tap order, one launch (lpips.py:117, :126-128)."""
+    for k, m in enumerate(maps):
+        _req(m, torch.float64, f"maps[{k}]")
+        if m.dim() != 2:
+            raise ValueError(f"maps[{k}]: expected (h, w)")
+    n = len(maps)
+    ptrs = (C.c_void_p * n)(*[m.data_ptr() for m in maps])
+    hs, ws = (C.c_int32 * n)(*[m.shape[0] for m in maps]), (C.c_int32 * n)(*[m.shape[1] for m in maps])
+    out = torch.empty((int(H), int(W)), dtype=torch.float64, device=maps[0].device)
+    check(lib().npp_lpips_compose(ptrs, hs, ws, n, int(H), int(W), _p(out), _stream()), "npp_lpips_compose")
+    return out
+
+
+def map_region_sums(dmap, weight=None):
+    """Per-block partial sums (blocks, 2) float64 -- the weights and the weighted map -- of an (H, W) float64 map under an (H, W) fp32
+    weight mask (None: all ones).  Fixed block count and order, like region_sums."""
+    _req(dmap, torch.float64, "dmap")
+    if dmap.dim() != 2:
+        raise ValueError("dmap: expected (H, W)")
+    H, W = int(dmap.shape[0]), int(dmap.shape[1])
+    if weight is not None:
+        _req(weight, torch.float32, "weight", (H, W))
+    nb = check(lib().npp_map_region_sums_blocks(H, W), "npp_map_region_sums_blocks")
+    part = torch.empty((nb, 2), dtype=torch.float64, device=dmap.device)
+    check(lib().npp_map_region_sums(_p(dmap), _p(weight), H, W, _p(part), _stream()), "npp_map_region_sums")
+    return part
+
+
 # ---- remapping variant: Gram-matrix style loss pieces (models/style_loss.py:37-74) ----------------------------
 _gram_ws = {}
 

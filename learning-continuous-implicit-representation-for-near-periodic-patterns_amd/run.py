@@ -46,7 +46,8 @@ def my_share(items):
 
 def metrics_table(args, names):
     """--train-args "--eval_metrics": one table over the images of this rank from the metrics.json each fit left in its result
-    directory (name, PSNR and SSIM of the unknown region).  Printed only when the flag is among the train arguments."""
+    directory (name, PSNR and SSIM of the unknown region; with "--eval_lpips NET" among them also its LPIPS, the mean of the distance
+    map over the region).  Printed only when the flag is among the train arguments."""
     import json
     if "--eval_metrics" not in shlex.split(args.train_args) or not names:
         return
@@ -54,15 +55,16 @@ def metrics_table(args, names):
     a = train_parse(["--datadir", "."] + (["--task", args.task] if args.task != "completion" else []) + shlex.split(args.train_args))
     expname = a.expname if not (args.task != "completion" and a.expname == "completion") else args.task     # train._plan's rule
     width = max([len(n) for n in names] + [5])
-    print(f"{'image':<{width}}  {'PSNR unknown':>12}  {'SSIM unknown':>12}")
+    cols = [("psnr", "{:.2f} dB", "PSNR unknown"), ("ssim", "{:.4f}", "SSIM unknown")] + ([("lpips", "{:.4f}", "LPIPS unknown")] if a.eval_lpips else [])
+    print(f"{'image':<{width}}" + "".join(f"  {title:>13}" if k == "lpips" else f"  {title:>12}" for k, _, title in cols))
     for n in names:
         try:
             with open(os.path.join(args.basedir, f"{expname}_top{args.p_topk}", n, "metrics.json")) as f:
                 u = json.load(f)["unknown"]
-            cells = ["n/a" if u[k] is None else fmt.format(u[k]) for k, fmt in (("psnr", "{:.2f} dB"), ("ssim", "{:.4f}"))]
+            cells = ["n/a" if (u.get(k) if k == "lpips" else u[k]) is None else fmt.format(u[k]) for k, fmt, _ in cols]
         except (OSError, ValueError, KeyError):
-            cells = ["-", "-"]                                     # no report: the fit failed or was found in place without one
-        print(f"{n:<{width}}  {cells[0]:>12}  {cells[1]:>12}")
+            cells = ["-"] * len(cols)                              # no report: the fit failed or was found in place without one
+        print(f"{n:<{width}}" + "".join(f"  {c:>13}" if k == "lpips" else f"  {c:>12}" for c, (k, _, _) in zip(cells, cols)))
     sys.stdout.flush()
 
 

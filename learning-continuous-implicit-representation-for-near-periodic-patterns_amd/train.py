@@ -102,6 +102,10 @@ def parse(argv=None):
                     help="every [EVAL] line also carries the SSIM of the known and the unknown region, and the last report (PSNR, SSIM, "
                          "MAE over all / known / unknown, npp_amd.metrics.report of the image as pred_rgb_img.png holds it) is written "
                          "as metrics.json into the image's result directory (npp_amd.evaluate reproduces it from the files)")
+    ap.add_argument("--eval_lpips", default=None, choices=["vgg", "alex"],
+                    help="with --eval_metrics: the report also carries LPIPS on this net (npp_amd.metrics.LPIPSMetric: per region the "
+                         "mean of the distance map, per image the scalar form) and every [EVAL] line the LPIPS of the known and the "
+                         "unknown region; vgg takes --vgg16 / --lpips_lin, alex --alexnet / --lpips_alex_lin")
     return ap.parse_args(argv)
 
 
@@ -155,9 +159,12 @@ def _plan(argv=None):
         raise SystemExit(f"{refused}: ablation switches of options/arg_config.py that the fused loop is not built for (D = 8, snake, sigmoid / tanh output); other widths / depths / activations run through reference_api.NPP_Net (dense.py)")
     if args.eval_metrics and args.normalize_type != 1:
         raise SystemExit("--eval_metrics judges images in [0, 1] (SSIM's data range is 1): --normalize_type 1 only")
+    if args.eval_lpips is not None and not args.eval_metrics:
+        raise SystemExit("--eval_lpips adds LPIPS to the report of --eval_metrics: give --eval_metrics as well")
     seg_task = args.task == "segmentation"
     from . import weights
     names = ["vgg19"] + ([] if seg_task else ["vgg16"]) + (["alexnet"] if seg_task else [])    # remapping: VGG16 is the style trunk
+    names += [n for n in ({"vgg": "vgg16", "alex": "alexnet"}.get(args.eval_lpips),) if n is not None and n not in names]
     weights.resolve(args, names, args.random_trunks)
     torch.cuda.set_device(torch.device(args.device))
     from . import io as nio
@@ -244,6 +251,18 @@ def _build(plan, stacked=False):
     job.args, job.fit, job.d, job.outroot, job.seg, job.load, job.weights, job.nio = args, fit, d, outroot, seg, load, weights, nio
     job.writer, job.pending, job.t0, job.name = ThreadPoolExecutor(1), [], time.time(), name
     job.metrics = None                                       # --eval_metrics: the report of the newest test set
+    job.lpips = None                                         # --eval_lpips: its LPIPSMetric
+    if args.eval_lpips is not None:
+        # (the state dict is the one object weights.load_state_dict gave the fit's own trunks: with --eval_lpips vgg and an fp32 LPIPS
+        # trunk in the loop the metric finds that trunk's packed weights; there is no second copy)
+        try:
+            from .evaluate import lpips_metric
+            job.lpips = lpips_metric(args.eval_lpips, args, args.lpips_lin if args.eval_lpips == "vgg" else args.lpips_alex_lin, args.device)
+        except BaseException:
+            import shutil
+            fit.close()
+            shutil.rmtree(outroot, ignore_errors=True)
+            raise
     return job
 
 
@@ -253,7 +272,8 @@ def _metrics_report(job, pred_dev, i):
     iteration."""
     from . import metrics
     d = job.d
-    rep = metrics.report(metrics.quantised(pred_dev, d["mask"], d["valid_mask"]), job.fit.img, d["mask"], d["valid_mask"], device=pred_dev.device)
+    rep = metrics.report(metrics.quantised(pred_dev, d["mask"], d["valid_mask"]), job.fit.img, d["mask"], d["valid_mask"], device=pred_dev.device,
+                         **({} if job.lpips is None else {"lpips": job.lpips}))
     rep["iteration"] = int(i)
     return rep
 
@@ -453,6 +473,9 @@ def _after_iteration(job, i):
             job.metrics = _metrics_report(job, pred_dev, i)
             line += ", SSIM known {} unknown {}".format(*("n/a" if job.metrics[r]["ssim"] is None else f"{job.metrics[r]['ssim']:.4f}"
                                                            for r in ("known", "unknown")))
+            if job.lpips is not None:
+                line += ", LPIPS known {} unknown {}".format(*("n/a" if job.metrics[r]["lpips"] is None else f"{job.metrics[r]['lpips']:.4f}"
+                                                                for r in ("known", "unknown")))
         print(line)
         if seg:                                                                         # NPP_segmentation/train.py:337-406
             from . import segment
