@@ -18,9 +18,24 @@ namespace npp {
 // host-side error plumbing (npp_api.cpp)
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE setting of a kernel: each launch site remembers which devices
-// of this process already have it (bit d of the mask), so a second GPU driven from the same process is set up as well.
+// hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE setting of a kernel: SmemOnce remembers which devices of this
+// process already have it (bit d of the mask), so a second GPU driven from the same process is set up as well.
 struct SmemOnce { unsigned long long done = 0; };
+bool smem_attr(SmemOnce& once, const void* fn, int bytes);
+
+// THE launch of a kernel with dynamic LDS.  Kern is a template argument, so the once-flag below exists once per kernel
+// instantiation, wherever it is launched from.  lds_limit is what the kernel's dynamic-LDS limit is raised to, once per device:
+// the launch's own lds_bytes, or the largest any launch of Kern asks for where lds_bytes varies (the limit is set only once);
+// 0 leaves the default 48 KiB alone (sites that raise it only above that pass `bytes > kLdsDefault ? limit : 0`).
+// who: the entry point's name in the error text.  Returns check_launch(who).
+constexpr int kLdsDefault = 48 * 1024;
+template <auto Kern, typename... Args>
+int launch_lds(const char* who, dim3 grid, dim3 block, size_t lds_bytes, int lds_limit, hipStream_t stream, const Args&... args) {
+  static SmemOnce once;
+  if (lds_limit && !smem_attr(once, (const void*)Kern, lds_limit)) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; }
+  hipLaunchKernelGGL(Kern, grid, block, lds_bytes, stream, args...);
+  return check_launch(who);
+}
 
 // Launch-time choices between kernel forms that compute the same result (npp_tune(); defaults = the measured-best forms).  Read
 // with relaxed loads by the launchers; an environment variable of the upper-cased name prefixed NPP_ (NPP_CONV_WINK=0) sets the
@@ -34,7 +49,6 @@ struct Tunables {
   int stash8;         // 1 (default): the training stash that feeds the weight gradients is 8-bit (bf8 gradients with a per-tile power-of-two scale, fp8 layer inputs; npp_layout.h "W8-format") and npp_mlp_wgrad runs on v_mfma_scale_f32_32x32x64_f8f6f4; 0: the round-2..5 16-bit stash and bf16 weight-gradient launch.  Read by npp_mlp_fwd* / npp_mlp_bwd* / npp_mlp_wgrad* at launch: flip it only between complete iterations
 };
 extern Tunables g_tune;
-bool smem_attr(SmemOnce& once, const void* fn, int bytes);
 
 constexpr float kInv2Pi = 0.15915494309189535f;
 

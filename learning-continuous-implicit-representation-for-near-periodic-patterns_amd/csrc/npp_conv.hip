@@ -1282,22 +1282,15 @@ extern "C" int npp_trunk_patch_in_loss_stack(const float* d_pred, int64_t Bp, in
 
 template <int CT, int PT, int S>
 static int conv_launch_mode(const ConvArgs& a, int mode, dim3 grid, hipStream_t s) {
-  const size_t smem = S > 1 ? (size_t)S * CT * PT * 16 * 64 * sizeof(float) : 0;
-#define NPP_CONV_GO(M)                                                                                        \
-  do {                                                                                                        \
-    static SmemOnce once;                                                                                     \
-    if (smem > 48 * 1024 && !smem_attr(once, (const void*)conv3x3_kernel<CT, PT, S, M>, (int)smem)) {          \
-      set_error("npp_conv3x3: smem attribute"); return NPP_ERR_LAUNCH;                                        \
-    }                                                                                                         \
-    hipLaunchKernelGGL((conv3x3_kernel<CT, PT, S, M>), grid, dim3(64 * S), smem, s, a);                       \
-  } while (0)
-  if (mode == kConvFwd) NPP_CONV_GO(kConvFwd);
-  else if (mode == kConvDgradMask) NPP_CONV_GO(kConvDgradMask);
-  else if (mode == kConvFwdPool) NPP_CONV_GO(kConvFwdPool);
-  else if (mode == kConvDgradPool) NPP_CONV_GO(kConvDgradPool);
-  else NPP_CONV_GO(kConvDgradLin);
-#undef NPP_CONV_GO
-  return NPP_OK;
+  const char* who = "npp_conv3x3";
+  constexpr size_t smem = S > 1 ? (size_t)S * CT * PT * 16 * 64 * sizeof(float) : 0;      // the split forms' reduction buffers
+  constexpr int limit = smem > (size_t)kLdsDefault ? (int)smem : 0;
+  const dim3 block(64 * S);
+  if (mode == kConvFwd) return launch_lds<conv3x3_kernel<CT, PT, S, kConvFwd>>(who, grid, block, smem, limit, s, a);
+  if (mode == kConvDgradMask) return launch_lds<conv3x3_kernel<CT, PT, S, kConvDgradMask>>(who, grid, block, smem, limit, s, a);
+  if (mode == kConvFwdPool) return launch_lds<conv3x3_kernel<CT, PT, S, kConvFwdPool>>(who, grid, block, smem, limit, s, a);
+  if (mode == kConvDgradPool) return launch_lds<conv3x3_kernel<CT, PT, S, kConvDgradPool>>(who, grid, block, smem, limit, s, a);
+  return launch_lds<conv3x3_kernel<CT, PT, S, kConvDgradLin>>(who, grid, block, smem, limit, s, a);
 }
 
 // mode 0: y = relu(conv(x) + bias)            (forward layer)
@@ -1391,7 +1384,8 @@ static int conv3x3_impl(const void* d_x, int N_total, int n_run, int H, int W, i
     a.y = nullptr;
     mode = kConvDgradPool;
   }
-  hipStream_t s = (hipStream_t)stream;
+  const hipStream_t s = (hipStream_t)stream;
+  const char* who = "npp_conv3x3";
   // Tile choice: the largest output tile per workgroup (fewest operand bytes per MFMA) that still yields about one
   // workgroup per CU, with the contraction split over S waves (CI % S == 0).  NPP_CONV_TILE="ct,pt,s" forces one
   // (diagnostics: tools/conv_probe.py).
@@ -1434,18 +1428,18 @@ static int conv3x3_impl(const void* d_x, int N_total, int n_run, int H, int W, i
       const int red = 4 * 2 * (2 * npt) * 4096;
       const int smem = 2 * 2 * stage > red ? 2 * 2 * stage : red;
       const dim3 kgrid((unsigned)(a.pos_tiles / (4 * npt)), (unsigned)(cot_n / 2));
-#define NPP_WINK_GO(NPT_, M)                                                                                                    \
-      do {                                                                                                                        \
-        static SmemOnce once;                                                                                                     \
-        if (!smem_attr(once, (const void*)conv3x3_wink_kernel<2, NPT_, 2, M>, 160 * 1024)) { set_error("npp_conv3x3: smem attribute"); return NPP_ERR_LAUNCH; } \
-        hipLaunchKernelGGL((conv3x3_wink_kernel<2, NPT_, 2, M>), kgrid, dim3(512), smem, s, a, wu);                               \
-      } while (0)
-      if (smem <= 160 * 1024) {
-        if (npt == 2) { if (mode == kConvFwd) NPP_WINK_GO(2, kConvFwd); else if (mode == kConvDgradMask) NPP_WINK_GO(2, kConvDgradMask); else NPP_WINK_GO(2, kConvDgradLin); }
-        else { if (mode == kConvFwd) NPP_WINK_GO(1, kConvFwd); else if (mode == kConvDgradMask) NPP_WINK_GO(1, kConvDgradMask); else NPP_WINK_GO(1, kConvDgradLin); }
-        return check_launch("npp_conv3x3");
+      constexpr int kWinkLdsMax = 160 * 1024;        // the limit set: the most a launch of these kernels may ask for (smem grows with Wp)
+      if (smem <= kWinkLdsMax) {
+        const dim3 kblock(512);
+        if (npt == 2) {
+          if (mode == kConvFwd) return launch_lds<conv3x3_wink_kernel<2, 2, 2, kConvFwd>>(who, kgrid, kblock, smem, kWinkLdsMax, s, a, wu);
+          if (mode == kConvDgradMask) return launch_lds<conv3x3_wink_kernel<2, 2, 2, kConvDgradMask>>(who, kgrid, kblock, smem, kWinkLdsMax, s, a, wu);
+          return launch_lds<conv3x3_wink_kernel<2, 2, 2, kConvDgradLin>>(who, kgrid, kblock, smem, kWinkLdsMax, s, a, wu);
+        }
+        if (mode == kConvFwd) return launch_lds<conv3x3_wink_kernel<2, 1, 2, kConvFwd>>(who, kgrid, kblock, smem, kWinkLdsMax, s, a, wu);
+        if (mode == kConvDgradMask) return launch_lds<conv3x3_wink_kernel<2, 1, 2, kConvDgradMask>>(who, kgrid, kblock, smem, kWinkLdsMax, s, a, wu);
+        return launch_lds<conv3x3_wink_kernel<2, 1, 2, kConvDgradLin>>(who, kgrid, kblock, smem, kWinkLdsMax, s, a, wu);
       }
-#undef NPP_WINK_GO
     }
   }
   // window-staged form (conv3x3_win_kernel): few input-channel steps, many positions, 64-channel output blocks
@@ -1455,17 +1449,10 @@ static int conv3x3_impl(const void* d_x, int N_total, int n_run, int H, int W, i
       ((win_wgs >= 200 && mode == kConvFwd && a.CI <= 4) || win_mode == 2)) {       // measured: only these layers gain (conv1_1, conv1_2, conv2_1 forward)
     const dim3 wgrid((unsigned)(a.pos_tiles / 8), (unsigned)(cot_n / 2));
     constexpr int smem = win_lds_bytes<2>();
-#define NPP_WIN_GO(M)                                                                                           \
-    do {                                                                                                          \
-      static SmemOnce once;                                                                                       \
-      if (!smem_attr(once, (const void*)conv3x3_win_kernel<2, M>, smem)) { set_error("npp_conv3x3: smem attribute"); return NPP_ERR_LAUNCH; } \
-      hipLaunchKernelGGL((conv3x3_win_kernel<2, M>), wgrid, dim3(256), smem, s, a);                               \
-    } while (0)
-    if (mode == kConvFwd) NPP_WIN_GO(kConvFwd);
-    else if (mode == kConvDgradMask) NPP_WIN_GO(kConvDgradMask);
-    else NPP_WIN_GO(kConvDgradLin);
-#undef NPP_WIN_GO
-    return check_launch("npp_conv3x3");
+    const dim3 wblock(256);
+    if (mode == kConvFwd) return launch_lds<conv3x3_win_kernel<2, kConvFwd>>(who, wgrid, wblock, smem, smem, s, a);
+    if (mode == kConvDgradMask) return launch_lds<conv3x3_win_kernel<2, kConvDgradMask>>(who, wgrid, wblock, smem, smem, s, a);
+    return launch_lds<conv3x3_win_kernel<2, kConvDgradLin>>(who, wgrid, wblock, smem, smem, s, a);
   }
   dim3 grid((unsigned)(a.pos_tiles / pick.pt), (unsigned)(cot_n / pick.ct));
   // weight-stationary numbering where the pack outweighs the activations the launch reads and there are channel groups for all XCDs
@@ -1476,13 +1463,14 @@ static int conv3x3_impl(const void* d_x, int N_total, int n_run, int H, int W, i
     a.pf = nullptr; a.pf_bytes = 0;                       // (the next pack is partitioned the same way: nothing to request into EVERY L2)
     grid = dim3((unsigned)(8 * (((int)grid.y + 7) / 8) * (int)grid.x), 1);
   }
-  int lrc = NPP_OK;
-#define NPP_CONV_CASE(CT_, PT_, S_) if (pick.ct == CT_ && pick.pt == PT_ && pick.s == S_) lrc = conv_launch_mode<CT_, PT_, S_>(a, mode, grid, s)
-  NPP_CONV_CASE(2, 2, 4); else NPP_CONV_CASE(2, 1, 4); else NPP_CONV_CASE(1, 1, 8); else NPP_CONV_CASE(1, 1, 4);
-  else NPP_CONV_CASE(2, 2, 1); else NPP_CONV_CASE(2, 1, 1); else NPP_CONV_CASE(1, 1, 1);
-#undef NPP_CONV_CASE
-  if (lrc) return lrc;
-  return check_launch("npp_conv3x3");
+  const int ct = pick.ct, pt = pick.pt, ws = pick.s;          // one of cands[]
+  if (ct == 2 && pt == 2 && ws == 4) return conv_launch_mode<2, 2, 4>(a, mode, grid, s);
+  if (ct == 2 && pt == 1 && ws == 4) return conv_launch_mode<2, 1, 4>(a, mode, grid, s);
+  if (ct == 1 && pt == 1 && ws == 8) return conv_launch_mode<1, 1, 8>(a, mode, grid, s);
+  if (ct == 1 && pt == 1 && ws == 4) return conv_launch_mode<1, 1, 4>(a, mode, grid, s);
+  if (ct == 2 && pt == 2 && ws == 1) return conv_launch_mode<2, 2, 1>(a, mode, grid, s);
+  if (ct == 2 && pt == 1 && ws == 1) return conv_launch_mode<2, 1, 1>(a, mode, grid, s);
+  return conv_launch_mode<1, 1, 1>(a, mode, grid, s);
 }
 
 extern "C" int npp_maxpool2_fwd(const void* d_x, int N, int H, int W, int C, void* d_y, void* stream) {

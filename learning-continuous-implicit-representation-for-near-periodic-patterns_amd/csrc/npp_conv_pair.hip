@@ -760,10 +760,8 @@ static int pair_launch(PairArgs& a, hipStream_t s) {
   static_assert(G::kLds <= 80 * 1024, "two workgroups per CU");
   a.tiles_x = (a.W + 15) / 16;
   a.tiles_y = (a.H + TH - 1) / TH;
-  static SmemOnce once;
-  if (!smem_attr(once, (const void*)conv_pair_fwd_kernel<CAS, CB, CC, TH>, G::kLds)) { set_error("npp_conv_pair_fwd: smem attribute"); return NPP_ERR_LAUNCH; }
-  hipLaunchKernelGGL((conv_pair_fwd_kernel<CAS, CB, CC, TH>), dim3((unsigned)(a.n_run * a.tiles_x * a.tiles_y)), dim3(256), G::kLds, s, a);
-  return check_launch("npp_conv_pair_fwd");
+  return launch_lds<conv_pair_fwd_kernel<CAS, CB, CC, TH>>("npp_conv_pair_fwd", dim3((unsigned)(a.n_run * a.tiles_x * a.tiles_y)), dim3(256),
+                                                           G::kLds, G::kLds, s, a);
 }
 
 // Shapes the fused pair is built for: (Cin, Cmid, Cout) = (16, 64, 64) and (64, 128, 128).  H, W even (the pool), any size.
@@ -802,10 +800,8 @@ extern "C" int npp_conv_pair_fwd(const void* d_x, int N_total, int n_run, int n_
   constexpr int kLds8 = 16 * 180 * 16 + 8 * 240 * 16 + 2 * 4 * 9 * 1024;
   a.tiles_x = (W + 15) / 16;
   a.tiles_y = (H + 7) / 8;
-  static SmemOnce once8;
-  if (!smem_attr(once8, (const void*)conv_pair8_fwd_kernel<4>, kLds8)) { set_error("npp_conv_pair_fwd: smem attribute"); return NPP_ERR_LAUNCH; }
-  hipLaunchKernelGGL((conv_pair8_fwd_kernel<4>), dim3((unsigned)(a.n_run * a.tiles_x * a.tiles_y)), dim3(512), kLds8, (hipStream_t)stream, a);
-  return check_launch("npp_conv_pair_fwd");
+  return launch_lds<conv_pair8_fwd_kernel<4>>("npp_conv_pair_fwd", dim3((unsigned)(a.n_run * a.tiles_x * a.tiles_y)), dim3(512), kLds8, kLds8,
+                                              (hipStream_t)stream, a);
 }
 
 
@@ -833,10 +829,8 @@ extern "C" int npp_conv_pair_dgrad(const void* d_dz_b, int N_total, int n_run, i
   a.stamps = npp::g_diag_stamps; a.stamps_n = npp::g_diag_n;
 #endif
   constexpr int kLds = 8 * 324 * 16 + 8 * 400 * 16 + 2 * 2 * 9 * 1024;
-  static SmemOnce once;
-  if (!smem_attr(once, (const void*)conv_pair_dgrad_kernel, kLds)) { set_error("npp_conv_pair_dgrad: smem attribute"); return NPP_ERR_LAUNCH; }
-  hipLaunchKernelGGL(conv_pair_dgrad_kernel, dim3((unsigned)(n_run * a.tiles_x * a.tiles_y)), dim3(512), kLds, (hipStream_t)stream, a);
-  return check_launch("npp_conv_pair_dgrad");
+  return launch_lds<conv_pair_dgrad_kernel>("npp_conv_pair_dgrad", dim3((unsigned)(n_run * a.tiles_x * a.tiles_y)), dim3(512), kLds, kLds,
+                                            (hipStream_t)stream, a);
 }
 
 
@@ -887,8 +881,6 @@ extern "C" int npp_conv_pair_fwd_patch(const float* d_pred_rows, const float* d_
   a.stamps = npp::g_diag_stamps; a.stamps_n = npp::g_diag_n;
 #endif
   typedef PairGeom<1, 64, 64, 16> G;
-  static SmemOnce once;
-  if (!smem_attr(once, (const void*)conv_pair_fwd_kernel<1, 64, 64, 16, true>, G::kLds)) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; }
-  hipLaunchKernelGGL((conv_pair_fwd_kernel<1, 64, 64, 16, true>), dim3((unsigned)(a.n_tiles + a.nb_loss)), dim3(256), G::kLds, (hipStream_t)stream, a);
-  return check_launch(who);
+  return launch_lds<conv_pair_fwd_kernel<1, 64, 64, 16, true>>(who, dim3((unsigned)(a.n_tiles + a.nb_loss)), dim3(256), G::kLds, G::kLds,
+                                                               (hipStream_t)stream, a);
 }

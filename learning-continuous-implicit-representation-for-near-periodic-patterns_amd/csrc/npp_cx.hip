@@ -1127,13 +1127,11 @@ static int cx_launch(const float* d_fx, const float* d_fy, int N, int C, int hw,
   const int t32 = hw / 32;
   if (fast) {
     hipLaunchKernelGGL(cx_sim_kernel, dim3((unsigned)(((int64_t)N * tiles * tiles + 7) / 8 * 8)), dim3(256), 0, s, d_fx, d_fy, N, C, hw, w);
-    static SmemOnce once;
     const size_t smem = (size_t)kCxRowWaves * hw * sizeof(float);
-    if (smem > 48 * 1024 && !smem_attr(once, (const void*)cx_rows_fwd32_kernel, kCxRowWaves * 64 * kCxMaxCols * 4)) {
-      set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(cx_rows_fwd32_kernel, dim3((unsigned)((int64_t)N * ((hw + kCxRowWaves - 1) / kCxRowWaves))), dim3(64 * kCxRowWaves), smem, s, N,
-                       hw, inv_h, w, scale, (int)loss_in_rows);
+    constexpr int kRowLdsMax = kCxRowWaves * 64 * kCxMaxCols * 4;      // the limit set: the widest row this form takes (hw <= 64 kCxMaxCols), not this launch's
+    const int rc = launch_lds<cx_rows_fwd32_kernel>(who, dim3((unsigned)((int64_t)N * ((hw + kCxRowWaves - 1) / kCxRowWaves))), dim3(64 * kCxRowWaves), smem,
+                                                    smem > (size_t)kLdsDefault ? kRowLdsMax : 0, s, N, hw, inv_h, w, scale, (int)loss_in_rows);
+    if (rc) return rc;                       // (the launcher checks its own launch: a failure ends the sequence here instead of at its last launch)
   } else if (big && !d_dfx && big_fwd_fits(N, C, hw)) {
     // whole-image crop, value only (the ranking's score): re-tiled normalised operands, 128 x 128 tiles in super-block order, the
     // matrix stored tiled, written once and read twice.  Everything lives in the D + cx regions (2 N hw^2 floats).

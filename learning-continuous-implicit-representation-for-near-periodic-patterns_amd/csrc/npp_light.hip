@@ -423,18 +423,12 @@ static int light_fwd_go(const npp_light_desc* L, const float* d_params, int64_t 
   LightArgs a{};
   a.L = *L; a.params = d_params; a.params_stride = params_stride; a.pack = d_pack; a.pack_stride = pack_stride;
   a.x_per = d_x_per; a.x_pos = d_x_pos; a.stash = d_stash; a.pred = d_pred; a.B = B; a.idx = d_idx; a.n_src = n_src; a.x_pos_cs = x_pos_cs; a.idx_cs = idx_cs;
-  if (light_rows_per_wg(C, B, false) == 64) {
-    static SmemOnce once;
-    if (!smem_attr(once, (const void*)light_fwd_kernel<2>, light_region_bytes(2))) { set_error("npp_light_fwd: smem attribute"); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL(light_fwd_kernel<2>, dim3((unsigned)(B / 64), (unsigned)C), dim3(kLThreads), light_region_bytes(2), (hipStream_t)stream, a,
-                       light_pack_desc());
-  } else {
-    static SmemOnce once;
-    if (!smem_attr(once, (const void*)light_fwd_kernel<1>, light_region_bytes(1))) { set_error("npp_light_fwd: smem attribute"); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL(light_fwd_kernel<1>, dim3((unsigned)(B / 32), (unsigned)C), dim3(kLThreads), light_region_bytes(1), (hipStream_t)stream, a,
-                       light_pack_desc());
-  }
-  return check_launch("npp_light_fwd");
+  const hipStream_t s = (hipStream_t)stream;
+  if (light_rows_per_wg(C, B, false) == 64)
+    return launch_lds<light_fwd_kernel<2>>("npp_light_fwd", dim3((unsigned)(B / 64), (unsigned)C), dim3(kLThreads), light_region_bytes(2),
+                                          light_region_bytes(2), s, a, light_pack_desc());
+  return launch_lds<light_fwd_kernel<1>>("npp_light_fwd", dim3((unsigned)(B / 32), (unsigned)C), dim3(kLThreads), light_region_bytes(1),
+                                        light_region_bytes(1), s, a, light_pack_desc());
 }
 
 extern "C" int npp_light_fwd(const npp_light_desc* L, const float* d_params, int64_t params_stride, const float* d_pack, int64_t pack_stride,
@@ -467,18 +461,12 @@ static int light_bwd_go(const npp_light_desc* L, const float* d_params, int64_t 
   a.L = *L; a.params = d_params; a.params_stride = params_stride; a.pack = d_pack; a.pack_stride = pack_stride;
   a.stash = (float*)d_stash; a.pred = (float*)d_pred; a.dpred = d_dpred; a.draw = d_draw; a.dstash = d_dstash; a.B = B;
   a.lo = LightLossArgs{d_gt, d_latents, d_spline, n_knots, x_scale, d_loss, d_dlatent, d_part, gt_cs};
-  if (light_rows_per_wg(C, B, true) == 64) {
-    static SmemOnce once;
-    if (!smem_attr(once, (const void*)light_bwd_kernel<2>, light_region_bytes(2))) { set_error("npp_light_bwd: smem attribute"); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL(light_bwd_kernel<2>, dim3((unsigned)(B / 64), (unsigned)C), dim3(kLThreads), light_region_bytes(2), (hipStream_t)stream, a,
-                       light_pack_desc());
-  } else {
-    static SmemOnce once;
-    if (!smem_attr(once, (const void*)light_bwd_kernel<1>, light_region_bytes(1))) { set_error("npp_light_bwd: smem attribute"); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL(light_bwd_kernel<1>, dim3((unsigned)(B / 32), (unsigned)C), dim3(kLThreads), light_region_bytes(1), (hipStream_t)stream, a,
-                       light_pack_desc());
-  }
-  return check_launch("npp_light_bwd");
+  const hipStream_t s = (hipStream_t)stream;
+  if (light_rows_per_wg(C, B, true) == 64)
+    return launch_lds<light_bwd_kernel<2>>("npp_light_bwd", dim3((unsigned)(B / 64), (unsigned)C), dim3(kLThreads), light_region_bytes(2),
+                                          light_region_bytes(2), s, a, light_pack_desc());
+  return launch_lds<light_bwd_kernel<1>>("npp_light_bwd", dim3((unsigned)(B / 32), (unsigned)C), dim3(kLThreads), light_region_bytes(1),
+                                        light_region_bytes(1), s, a, light_pack_desc());
 }
 
 extern "C" int npp_light_bwd(const npp_light_desc* L, const float* d_params, int64_t params_stride, const float* d_pack, int64_t pack_stride,

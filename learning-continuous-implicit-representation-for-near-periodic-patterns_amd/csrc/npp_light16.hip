@@ -597,12 +597,9 @@ static int l16_fwd_go(const npp_light_desc* L, const float* d_params, int64_t pa
   a.L = *L; a.params = d_params; a.params_stride = params_stride; a.pack = (const bf16x8*)d_pack; a.pack_stride16 = pack_stride_bytes / 16;
   a.x_per = d_x_per; a.x_pos = d_x_pos; a.idx = d_idx; a.n_src = n_src; a.actF = (char*)d_actF; a.act_stride = act_stride_bytes;
   a.pred = d_pred; a.B = B; a.x_pos_cs = x_pos_cs; a.idx_cs = idx_cs;
-  static SmemOnce once;
-  if (!smem_attr(once, (const void*)light16_fwd_kernel, kL16SmemF)) { set_error("npp_light16_fwd: smem attribute"); return NPP_ERR_LAUNCH; }
   const int n_wg = (int)(B / kRowTile);
-  hipLaunchKernelGGL(light16_fwd_kernel, dim3((unsigned)((n_wg * C + 7) / 8 * 8)), dim3(kL16Threads), kL16SmemF, (hipStream_t)stream, a,
-                     l16_pack_desc(), n_wg, C);
-  return check_launch("npp_light16_fwd");
+  return launch_lds<light16_fwd_kernel>("npp_light16_fwd", dim3((unsigned)((n_wg * C + 7) / 8 * 8)), dim3(kL16Threads), kL16SmemF, kL16SmemF,
+                                        (hipStream_t)stream, a, l16_pack_desc(), n_wg, C);
 }
 extern "C" int npp_light16_fwd(const npp_light_desc* L, const float* d_params, int64_t params_stride, const void* d_pack,
                                int64_t pack_stride_bytes, const float* d_x_per, const float* d_x_pos, const int64_t* d_idx, int64_t n_src,
@@ -637,12 +634,9 @@ static int l16_bwd_go(const npp_light_desc* L, const float* d_params, int64_t pa
   a.actF = (char*)d_actF; a.act_stride = act_stride_bytes; a.dzF = (char*)d_dzF; a.dz_stride = dz_stride_bytes;
   a.pred = (float*)d_pred; a.dpred = d_dpred; a.B = B;
   a.lo = LightLossArgs{d_gt, d_latents, d_spline, n_knots, x_scale, d_loss, d_dlatent, d_part, gt_cs};
-  static SmemOnce once;
-  if (!smem_attr(once, (const void*)light16_bwd_kernel, kL16SmemB)) { set_error("npp_light16_bwd: smem attribute"); return NPP_ERR_LAUNCH; }
   const int n_wg = (int)(B / kRowTile);
-  hipLaunchKernelGGL(light16_bwd_kernel, dim3((unsigned)((n_wg * C + 7) / 8 * 8)), dim3(kL16Threads), kL16SmemB, (hipStream_t)stream, a,
-                     l16_pack_desc(), n_wg, C);
-  return check_launch("npp_light16_bwd");
+  return launch_lds<light16_bwd_kernel>("npp_light16_bwd", dim3((unsigned)((n_wg * C + 7) / 8 * 8)), dim3(kL16Threads), kL16SmemB, kL16SmemB,
+                                        (hipStream_t)stream, a, l16_pack_desc(), n_wg, C);
 }
 extern "C" int npp_light16_bwd(const npp_light_desc* L, const float* d_params, int64_t params_stride, const void* d_pack,
                                int64_t pack_stride_bytes, const void* d_actF, int64_t act_stride_bytes, const float* d_pred,

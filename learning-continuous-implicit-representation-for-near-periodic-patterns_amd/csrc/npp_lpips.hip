@@ -345,17 +345,13 @@ static int lp_launch(LpMulti& m, void* stream, const char* who) {
     const int q = m.t[i].few ? m.t[i].C / 64 : m.t[i].C / 16;
     maxq = q > maxq ? q : maxq;
   }
-#define NPP_LP_GO(MQ)                                                                                                                  \
-  do {                                                                                                                                 \
-    static SmemOnce once;                                                                                                              \
-    if (!smem_attr(once, (const void*)lpips_multi_kernel<MQ>, lp_smem_bytes(kLpipsMaxC, 4))) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; } \
-    hipLaunchKernelGGL(lpips_multi_kernel<MQ>, dim3((unsigned)nb, (unsigned)m.n_taps), dim3(256), (size_t)smem, (hipStream_t)stream, m); \
-  } while (0)
-  if (maxq <= 8) NPP_LP_GO(8);
-  else if (maxq <= 16) NPP_LP_GO(16);
-  else NPP_LP_GO(32);
-#undef NPP_LP_GO
-  return check_launch(who);
+  // the limit set: what the widest tap any launch may carry asks for (smem is this launch's own)
+  constexpr int kLpLdsMax = lp_smem_bytes(kLpipsMaxC, 4);
+  const dim3 grid((unsigned)nb, (unsigned)m.n_taps), block(256);
+  const hipStream_t s = (hipStream_t)stream;
+  if (maxq <= 8) return launch_lds<lpips_multi_kernel<8>>(who, grid, block, (size_t)smem, kLpLdsMax, s, m);
+  if (maxq <= 16) return launch_lds<lpips_multi_kernel<16>>(who, grid, block, (size_t)smem, kLpLdsMax, s, m);
+  return launch_lds<lpips_multi_kernel<32>>(who, grid, block, (size_t)smem, kLpLdsMax, s, m);
 }
 
 extern "C" int npp_lpips_layer(const float* d_f0, const float* d_f1, int N, int C, int hw, const float* d_lin,

@@ -356,20 +356,13 @@ static int bwd_go(const BwdArgs& A, int K, void* stream) {
   const NetDesc d = make_desc(K);
   const BwdDesc bd = make_bwd_desc(K);
   const dim3 grid(A.S.M ? stack_grid(A.S) : (unsigned)(A.Bp / kRowTile)), block(kThreadsB);
-  hipStream_t s = (hipStream_t)stream;
-#define NPP_LAUNCH_B(M, S8)                                                                        \
-  do {                                                                                             \
-    static SmemOnce once;                                                                          \
-    if (!smem_attr(once, (const void*)mlp_bwd_kernel<M, S8>, kSmemBwd)) {                          \
-      set_error("npp_mlp_bwd: smem attribute"); return NPP_ERR_LAUNCH;                             \
-    }                                                                                              \
-    hipLaunchKernelGGL((mlp_bwd_kernel<M, S8>), grid, block, kSmemBwd, s, A, d, bd);               \
-  } while (0)
+  const hipStream_t s = (hipStream_t)stream;
+  const char* who = "npp_mlp_bwd";
   const bool s8 = __atomic_load_n(&g_tune.stash8, __ATOMIC_RELAXED) != 0;
-  if (K > 1) { if (s8) NPP_LAUNCH_B(true, true); else NPP_LAUNCH_B(true, false); }
-  else { if (s8) NPP_LAUNCH_B(false, true); else NPP_LAUNCH_B(false, false); }
-#undef NPP_LAUNCH_B
-  return check_launch("npp_mlp_bwd");
+  if (K > 1) return s8 ? launch_lds<mlp_bwd_kernel<true, true>>(who, grid, block, kSmemBwd, kSmemBwd, s, A, d, bd)
+                       : launch_lds<mlp_bwd_kernel<true, false>>(who, grid, block, kSmemBwd, kSmemBwd, s, A, d, bd);
+  return s8 ? launch_lds<mlp_bwd_kernel<false, true>>(who, grid, block, kSmemBwd, kSmemBwd, s, A, d, bd)
+            : launch_lds<mlp_bwd_kernel<false, false>>(who, grid, block, kSmemBwd, kSmemBwd, s, A, d, bd);
 }
 
 extern "C" int npp_mlp_bwd(const float* d_dpred, const float* d_pred, int64_t Bp, int K, int width, const void* d_wb,

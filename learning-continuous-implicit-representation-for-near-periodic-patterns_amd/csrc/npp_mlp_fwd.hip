@@ -992,55 +992,33 @@ using namespace npp;
 #undef s_actF
 #undef s_actE
 
-static int fwd_launch(const FwdArgs& A, const EmbedDev& e, const NetDesc& d, bool emb_in, void* stream, const char* who) {
-  const dim3 grid(A.S.M ? stack_grid(A.S) : (unsigned)(A.Bp / kRowTile)), block(kThreads);
-  const bool train = A.actF != nullptr, multi = d.K > 1;
+// Every launched instantiation of mlp_fwd_kernel, as one selection over (kernel form, stash form T, K > 1).  The entry point names
+// the form; T: 0 no stash (inference), 1 the 16-bit training stash, 2 the 8-bit one (npp_tune "stash8").  The stacked form always
+// trains and the render forms never do, so only those T exist for them: 3 forms x 3 T + stacked x 2 T + 2 render forms, x 2 for K.
+enum FwdForm { kFwdPlain, kFwdEmbIn, kFwdStack, kFwdAct, kFwdCoordF, kFwdGrid };
+struct FwdLaunch {
+  const FwdArgs& A; const EmbedDev& e; const NetDesc& d;
+  dim3 grid; hipStream_t stream; const char* who;
+  template <int T, FwdForm F>
+  int go() const {
+    constexpr bool EMB_IN = F == kFwdEmbIn, STACK = F == kFwdStack, ACT = F == kFwdAct;      // ACT: the output nonlinearity is read from the arguments
+    constexpr int CM = F == kFwdCoordF ? kCoordF32 : F == kFwdGrid ? kCoordGrid : kCoordI32;
+    const dim3 block(kThreads);
+    return d.K > 1 ? launch_lds<mlp_fwd_kernel<T, true, EMB_IN, STACK, ACT, CM>>(who, grid, block, kSmemFwd, kSmemFwd, stream, A, e, d)
+                   : launch_lds<mlp_fwd_kernel<T, false, EMB_IN, STACK, ACT, CM>>(who, grid, block, kSmemFwd, kSmemFwd, stream, A, e, d);
+  }
+};
+
+static int fwd_launch(FwdForm f, const FwdArgs& A, const EmbedDev& e, const NetDesc& d, void* stream, const char* who) {
   const bool s8 = __atomic_load_n(&g_tune.stash8, __ATOMIC_RELAXED) != 0;     // npp_tune "stash8": the 8-bit training stash
-  hipStream_t s = (hipStream_t)stream;
-#define NPP_LAUNCH(T, M, E)                                                                       \
-  do {                                                                                            \
-    static SmemOnce once;                                                                         \
-    if (!smem_attr(once, (const void*)mlp_fwd_kernel<T, M, E>, kSmemFwd)) {                       \
-      set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH;                                \
-    }                                                                                             \
-    hipLaunchKernelGGL((mlp_fwd_kernel<T, M, E>), grid, block, kSmemFwd, s, A, e, d);             \
-  } while (0)
-#define NPP_LAUNCH2(E)                                                                            \
-  do {                                                                                            \
-    if (train && s8) { if (multi) NPP_LAUNCH(2, true, E); else NPP_LAUNCH(2, false, E); }         \
-    else if (train) { if (multi) NPP_LAUNCH(1, true, E); else NPP_LAUNCH(1, false, E); }          \
-    else { if (multi) NPP_LAUNCH(0, true, E); else NPP_LAUNCH(0, false, E); }                     \
-  } while (0)
-  if (A.S.M) {                            // stacked launch: training form, coordinates in
-#define NPP_LAUNCH_STACK(T, M)                                                                                 \
-    do {                                                                                                         \
-      static SmemOnce once;                                                                                      \
-      if (!smem_attr(once, (const void*)mlp_fwd_kernel<T, M, false, true>, kSmemFwd)) {                          \
-        set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH;                                             \
-      }                                                                                                          \
-      hipLaunchKernelGGL((mlp_fwd_kernel<T, M, false, true>), grid, block, kSmemFwd, s, A, e, d);                \
-    } while (0)
-    if (s8) { if (multi) NPP_LAUNCH_STACK(2, true); else NPP_LAUNCH_STACK(2, false); }
-    else { if (multi) NPP_LAUNCH_STACK(1, true); else NPP_LAUNCH_STACK(1, false); }
-#undef NPP_LAUNCH_STACK
-  } else if (emb_in) NPP_LAUNCH2(true);
-  else if (A.out_act != 1) {               // npp_mlp_fwd_act: the instantiations that read the nonlinearity from the arguments
-#define NPP_LAUNCH_ACT(T, M)                                                                                   \
-    do {                                                                                                         \
-      static SmemOnce once;                                                                                      \
-      if (!smem_attr(once, (const void*)mlp_fwd_kernel<T, M, false, false, true>, kSmemFwd)) {                   \
-        set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH;                                             \
-      }                                                                                                          \
-      hipLaunchKernelGGL((mlp_fwd_kernel<T, M, false, false, true>), grid, block, kSmemFwd, s, A, e, d);         \
-    } while (0)
-    if (train && s8) { if (multi) NPP_LAUNCH_ACT(2, true); else NPP_LAUNCH_ACT(2, false); }
-    else if (train) { if (multi) NPP_LAUNCH_ACT(1, true); else NPP_LAUNCH_ACT(1, false); }
-    else { if (multi) NPP_LAUNCH_ACT(0, true); else NPP_LAUNCH_ACT(0, false); }
-#undef NPP_LAUNCH_ACT
-  } else NPP_LAUNCH2(false);
-#undef NPP_LAUNCH2
-#undef NPP_LAUNCH
-  return check_launch(who);
+  const int T = A.actF != nullptr ? (s8 ? 2 : 1) : 0;
+  if (f == kFwdPlain && A.out_act != 1) f = kFwdAct;
+  const FwdLaunch L{A, e, d, dim3(A.S.M ? stack_grid(A.S) : (unsigned)(A.Bp / kRowTile)), (hipStream_t)stream, who};
+  if (f == kFwdStack) return s8 ? L.go<2, kFwdStack>() : L.go<1, kFwdStack>();      // always trains, whatever actF says: never T = 0
+  if (f == kFwdEmbIn) return T == 2 ? L.go<2, kFwdEmbIn>() : T == 1 ? L.go<1, kFwdEmbIn>() : L.go<0, kFwdEmbIn>();
+  if (f == kFwdAct) return T == 2 ? L.go<2, kFwdAct>() : T == 1 ? L.go<1, kFwdAct>() : L.go<0, kFwdAct>();
+  if (f == kFwdPlain) return T == 2 ? L.go<2, kFwdPlain>() : T == 1 ? L.go<1, kFwdPlain>() : L.go<0, kFwdPlain>();
+  return f == kFwdCoordF ? L.go<0, kFwdCoordF>() : L.go<0, kFwdGrid>();
 }
 
 static int fwd_check(int64_t Bp, int width, const void* in, const void* d_wf, const float* d_params, const float* d_pred,
@@ -1060,7 +1038,7 @@ extern "C" int npp_mlp_fwd(const int32_t* d_coords_yx, int64_t Bp, const npp_emb
   FwdArgs A{};
   A.coords = d_coords_yx; A.Bp = Bp; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_pred;
   A.actF = (char*)d_actT; A.out_act = 1;
-  return fwd_launch(A, make_embed_dev(*cfg), make_desc(cfg->K), false, stream, "npp_mlp_fwd");
+  return fwd_launch(kFwdPlain, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, "npp_mlp_fwd");
 }
 
 // npp_mlp_fwd with the output nonlinearity of render() as an argument (models/helpers.py:55-60): 1 sigmoid (--normalize_type 1, what
@@ -1074,7 +1052,7 @@ extern "C" int npp_mlp_fwd_act(const int32_t* d_coords_yx, int64_t Bp, const npp
   FwdArgs A{};
   A.coords = d_coords_yx; A.Bp = Bp; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_pred;
   A.actF = (char*)d_actT; A.out_act = out_act;
-  return fwd_launch(A, make_embed_dev(*cfg), make_desc(cfg->K), false, stream, "npp_mlp_fwd_act");
+  return fwd_launch(kFwdPlain, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, "npp_mlp_fwd_act");
 }
 
 extern "C" int npp_mlp_fwd_emb(const float* d_emb, int64_t ld, int64_t Bp, int K, int width, const void* d_wf,
@@ -1090,32 +1068,12 @@ extern "C" int npp_mlp_fwd_emb(const float* d_emb, int64_t ld, int64_t Bp, int K
   A.emb = d_emb; A.emb_ld = ld; A.out_act = out_act;
   EmbedDev e{};
   e.K = K;
-  return fwd_launch(A, e, make_desc(K), true, stream, "npp_mlp_fwd_emb");
+  return fwd_launch(kFwdEmbIn, A, e, make_desc(K), stream, "npp_mlp_fwd_emb");
 }
 
 // ---- render paths: fp32 positions / the implicit canvas grid (include/npp_hip.h "continuous coordinates") -----------------------
 namespace npp {
 int check_grid(const npp_grid* g, const char* who);
-}
-
-template <int CM>
-static int fwd_launch_render(const FwdArgs& A, const npp_embed_cfg* cfg, int64_t n_wg, void* stream, const char* who) {
-  const EmbedDev e = make_embed_dev(*cfg);
-  const NetDesc d = make_desc(cfg->K);
-  const dim3 grid((unsigned)n_wg), block(kThreads);
-  hipStream_t s = (hipStream_t)stream;
-#define NPP_LAUNCH_RENDER(M)                                                                                   \
-  do {                                                                                                         \
-    static SmemOnce once;                                                                                      \
-    if (!smem_attr(once, (const void*)mlp_fwd_kernel<0, M, false, false, false, CM>, kSmemFwd)) {              \
-      set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH;                                             \
-    }                                                                                                          \
-    hipLaunchKernelGGL((mlp_fwd_kernel<0, M, false, false, false, CM>), grid, block, kSmemFwd, s, A, e, d);    \
-  } while (0)
-  if (d.K > 1) NPP_LAUNCH_RENDER(true);
-  else NPP_LAUNCH_RENDER(false);
-#undef NPP_LAUNCH_RENDER
-  return check_launch(who);
 }
 
 extern "C" int npp_mlp_fwd_coordf(const float* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_wf,
@@ -1128,7 +1086,7 @@ extern "C" int npp_mlp_fwd_coordf(const float* d_coords_yx, int64_t Bp, const np
   FwdArgs A{};
   A.Bp = Bp; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_pred; A.out_act = out_act;
   A.coordsf = d_coords_yx;
-  return fwd_launch_render<kCoordF32>(A, cfg, Bp / kRowTile, stream, who);
+  return fwd_launch(kFwdCoordF, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, who);
 }
 
 extern "C" int npp_mlp_fwd_grid(const npp_grid* grid, const npp_embed_cfg* cfg, int width, const void* d_wf, const float* d_params,
@@ -1145,7 +1103,7 @@ extern "C" int npp_mlp_fwd_grid(const npp_grid* grid, const npp_embed_cfg* cfg, 
   FwdArgs A{};
   A.Bp = n_wg * kRowTile; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_out; A.out_act = out_act;
   A.g = *grid;
-  return fwd_launch_render<kCoordGrid>(A, cfg, n_wg, stream, who);
+  return fwd_launch(kFwdGrid, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, who);
 }
 
 // ---- stacked form: M images per launch (npp_common.h "stacked launches") ----------------------------------------------------
@@ -1178,5 +1136,5 @@ extern "C" int npp_mlp_fwd_stack(const int32_t* d_coords_yx, int64_t Bp, const v
   A.wf_stride16 = wf_stride_bytes / 16; A.params_stride = params_stride; A.act_stride = act_stride_bytes;
   EmbedDev e{};
   e.K = K;
-  return fwd_launch(A, e, make_desc(K), false, stream, "npp_mlp_fwd_stack");
+  return fwd_launch(kFwdStack, A, e, make_desc(K), stream, "npp_mlp_fwd_stack");
 }

@@ -328,17 +328,9 @@ static int fwd32_launch(const Fwd32Args& A, const npp_embed_cfg* cfg, int64_t n_
   const NetDesc d = make_desc(cfg->K);
   const Desc32 d32 = make_desc32(cfg->K);
   const dim3 grid((unsigned)n_wg), block(kT32);
-  hipStream_t s = (hipStream_t)stream;
-  if (cfg->K > 1) {
-    static SmemOnce once;
-    if (!smem_attr(once, (const void*)mlp_fwd32_kernel<true, CM, STASH>, kSmem32)) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL((mlp_fwd32_kernel<true, CM, STASH>), grid, block, kSmem32, s, A, e, d, d32);
-  } else {
-    static SmemOnce once;
-    if (!smem_attr(once, (const void*)mlp_fwd32_kernel<false, CM, STASH>, kSmem32)) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL((mlp_fwd32_kernel<false, CM, STASH>), grid, block, kSmem32, s, A, e, d, d32);
-  }
-  return NPP_OK;
+  const hipStream_t s = (hipStream_t)stream;
+  return cfg->K > 1 ? launch_lds<mlp_fwd32_kernel<true, CM, STASH>>(who, grid, block, kSmem32, kSmem32, s, A, e, d, d32)
+                    : launch_lds<mlp_fwd32_kernel<false, CM, STASH>>(who, grid, block, kSmem32, kSmem32, s, A, e, d, d32);
 }
 
 extern "C" int npp_mlp_fwd32(const int32_t* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_w32,
@@ -349,8 +341,7 @@ extern "C" int npp_mlp_fwd32(const int32_t* d_coords_yx, int64_t Bp, const npp_e
   if (Bp <= 0 || Bp % kRowTile || Bp / kRowTile > 0x7fffffffLL) { set_error("npp_mlp_fwd32: Bp=%lld must be a positive multiple of %d", (long long)Bp, kRowTile); return NPP_ERR_ARG; }
   if (!d_coords_yx || !d_w32 || !d_params || !d_out || out_act < 0 || out_act > 2) { set_error("npp_mlp_fwd32: bad argument"); return NPP_ERR_ARG; }
   Fwd32Args A{d_coords_yx, Bp, (const float*)d_w32, d_params, d_out, out_act};
-  if ((rc = fwd32_launch<kCoordI32>(A, cfg, Bp / kRowTile, stream, "npp_mlp_fwd32"))) return rc;
-  return check_launch("npp_mlp_fwd32");
+  return fwd32_launch<kCoordI32>(A, cfg, Bp / kRowTile, stream, "npp_mlp_fwd32");
 }
 
 extern "C" int npp_mlp_fwd32_coordf(const float* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_w32,
@@ -362,8 +353,7 @@ extern "C" int npp_mlp_fwd32_coordf(const float* d_coords_yx, int64_t Bp, const 
   if (Bp <= 0 || Bp % kRowTile || Bp / kRowTile > 0x7fffffffLL) { set_error("%s: Bp=%lld must be a positive multiple of %d", who, (long long)Bp, kRowTile); return NPP_ERR_ARG; }
   if (!d_coords_yx || !d_w32 || !d_params || !d_out || out_act < 0 || out_act > 2) { set_error("%s: bad argument", who); return NPP_ERR_ARG; }
   Fwd32Args A{nullptr, Bp, (const float*)d_w32, d_params, d_out, out_act, d_coords_yx, npp_grid{}};
-  if ((rc = fwd32_launch<kCoordF32>(A, cfg, Bp / kRowTile, stream, who))) return rc;
-  return check_launch(who);
+  return fwd32_launch<kCoordF32>(A, cfg, Bp / kRowTile, stream, who);
 }
 
 extern "C" int npp_mlp_fwd32_grid(const npp_grid* grid, const npp_embed_cfg* cfg, int width, const void* d_w32, const float* d_params,
@@ -377,8 +367,7 @@ extern "C" int npp_mlp_fwd32_grid(const npp_grid* grid, const npp_embed_cfg* cfg
   if (!d_w32 || !d_params || !d_out || out_act < 0 || out_act > 2) { set_error("%s: bad argument", who); return NPP_ERR_ARG; }
   const int64_t n_wg = (grid->n + kRowTile - 1) / kRowTile;
   Fwd32Args A{nullptr, n_wg * kRowTile, (const float*)d_w32, d_params, d_out, out_act, nullptr, *grid};
-  if ((rc = fwd32_launch<kCoordGrid>(A, cfg, n_wg, stream, who))) return rc;
-  return check_launch(who);
+  return fwd32_launch<kCoordGrid>(A, cfg, n_wg, stream, who);
 }
 
 // The forward of the exact-fp32 fit: npp_mlp_fwd32 plus the stash (d_stash: sizes[1] of npp_train_workspace32)
@@ -391,6 +380,5 @@ extern "C" int npp_mlp_fwd32_train(const int32_t* d_coords_yx, int64_t Bp, const
   if (Bp <= 0 || Bp % kRowTile || Bp / kRowTile > 0x7fffffffLL) { set_error("%s: Bp=%lld must be a positive multiple of %d", who, (long long)Bp, kRowTile); return NPP_ERR_ARG; }
   if (!d_coords_yx || !d_w32 || !d_params || !d_pred || !d_stash || out_act < 0 || out_act > 2) { set_error("%s: bad argument", who); return NPP_ERR_ARG; }
   Fwd32Args A{d_coords_yx, Bp, (const float*)d_w32, d_params, d_pred, out_act, nullptr, npp_grid{}, (float*)d_stash};
-  if ((rc = fwd32_launch<kCoordI32, true>(A, cfg, Bp / kRowTile, stream, who))) return rc;
-  return check_launch(who);
+  return fwd32_launch<kCoordI32, true>(A, cfg, Bp / kRowTile, stream, who);
 }

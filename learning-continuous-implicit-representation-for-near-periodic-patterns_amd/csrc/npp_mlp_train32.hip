@@ -341,17 +341,9 @@ extern "C" int npp_mlp_bwd32(const float* d_dpred, const float* d_pred, int64_t 
   if (!d_dpred || !d_pred || !d_w32_bwd || !d_params || !d_stash || !d_dz || out_act < 0 || out_act > 2) { set_error("%s: bad argument", who); return NPP_ERR_ARG; }
   Bwd32Args a{d_dpred, d_pred, Bp, (const float*)d_w32_bwd, d_params, (const float*)d_stash, (float*)d_dz, out_act};
   const dim3 grid((unsigned)(Bp / kRowTile)), block(kTB32);
-  hipStream_t st = (hipStream_t)stream;
-  if (K > 1) {
-    static SmemOnce once;
-    if (!smem_attr(once, (const void*)mlp_bwd32_kernel<true>, kSmemB32)) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL(mlp_bwd32_kernel<true>, grid, block, kSmemB32, st, a, make_desc(K), make_bdesc32(K));
-  } else {
-    static SmemOnce once;
-    if (!smem_attr(once, (const void*)mlp_bwd32_kernel<false>, kSmemB32)) { set_error("%s: smem attribute", who); return NPP_ERR_LAUNCH; }
-    hipLaunchKernelGGL(mlp_bwd32_kernel<false>, grid, block, kSmemB32, st, a, make_desc(K), make_bdesc32(K));
-  }
-  return check_launch(who);
+  const hipStream_t st = (hipStream_t)stream;
+  return K > 1 ? launch_lds<mlp_bwd32_kernel<true>>(who, grid, block, kSmemB32, kSmemB32, st, a, make_desc(K), make_bdesc32(K))
+               : launch_lds<mlp_bwd32_kernel<false>>(who, grid, block, kSmemB32, kSmemB32, st, a, make_desc(K), make_bdesc32(K));
 }
 
 extern "C" int npp_mlp_wgrad32(const void* d_dz, const void* d_stash, const npp_embed_cfg* cfg, int64_t Bp, int K, int width, int ksplit,

@@ -852,9 +852,6 @@ static int wgrad_launch(const void* d_dzT, const void* d_actT, int64_t Bp, int K
     set_error("npp_mlp_wgrad: %d workgroup tiles per split exceed the %d whose scales fit in LDS: raise ksplit", A.wg_chunk, kScale8Max);
     return NPP_ERR_ARG;
   }
-  static SmemOnce once, once8;
-  if (!smem_attr(once, (const void*)wgrad_kernel, kSmemW)) { set_error("npp_mlp_wgrad: smem attribute"); return NPP_ERR_LAUNCH; }
-  if (!smem_attr(once8, (const void*)wgrad8_kernel, kSmemW8)) { set_error("npp_mlp_wgrad: smem attribute"); return NPP_ERR_LAUNCH; }
   A.ntiles = ntiles; A.ksplit = ksplit;
   unsigned grid = (unsigned)(ntiles * ksplit);
   if (M) {
@@ -866,9 +863,8 @@ static int wgrad_launch(const void* d_dzT, const void* d_actT, int64_t Bp, int K
     }
     grid = stack_grid(A.S);
   }
-  if (s8) hipLaunchKernelGGL(wgrad8_kernel, dim3(grid), dim3(kWThreads), kSmemW8, (hipStream_t)stream, A);
-  else hipLaunchKernelGGL(wgrad_kernel, dim3(grid), dim3(kWThreads), kSmemW, (hipStream_t)stream, A);
-  return check_launch("npp_mlp_wgrad");
+  return s8 ? launch_lds<wgrad8_kernel>("npp_mlp_wgrad", dim3(grid), dim3(kWThreads), kSmemW8, kSmemW8, (hipStream_t)stream, A)
+            : launch_lds<wgrad_kernel>("npp_mlp_wgrad", dim3(grid), dim3(kWThreads), kSmemW, kSmemW, (hipStream_t)stream, A);
 }
 
 // ---- the same launch over NPP_Net_light's 16-bit stashes (csrc/npp_light16.hip): seven jobs per candidate, candidate =
@@ -923,12 +919,9 @@ extern "C" int npp_light16_wgrad(const npp_light_desc* L, const void* d_actF, in
   if (L->ld[4] < (kLW + kLPos + 3) / 4 * 4) { set_error("npp_light16_wgrad: pos_linears.0 must be stored %d wide", (kLW + kLPos + 3) / 4 * 4); return NPP_ERR_ARG; }
   A.njobs = nj;
   A.wg_chunk = (int)((A.n_wg + ksplit - 1) / ksplit);
-  static SmemOnce once;
-  if (!smem_attr(once, (const void*)wgrad_kernel, kSmemW)) { set_error("npp_light16_wgrad: smem attribute"); return NPP_ERR_LAUNCH; }
   A.ntiles = tile; A.ksplit = ksplit;
   A.S = make_stack(C, tile * ksplit, nullptr);
   A.dz_img_stride = dz_stride_bytes; A.act_img_stride = act_stride_bytes; A.slab_img_stride = slab_cand_stride;
-  hipLaunchKernelGGL(wgrad_kernel, dim3(stack_grid(A.S)), dim3(kWThreads), kSmemW, (hipStream_t)stream, A);
-  return check_launch("npp_light16_wgrad");
+  return launch_lds<wgrad_kernel>("npp_light16_wgrad", dim3(stack_grid(A.S)), dim3(kWThreads), kSmemW, kSmemW, (hipStream_t)stream, A);
 #endif
 }

@@ -305,6 +305,40 @@ def test_fused_light_chains_equal_the_layer_by_layer_path(dev):
     assert nets[0].nets[0].opt_step == nets[1].nets[0].opt_step == 10
 
 
+def test_fused_light_chains_at_64_row_blocks(dev):
+    """The fused chains where both run 64 rows per workgroup (csrc/npp_light.hip light_rows_per_wg: the forward once
+    C (B / 32) > 768, the data-gradient chain once it is > 1536; 3 candidates of 16 448 rows: 1542): predictions, losses and every
+    parameter gradient of one step against the layer-by-layer dense path, at the tolerances of
+    test_fused_light_chains_equal_the_layer_by_layer_path (which stays on the 32-row forms)."""
+    from npp_amd import ops
+    from npp_amd.light import NPPNetLightBatch, default_light_init
+    H, B, C = 96, 16448, 3
+    assert ops.light_part_blocks(C, B) == B // 64 and ops.light_part_blocks(C, 256) == 256 // 32
+    rng = np.random.RandomState(12)
+    angles = np.array([[0.0, 90.0], [30.0, 120.0], [10.0, 80.0]], np.float32)
+    periods = np.array([[12.0, 9.0], [7.0, 15.0], [20.0, 6.0]], np.float32)
+    freqs = (rng.randn(10) * 10).astype(np.float32)
+    init = default_light_init(256, 4)
+    nets = [NPPNetLightBatch([(angles[i], periods[i]) for i in range(C)], freqs, (H, H), init, device=dev, fused=f) for f in (True, False)]
+    coords = torch.from_numpy(np.stack([rng.randint(0, H, B), rng.randint(0, H, B)], 1).astype(np.int32)).to(dev)
+    tabs = [n_.embed(coords) for n_ in nets[0].nets]
+    x_pos, x_per = tabs[0][0], torch.stack([t[1] for t in tabs])
+    gt = torch.from_numpy(rng.rand(B, 3).astype(np.float32)).to(dev)
+    nets[0].fused_adam = False               # keep the gradients for the comparison (the fused Adam launch clears them)
+    losses = [n_.train_step(x_pos, x_per, gt).clone() for n_ in nets]
+    pf, pu = nets[0]._ws[("fused", B)]["pred"], nets[1]._ws[B]["pred"]
+    print("max |pred difference|", float((pf - pu).abs().max()))
+    np.testing.assert_allclose(pf.cpu().numpy(), pu.cpu().numpy(), atol=3e-6)
+    for name in nets[0].dw:
+        for part in ("dw", "db"):
+            a, b_ = getattr(nets[0], part)[name].cpu().numpy(), getattr(nets[1], part)[name].cpu().numpy()
+            for ci in range(C):
+                print(name, part, ci, f"rel L2 {rel_l2(a[ci], b_[ci]):.3e}")
+                assert rel_l2(a[ci], b_[ci]) < 2e-5, (name, part, ci, rel_l2(a[ci], b_[ci]))
+    assert rel_l2(nets[0].grad.cpu().numpy(), nets[1].grad.cpu().numpy()) < 2e-5
+    np.testing.assert_allclose(losses[0].cpu().numpy(), losses[1].cpu().numpy(), rtol=2e-5)
+
+
 def test_create_npp_net_is_search_consumes_the_generator_like_the_reference(dev, golden):
     """torch.manual_seed(0); create_npp_net(..., is_search=True) (search.py:91-99) through the boundary module leaves the SAME
     Fourier frequencies and the SAME initial weights as the reference's own construction (g10c_light_init.npz): the position embedder's

@@ -188,11 +188,13 @@ def _lpips_plain_head_torch(f0, f1, lin):
     return ((n0 - n1).pow(2) * lin[None, :, None, None]).sum(1).mean((1, 2)).sum()
 
 
-@pytest.mark.parametrize("C,hw", [(64, 24), (256, 12), (512, 6)])
+@pytest.mark.parametrize("C,hw", [(64, 24), (256, 12), (512, 6), (256, 27), (512, 27)])
 def test_lpips_plain_head_with_gradient(dev, C, hw):
     """npp_lpips_layer with no latents = LPIPS.forward(use_robust=False) (lpips.py:108-109) -- the in-loop head under
     --use_adaptive_perceptual_loss off: value against the forward-only kernel the ranking score uses (pinned to the reference by g10)
-    and against torch fp32, gradient against torch autograd."""
+    and against torch fp32, gradient against torch autograd.  The 27 x 27 taps have more than 2048 positions (3 x 729), where a
+    thread takes C / 16 channels of 16 positions: the 16- and 32-channel forms of the kernel (csrc/npp_lpips.hip lp_launch), which
+    no tap of the loop's patch sizes reaches."""
     from npp_amd import ops
     g = torch.Generator().manual_seed(C)
     N = 3
@@ -363,32 +365,40 @@ def test_lpips_branch_as_a_captured_graph_equals_its_launches(dev, decay):
 def test_fused_chain_with_tanh_output(dev):
     """render()'s other output nonlinearity (models/helpers.py:57-58, --normalize_type 2) in the fused launches: npp_mlp_fwd_act
     (tanh / raw) and npp_mlp_bwd_act behind it.  The forward against its own raw output; the backward against the sigmoid path fed a
-    d pred that gives the same d raw -- every weight gradient must then agree."""
+    d pred that gives the same d raw -- every weight gradient must then agree.  With K = 3 and K = 1 and with either training stash:
+    each pair is another instantiation of the forward kernel that reads the nonlinearity from its arguments."""
     from npp_amd import ops
     from npp_amd.model import NPPNet
-    H, K, rows = 128, 3, 1024
-    angles, periods, _ = oracle.synthetic_periodicity(H, K)
-    P = oracle.init_params(K, seed=5)
-    ns = NPPNet(angles, periods, oracle.SEED0_FREQS, (H, H), params=P, device=dev, ksplit=2, out_act=1)
-    nt = NPPNet(angles, periods, oracle.SEED0_FREQS, (H, H), params=P, device=dev, ksplit=2, out_act=2)
-    g = torch.Generator().manual_seed(2)
-    c = torch.randint(0, H, (rows, 2), generator=g, dtype=torch.int32).to(dev)
-    raw = ops.mlp_fwd(c, ns.cfg, ns.wf, ns.params, width=ns.width, out_act=0)
-    ns.zero_grad(); nt.zero_grad()
-    ns.forward_train(c); nt.forward_train(c)
-    ws, wt = ns.workspace(rows), nt.workspace(rows)
-    np.testing.assert_allclose(ws["pred"].cpu().numpy(), torch.sigmoid(raw).cpu().numpy(), atol=2e-6)
-    np.testing.assert_allclose(wt["pred"].cpu().numpy(), torch.tanh(raw).cpu().numpy(), atol=2e-6)
-    np.testing.assert_allclose(nt.render(c).cpu().numpy(), torch.tanh(raw).cpu().numpy(), atol=2e-6)
-    dp = torch.randn(rows, 3, generator=g).to(dev) * 1e-3
-    s_, t_ = ws["pred"], wt["pred"]
-    ws["dpred"].copy_(dp)
-    wt["dpred"].copy_(dp * (s_ * (1 - s_)) / (1 - t_ * t_).clamp_min(1e-6))
-    ns.backward(rows); nt.backward(rows)
-    torch.cuda.synchronize()
-    gs, gt_ = ns.grads(), nt.grads()
-    for name in gs:
-        assert rel_l2(gt_[name], gs[name]) < 1e-4, (name, rel_l2(gt_[name], gs[name]))
+    H, rows = 128, 1024
+    old = ops.tune("stash8")
+    try:
+        for K, s8 in ((3, 1), (3, 0), (1, 1), (1, 0)):
+            ops.tune("stash8", s8)
+            angles, periods, _ = oracle.synthetic_periodicity(H, K)
+            P = oracle.init_params(K, seed=5)
+            ns = NPPNet(angles, periods, oracle.SEED0_FREQS, (H, H), params=P, device=dev, ksplit=2, out_act=1)
+            nt = NPPNet(angles, periods, oracle.SEED0_FREQS, (H, H), params=P, device=dev, ksplit=2, out_act=2)
+            g = torch.Generator().manual_seed(2)
+            c = torch.randint(0, H, (rows, 2), generator=g, dtype=torch.int32).to(dev)
+            raw = ops.mlp_fwd(c, ns.cfg, ns.wf, ns.params, width=ns.width, out_act=0)
+            ns.zero_grad(); nt.zero_grad()
+            ns.forward_train(c); nt.forward_train(c)
+            ws, wt = ns.workspace(rows), nt.workspace(rows)
+            np.testing.assert_allclose(ws["pred"].cpu().numpy(), torch.sigmoid(raw).cpu().numpy(), atol=2e-6)
+            np.testing.assert_allclose(wt["pred"].cpu().numpy(), torch.tanh(raw).cpu().numpy(), atol=2e-6)
+            np.testing.assert_allclose(nt.render(c).cpu().numpy(), torch.tanh(raw).cpu().numpy(), atol=2e-6)
+            dp = torch.randn(rows, 3, generator=g).to(dev) * 1e-3
+            s_, t_ = ws["pred"], wt["pred"]
+            ws["dpred"].copy_(dp)
+            wt["dpred"].copy_(dp * (s_ * (1 - s_)) / (1 - t_ * t_).clamp_min(1e-6))
+            ns.backward(rows); nt.backward(rows)
+            torch.cuda.synchronize()
+            gs, gt_ = ns.grads(), nt.grads()
+            for name in gs:
+                print(f"K={K} stash8={s8} {name}: rel L2 {rel_l2(gt_[name], gs[name]):.3e}")
+                assert rel_l2(gt_[name], gs[name]) < 1e-4, (K, s8, name, rel_l2(gt_[name], gs[name]))
+    finally:
+        ops.tune("stash8", old)
 
 
 def test_adam_golden(dev, golden):
