@@ -946,6 +946,34 @@ int npp_blur_sv_share(const uint8_t* d_gray_hw, int H, int W, int sv_num, double
 int npp_binary_morph(const uint8_t* d_in_hw, int H, int W, int iterations, int dilate, uint8_t* d_tmp_hw, uint8_t* d_out_hw,
                      void* stream);
 
+/* ---- segmentation task: 4-connected components (regions.py; csrc/npp_regions.hip) ------------------------------- */
+/* The input is an (H, W) int32 LABEL IMAGE: 0 = outside, any other value a class; two pixels are connected when they are 4-neighbours
+ * carrying the same non-zero value (a binary mask: every set value 1).  H, W >= 1 and H W < 2^31, otherwise arbitrary (1 x W and H x 1
+ * included; no multiple of any tile).  No entry keeps state in device memory between launches; scratch is the caller's, its size is
+ * stated by the entry and it needs no initial content; every sum is an integer sum: two calls give identical bits.  Bad arguments:
+ * NPP_ERR_ARG and a message, nothing launched.
+ * npp_cc_label: d_root_hw (H, W) int32 (an array of its own) = -1 where the input is 0, elsewhere the SMALLEST row-major index
+ *   i W + j of the pixel's component: a pure function of the input, whatever the launch schedule.  Three launches (tiles in LDS, the
+ *   pairs across tile borders by device-scope atomics, every pixel to its root); H <= 65535 * 16.
+ * npp_cc_number: roots -> numbers 1..C in ascending root order = raster order of first appearance (a root is its component's first
+ *   pixel in raster order), 0 outside: the numbering of scipy.ndimage.label.  *d_count = C (a device word).  d_numbered_hw may be
+ *   d_root_hw.  d_scratch: npp_cc_number_scratch_bytes(H, W) bytes, 4-byte aligned.
+ * npp_cc_stats: per component c = 1..C of a numbered image, at index c - 1: d_size_c int64 pixel count; d_sums_cn (C, nch) int64 sums
+ *   of the nch <= 4 channels of the (H, W, nch) uint8 image d_values_hwc (nch = 0: no image, no sums); d_box_c4 (C, 4) int32 bounding
+ *   box (first row, first column, last row, last column), (INT_MAX, INT_MAX, -1, -1) for a number without pixels; d_border_c one byte,
+ *   1 = the component touches the image border.  Numbers outside 1..C are skipped.  The entry initialises its outputs itself.
+ * npp_cc_*_host: the same definitions in plain C++ on host memory, no GPU. */
+int npp_cc_label(const int32_t* d_labels_hw, int H, int W, int32_t* d_root_hw, void* stream);
+int64_t npp_cc_number_scratch_bytes(int H, int W);
+int npp_cc_number(const int32_t* d_root_hw, int H, int W, int32_t* d_numbered_hw, int32_t* d_count, void* d_scratch, int64_t scratch_bytes,
+                  void* stream);
+int npp_cc_stats(const int32_t* d_numbered_hw, int H, int W, int C, const uint8_t* d_values_hwc, int nch, int64_t* d_size_c,
+                 int64_t* d_sums_cn, uint8_t* d_border_c, int32_t* d_box_c4, void* stream);
+int npp_cc_label_host(const int32_t* labels_hw, int H, int W, int32_t* root_hw);
+int npp_cc_number_host(const int32_t* root_hw, int H, int W, int32_t* numbered_hw, int32_t* count);
+int npp_cc_stats_host(const int32_t* numbered_hw, int H, int W, int C, const uint8_t* values_hwc, int nch, int64_t* size_c,
+                      int64_t* sums_cn, uint8_t* border_c, int32_t* box_c4);
+
 /* ---- quality report: SSIM and region-wise PSNR / MAE of an image against a ground truth (metrics.py) ------------------------- */
 /* Both images are (H, W, 3) fp32 in [0, 1], read as they lie; all arithmetic and every output is float64.  No entry keeps state in
  * device memory between launches and none uses atomics: two calls give identical bits.

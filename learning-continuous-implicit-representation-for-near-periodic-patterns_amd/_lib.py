@@ -174,6 +174,13 @@ SYMBOLS = {
     "npp_rgb_to_gray_u8": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "npp_blur_sv_share": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "npp_binary_morph": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "npp_cc_label": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "npp_cc_number_scratch_bytes": (_i64, [_i32, _i32]),
+    "npp_cc_number": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "npp_cc_stats": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "npp_cc_label_host": (_i32, [_vp, _i32, _i32, _vp]),
+    "npp_cc_number_host": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "npp_cc_stats_host": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "npp_ssim_map": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "npp_region_sums_blocks": (_i32, [_i32, _i32]),
     "npp_region_sums": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),

@@ -6,7 +6,9 @@ reference's own result differs from run to run (unseeded k-means starts).  This 
 
 What runs where: everything per PIXEL -- colour conversion and blur, the ten assign / update rounds of SLIC, the per-superpixel
 sums and histograms -- is HIP (csrc/npp_slic.hip through ops.slic_*).  Everything per SUPERPIXEL (a few hundred nodes) is NumPy /
-SciPy on the host: the connectivity repair (a graph traversal done once per image), the mixture model and the graph cut.
+SciPy on the host: the connectivity repair (a graph traversal done once per image), the mixture model and the graph cut.  The repair's
+own per-pixel half -- labelling the 4-connected fragments, their sizes, colour sums and touching pairs -- runs on the host by default and
+through npp_amd.regions (csrc/npp_regions.hip) with cc_device; its merge rounds over the fragments are host work either way.
 """
 import numpy as np
 import scipy.sparse as sparse
@@ -48,7 +50,37 @@ def slic_geometry(mask, sp_size):
     return n_segments, S, pos[keep]
 
 
-def enforce_connectivity(labels, min_size, colour, max_size=None):
+def _fragments_cc(labels, colour, cc_device):
+    """The per-pixel half of enforce_connectivity through npp_amd.regions on `cc_device` ("cpu": the library's host twins; a CUDA
+    device: the kernels): -> frag (H,W) int32 tensor on that device (the 4-connected fragments numbered 1..C in raster order, 0
+    outside), C, size (C+1,) and csum (C+1, nch) float64 (entry 0 unused: 0), the sorted unique int64 codes of the touching pairs."""
+    import torch
+    from . import ops, regions
+    colour = np.asarray(colour)
+    H, W = labels.shape
+    if colour.dtype != np.uint8 or colour.shape[:2] != (H, W) or colour.ndim != 3 or not 1 <= colour.shape[2] <= ops.CC_MAX_CHANNELS:
+        raise TypeError(f"enforce_connectivity(cc_device={cc_device!r}): colour must be an ({H}, {W}, 1..{ops.CC_MAX_CHANNELS}) uint8 "
+                        f"image (what slic() passes), got {colour.dtype} {colour.shape}")
+    dev = torch.device("cpu") if str(cc_device) == "cpu" else ops.select_device(cc_device)
+    lab = torch.from_numpy(np.ascontiguousarray(np.where(labels > 0, labels, 0), np.int32))      # (the host path's `inside`)
+    if dev.type == "cuda":
+        frag, C = regions.label(lab.to(dev), dev)
+        sz, cs, _, _ = regions.component_stats(frag, C, torch.from_numpy(np.ascontiguousarray(colour)).to(dev))
+        sz, cs = sz.cpu().numpy(), cs.cpu().numpy()
+    else:
+        frag, C = regions.label(lab, "cpu")
+        sz, cs, _, _ = regions.component_stats(frag.numpy(), C, colour)
+    size = np.concatenate([[0.0], sz.astype(np.float64)])
+    csum = np.concatenate([np.zeros((1, colour.shape[2])), cs.astype(np.float64)])
+    f = frag.long()
+    i, j = torch.cat([f[:, :-1].reshape(-1), f[:-1].reshape(-1)]), torch.cat([f[:, 1:].reshape(-1), f[1:].reshape(-1)])
+    k = (i != j) & (i > 0) & (j > 0)
+    i, j = i[k], j[k]
+    pairs = torch.unique(torch.minimum(i, j) * (C + 1) + torch.maximum(i, j), sorted=True)
+    return frag, C, size, csum, pairs.cpu().numpy()
+
+
+def enforce_connectivity(labels, min_size, colour, max_size=None, cc_device=None):
     """Connectivity repair of a label image (0 = outside the mask): every 4-connected fragment becomes a segment of its own, then the
     segments smaller than `min_size` pixels are merged away in rounds -- each picks one adjacent segment, all picks of a round are
     carried out together -- until none is left that has a neighbour; labels are renumbered 1..N in raster order of first appearance.
@@ -58,9 +90,22 @@ def enforce_connectivity(labels, min_size, colour, max_size=None):
     image most of the area lies in fragments below `min_size`, and the merge decides what the superpixels are.  Merging by colour
     keeps a fragment of a flat region out of the textured segment next to it (and the other way round), which merging by border
     length or by size does not.  Host code on purpose: a graph traversal over a few thousand fragments, done once per image (whole
-    rounds at a time in NumPy)."""
+    rounds at a time in NumPy).  cc_device: None -- the fragments, their sizes, colour sums and touching pairs are found on the
+    host too (SciPy); "cpu" or a CUDA device -- by npp_amd.regions there (`colour` must then be the uint8 image itself); the merge
+    rounds are the same host code and the returned labels are identical."""
     labels = np.asarray(labels)
     H, W = labels.shape
+    if cc_device is not None:
+        import torch
+        frag_t, C, size, csum, pairs = _fragments_cc(labels, colour, cc_device)
+        max_size = 6 * min_size if max_size is None else max_size
+        root = _merge_rounds(C, size, csum, pairs, min_size, max_size)
+        # raster order of first appearance = ascending lowest fragment number: the fragments are numbered in that order themselves
+        remap = np.zeros(C + 1, np.int32)
+        kept = np.unique(root[1:])
+        remap[kept] = np.arange(1, len(kept) + 1)
+        lut = torch.from_numpy(remap[root]).to(frag_t.device)
+        return lut[frag_t.long()].cpu().numpy()
     idx = np.arange(H * W).reshape(H, W)
     same_h = (labels[:, :-1] == labels[:, 1:]) & (labels[:, :-1] > 0)
     same_v = (labels[:-1] == labels[1:]) & (labels[:-1] > 0)
@@ -83,13 +128,21 @@ def enforce_connectivity(labels, min_size, colour, max_size=None):
     colour = np.asarray(colour, np.float64).reshape(H * W, -1)
     csum = np.stack([np.bincount(frag.ravel(), weights=colour[:, k], minlength=C + 1) for k in range(colour.shape[1])], 1)
     max_size = 6 * min_size if max_size is None else max_size
+    pairs = _touching(np.concatenate([frag[:, :-1].ravel(), frag[:-1].ravel()]), np.concatenate([frag[:, 1:].ravel(), frag[1:].ravel()]), C)
+    root = _merge_rounds(C, size, csum, pairs, min_size, max_size)
+    return raster_numbers(root[frag])[0].astype(np.int32)
 
-    def touching(i, j):
-        """Unordered pairs of different segments as one sorted int64 code each."""
-        k = (i != j) & (i > 0) & (j > 0)
-        i, j = i[k], j[k]
-        return np.unique(np.minimum(i, j) * (C + 1) + np.maximum(i, j))
-    pairs = touching(np.concatenate([frag[:, :-1].ravel(), frag[:-1].ravel()]), np.concatenate([frag[:, 1:].ravel(), frag[1:].ravel()]))
+
+def _touching(i, j, C):
+    """Unordered pairs of different segments as one sorted int64 code each."""
+    k = (i != j) & (i > 0) & (j > 0)
+    i, j = i[k], j[k]
+    return np.unique(np.minimum(i, j) * (C + 1) + np.maximum(i, j))
+
+
+def _merge_rounds(C, size, csum, pairs, min_size, max_size):
+    """The merge rounds of enforce_connectivity over the fragments 1..C (size (C+1,), csum (C+1, nch) float64, pairs: the touching
+    codes) -> root (C+1,): every fragment's segment, named by the lowest fragment number in it."""
     root = np.arange(C + 1)
     while True:
         i, j = pairs // (C + 1), pairs % (C + 1)
@@ -110,8 +163,8 @@ def enforce_connectivity(labels, min_size, colour, max_size=None):
         root = to[root]
         size = np.bincount(to, weights=size, minlength=C + 1)
         csum = np.stack([np.bincount(to, weights=csum[:, k], minlength=C + 1) for k in range(csum.shape[1])], 1)
-        pairs = touching(to[i], to[j])
-    return raster_numbers(root[frag])[0].astype(np.int32)
+        pairs = _touching(to[i], to[j], C)
+    return root
 
 
 def slic_raw(img_u8, mask, sp_size, sp_regul, n_iter=10, device="cuda:0"):
@@ -135,14 +188,15 @@ def slic_raw(img_u8, mask, sp_size, sp_regul, n_iter=10, device="cuda:0"):
     return labels.cpu().numpy(), S
 
 
-def slic(img_u8, mask, sp_size, sp_regul, n_iter=10, device="cuda:0"):
+def slic(img_u8, mask, sp_size, sp_regul, n_iter=10, device="cuda:0", cc_device=None):
     """Masked SLIC superpixels of an (H,W,3) uint8 image (imsegm/superpixels.py:53-64 with the deterministic start of slic_geometry):
     (H,W) int32 labels, 0 outside the mask, 1..N inside, every superpixel 4-connected.  The pixel work runs on `device`; the
-    connectivity repair (fragments below half the mean segment size S^2 are merged away) on the host."""
+    connectivity repair (fragments below half the mean segment size S^2 are merged away) on the host, its per-pixel half on `cc_device`
+    when one is given (enforce_connectivity)."""
     img_u8 = as_u8(img_u8)
     mask = np.asarray(mask).reshape(img_u8.shape[:2]) > 0
     labels, S = slic_raw(img_u8, mask, sp_size, sp_regul, n_iter, device)
-    return enforce_connectivity(labels, 0.5 * S * S, img_u8)
+    return enforce_connectivity(labels, 0.5 * S * S, img_u8, cc_device=cc_device)
 
 
 def superpixel_features(img_u8, labels, device="cuda:0"):
@@ -369,13 +423,13 @@ def masks_from_classes(labels, classes, valid):
     return seg, period, non_period
 
 
-def initial_segmentation(img, valid_mask, nb_classes=3, sp_size=20, sp_regul=0.1, seed=0, device="cuda:0"):
+def initial_segmentation(img, valid_mask, nb_classes=3, sp_size=20, sp_regul=0.1, seed=0, device="cuda:0", cc_device=None):
     """The initial periodic / non-periodic masks of an image (loaders.py:162-205).  img (H,W,3) uint8 (or float in [0,1]), valid_mask
     (H,W[,1]) with > 0.5 = valid.  -> dict(period_mask, non_period_mask (H,W) bool, seg (H,W) uint8: 0 invalid, class + 1 elsewhere,
     slic (H,W) int32 superpixels, proba (N, nb_classes) per superpixel)."""
     img_u8 = as_u8(img)
     valid = np.asarray(valid_mask).reshape(img_u8.shape[:2]) > 0.5
-    sp = slic(img_u8, valid, sp_size, sp_regul, device=device)
+    sp = slic(img_u8, valid, sp_size, sp_regul, device=device, cc_device=cc_device)
     _, centroids, feats = superpixel_features(img_u8, sp, device=device)
     classes, proba = segment_superpixels(sp, feats, centroids, nb_classes, seed)
     seg, period, non_period = masks_from_classes(sp, classes, valid)

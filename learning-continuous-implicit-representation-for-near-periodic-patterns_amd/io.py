@@ -236,14 +236,15 @@ def blur_with_mask(img, mask, sigma=3):
 
 
 def load_npp_segmentation(datadir, p_topk=3, period_mask=None, non_period_mask=None, init_seg=None, nb_classes=3, sp_size=20,
-                          sp_regul=0.1, seed=0, device="cuda:0"):
+                          sp_regul=0.1, seed=0, device="cuda:0", cc_device=None):
     """loaders/loaders.py:141-239 -> dict(img, blur_img, period_mask (H,W,1), non_period_mask (H,W,1), valid_mask, shifts,
     angles, periods, patch_size, init_seg_source).  The INITIAL coarse segmentation (SLIC superpixels + GMM + graph cut through the
     reference's vendored imsegm package, loaders.py:162-205) comes from, in this order: the `period_mask` / `non_period_mask` arrays;
     with init_seg None (the default) or "auto", `period_mask.png` / `non_period_mask.png` (white = member) next to config.odgt; with
     init_seg "auto" when a PNG is missing, or always with "compute", init_segment.initial_segmentation(nb_classes, sp_size, sp_regul
     as options/arg_config.py:210-216; seed, device) -- this build's deterministic statement of that step, whose pixel work runs on
-    `device`.  init_seg None without arrays or PNGs raises FileNotFoundError.  `init_seg_source` says which it was: "arrays", "files"
+    `device` (cc_device: where its connectivity repair labels the fragments, init_segment.enforce_connectivity; None = the host).
+    init_seg None without arrays or PNGs raises FileNotFoundError.  `init_seg_source` says which it was: "arrays", "files"
     or "computed".  The rest follows the reference: the masked Gaussian blur of the image the fit trains on (:157-159), the top-k
     periodicity and the patch size rule (:232-236)."""
     if init_seg not in (None, "auto", "compute"):
@@ -268,7 +269,7 @@ def load_npp_segmentation(datadir, p_topk=3, period_mask=None, non_period_mask=N
         from PIL import Image
         from . import init_segment
         img_u8 = np.array(Image.open(info["fpath_gt_img"]).convert("RGB"))             # loaders.py:152: the 8-bit image itself
-        r = init_segment.initial_segmentation(img_u8, valid, nb_classes, sp_size, sp_regul, seed, device)
+        r = init_segment.initial_segmentation(img_u8, valid, nb_classes, sp_size, sp_regul, seed, device, cc_device=cc_device)
         period_mask, non_period_mask, source = r["period_mask"], r["non_period_mask"], "computed"
     else:
         source = "arrays" if period_mask is not None and non_period_mask is not None else "files"

@@ -1392,6 +1392,108 @@ def binary_morph(mask_u8, iterations, dilate):
     return out
 
 
+# ---- segmentation task: 4-connected components (include/npp_hip.h npp_cc_*; regions.py is the public face) ----------------------
+# Device tensors in, device tensors out; the *_host forms take and return NumPy arrays and never touch a GPU.  Scratch is allocated
+# per call and needs no initial content.
+CC_MAX_CHANNELS = 4
+
+
+def cc_label(labels):
+    """(H,W) int32 label image (0 = outside) -> (H,W) int32 roots: -1 outside, else the smallest row-major index of the pixel's
+    4-connected component of equal labels."""
+    _req(labels, torch.int32, "labels")
+    if labels.dim() != 2:
+        raise ValueError("labels: expected (H, W)")
+    H, W = labels.shape
+    root = torch.empty((H, W), dtype=torch.int32, device=labels.device)
+    check(lib().npp_cc_label(_p(labels), H, W, _p(root), _stream()), "npp_cc_label")
+    return root
+
+
+def cc_number(root):
+    """Roots (H,W) int32 -> (numbered (H,W) int32: 1..C in raster order of first appearance, 0 outside; C as a one-word int32 device
+    tensor)."""
+    _req(root, torch.int32, "root")
+    if root.dim() != 2:
+        raise ValueError("root: expected (H, W)")
+    H, W = root.shape
+    nbytes = check(lib().npp_cc_number_scratch_bytes(H, W), "npp_cc_number_scratch_bytes")
+    ws = torch.empty(int(nbytes) // 4, dtype=torch.int32, device=root.device)
+    numbered = torch.empty((H, W), dtype=torch.int32, device=root.device)
+    count = torch.empty(1, dtype=torch.int32, device=root.device)
+    check(lib().npp_cc_number(_p(root), H, W, _p(numbered), _p(count), _p(ws), int(nbytes), _stream()), "npp_cc_number")
+    return numbered, count
+
+
+def cc_stats(numbered, C_, values_u8=None):
+    """Per component 1..C_ of a numbered (H,W) int32 image -> sizes (C,) int64, sums (C,nch) int64 of the (H,W,nch) uint8 image
+    `values_u8` (None: nch = 0), border (C,) uint8 (1 = touches the image border), boxes (C,4) int32 (y0, x0, y1, x1 inclusive)."""
+    _req(numbered, torch.int32, "numbered")
+    if numbered.dim() != 2:
+        raise ValueError("numbered: expected (H, W)")
+    H, W = numbered.shape
+    nch = 0
+    if values_u8 is not None:
+        _req(values_u8, torch.uint8, "values_u8")
+        if values_u8.dim() != 3 or tuple(values_u8.shape[:2]) != (H, W) or not 1 <= values_u8.shape[2] <= CC_MAX_CHANNELS:
+            raise ValueError(f"values_u8: expected ({H}, {W}, 1..{CC_MAX_CHANNELS}), got {tuple(values_u8.shape)}")
+        nch = int(values_u8.shape[2])
+    C_ = int(C_)
+    dev = numbered.device
+    size = torch.empty(C_, dtype=torch.int64, device=dev)
+    sums = torch.empty((C_, nch), dtype=torch.int64, device=dev)
+    border = torch.empty(C_, dtype=torch.uint8, device=dev)
+    box = torch.empty((C_, 4), dtype=torch.int32, device=dev)
+    check(lib().npp_cc_stats(_p(numbered), H, W, C_, _p(values_u8), nch, _p(size), _p(sums), _p(border), _p(box), _stream()), "npp_cc_stats")
+    return size, sums, border, box
+
+
+def _np_ptr(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def cc_label_host(labels):
+    """cc_label on a NumPy (H,W) int32 array, by the library's host twin."""
+    labels = np.ascontiguousarray(labels, np.int32)
+    if labels.ndim != 2:
+        raise ValueError("labels: expected (H, W)")
+    root = np.empty(labels.shape, np.int32)
+    check(lib().npp_cc_label_host(_np_ptr(labels), labels.shape[0], labels.shape[1], _np_ptr(root)), "npp_cc_label_host")
+    return root
+
+
+def cc_number_host(root):
+    """cc_number on a NumPy array -> (numbered (H,W) int32, C int)."""
+    root = np.ascontiguousarray(root, np.int32)
+    if root.ndim != 2:
+        raise ValueError("root: expected (H, W)")
+    numbered = np.empty(root.shape, np.int32)
+    count = np.zeros(1, np.int32)
+    check(lib().npp_cc_number_host(_np_ptr(root), root.shape[0], root.shape[1], _np_ptr(numbered), _np_ptr(count)), "npp_cc_number_host")
+    return numbered, int(count[0])
+
+
+def cc_stats_host(numbered, C_, values_u8=None):
+    """cc_stats on NumPy arrays."""
+    numbered = np.ascontiguousarray(numbered, np.int32)
+    if numbered.ndim != 2:
+        raise ValueError("numbered: expected (H, W)")
+    H, W = numbered.shape
+    nch = 0
+    if values_u8 is not None:
+        values_u8 = np.asarray(values_u8)
+        if values_u8.dtype != np.uint8 or values_u8.ndim != 3 or values_u8.shape[:2] != (H, W) or not 1 <= values_u8.shape[2] <= CC_MAX_CHANNELS:
+            raise ValueError(f"values_u8: expected a uint8 ({H}, {W}, 1..{CC_MAX_CHANNELS}) array")
+        values_u8 = np.ascontiguousarray(values_u8)
+        nch = int(values_u8.shape[2])
+    C_ = int(C_)
+    size, sums = np.empty(C_, np.int64), np.empty((C_, nch), np.int64)
+    border, box = np.empty(C_, np.uint8), np.empty((C_, 4), np.int32)
+    check(lib().npp_cc_stats_host(_np_ptr(numbered), H, W, C_, _np_ptr(values_u8) if nch else None, nch, _np_ptr(size), _np_ptr(sums),
+                                  _np_ptr(border), _np_ptr(box)), "npp_cc_stats_host")
+    return size, sums, border, box
+
+
 # ---- quality report (include/npp_hip.h npp_ssim_map / npp_region_sums) ----------------------------------------------------------
 SSIM_WIN = 11           # window taps per axis; the map is (H - 10, W - 10)
 

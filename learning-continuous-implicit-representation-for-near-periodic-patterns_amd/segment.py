@@ -116,10 +116,15 @@ def remove_small_objects(mask, min_size=500):
     return keep[lab]
 
 
-def segmentation_eval(pred_img, blur_img, valid_mask, non_period_mask, alex, lins, l1_thresh=0.15, lpips_thresh=0.3, lpips_layers=1):
+def segmentation_eval(pred_img, blur_img, valid_mask, non_period_mask, alex, lins, l1_thresh=0.15, lpips_thresh=0.3, lpips_layers=1,
+                      final_mask="host"):
     """NPP_segmentation/train.py:337-393.  pred_img, blur_img (H,W,3) in [0,1]; valid_mask, non_period_mask (H,W,1).
-    -> dict(non_period_mask_final (H,W,1) int, l1_img, l1_mask, lpips_maps [layers])."""
+    -> dict(non_period_mask_final (H,W,1) int, l1_img, l1_mask, lpips_maps [layers]).  final_mask: where step 4 runs -- "host": every
+    layer's mask is copied to the host, SciPy fills the holes and removes the small objects; "gpu": the layers are combined on the
+    device, npp_amd.regions does both there and the final mask is copied once (the same mask)."""
     from scipy import ndimage
+    if final_mask not in ("host", "gpu"):
+        raise ValueError(f"final_mask: 'host' or 'gpu', not {final_mask!r}")
     dev = alex.device
     t = lambda a: torch.as_tensor(np.asarray(a, np.float32)).to(dev)                  # noqa: E731
     valid = t(valid_mask).permute(2, 0, 1)[None]
@@ -133,9 +138,17 @@ def segmentation_eval(pred_img, blur_img, valid_mask, non_period_mask, alex, lin
     for i in range(lpips_layers):
         lp_np = npm * maps[i]                                                           # only the non-periodic candidates
         period_i = (lp_np < lpips_thresh) & l1_mask                                     # :376-380
+        if final_mask == "gpu":
+            final = (~period_i)[0, 0] if final is None else final | (~period_i)[0, 0]
+            continue
         non_i = (~period_i)[0, 0].float().cpu().numpy()
         final = non_i if final is None else final + non_i
-    final = ndimage.binary_fill_holes(final > 0)                                        # :390-391
-    final = remove_small_objects(final[..., None].astype(bool), min_size=500).astype(int)   # :392-393, on the (H,W,1) array
+    if final_mask == "gpu":
+        from . import regions
+        final = regions.remove_small_objects(regions.fill_holes(final.contiguous(), dev), 500, dev)   # :390-393
+        final = final.cpu().numpy()[..., None].astype(int)
+    else:
+        final = ndimage.binary_fill_holes(final > 0)                                    # :390-391
+        final = remove_small_objects(final[..., None].astype(bool), min_size=500).astype(int)   # :392-393, on the (H,W,1) array
     return dict(non_period_mask_final=final, l1_img=(l1 * valid)[0, 0].cpu().numpy(), l1_mask=l1_mask[0, 0].cpu().numpy(),
                 lpips_maps=[(npm * m)[0, 0].cpu().numpy() for m in maps[:lpips_layers]])

@@ -35,6 +35,10 @@ def parse(argv=None):
     ap.add_argument("--blur_detection", default="host", choices=["host", "gpu"],
                     help="remapping: where the clear / blurry mask (NPP_remapping/blur_detection.py) is computed.  host: io.get_blur_map "
                          "(one batched LAPACK SVD per image row); gpu: npp_amd.blur on --device (the same mask)")
+    ap.add_argument("--components", default="host", choices=["host", "gpu"],
+                    help="segmentation: where the connected-component work runs -- the per-pixel half of the SLIC connectivity repair "
+                         "(init_segment.enforce_connectivity) and the hole filling / small-object removal of the final non-periodic mask.  "
+                         "host: SciPy (default); gpu: npp_amd.regions on --device (the same labels and masks)")
     ap.add_argument("--init_segmentation", default="auto", choices=["file", "auto", "compute"],
                     help="segmentation: where the initial periodic / non-periodic masks (loaders.py:162-205) come from.  file: "
                          "period_mask.png / non_period_mask.png next to config.odgt; compute: npp_amd.init_segment (SLIC superpixels on "
@@ -186,7 +190,7 @@ def _plan(argv=None):
         # (the masks are computed here, not in _build: they are part of the loaded data, and no directory is needed for them)
         d = nio.load_npp_segmentation(args.datadir, args.p_topk, init_seg=None if args.init_segmentation == "file" else args.init_segmentation,
                                       nb_classes=args.nb_classes, sp_size=args.sp_size, sp_regul=args.sp_regul, seed=args.seed,
-                                      device=args.device)
+                                      device=args.device, cc_device=args.device if args.components == "gpu" else None)
         d["mask"], d["masked_img"] = d["period_mask"], d["blur_img"]
     else:
         # --normalize_type 2: tanh output; the reference rescales only the evaluation image (loaders.py:111), training stays on
@@ -482,7 +486,8 @@ def _after_iteration(job, i):
             alex = segment.AlexFeatures(load(args.alexnet), device=args.device)
             lins = weights.lpips_lin("alex", args.lpips_alex_lin)
             r = segment.segmentation_eval(pred * d["valid_mask"], d["blur_img"], d["valid_mask"], d["non_period_mask"], alex, lins,
-                                          args.l1_thresh, args.lpips_thresh, args.lpips_layers)
+                                          args.l1_thresh, args.lpips_thresh, args.lpips_layers,
+                                          final_mask="gpu" if args.components == "gpu" else "host")
             tdir = os.path.join(outroot, f"testset_{i:06d}")
             import matplotlib
             matplotlib.use("Agg")
