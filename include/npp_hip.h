@@ -325,6 +325,16 @@ int npp_adam_step_dev(float* d_p, float* d_m, float* d_v, const float* d_gslabs,
                       int n_slabs, int64_t slab_stride, float beta1, float beta2, float eps,
                       const float* d_hp, void* stream);
 
+/* npp_adam_step_net_pack with step_size = lr / (1 - b1^t) and 1 / sqrt(1 - b2^t) read from device memory (d_hp[0], d_hp[1]):
+ * optimizer.step() of NPP_completion/train.py:253 with the LR rule of :257-263 applied by whoever writes the two words (the
+ * host, in the double arithmetic of npp_adam_step_net_pack) -- the form a captured HIP graph of one optimisation iteration
+ * replays (fit.CompletionFit(graph_iteration=True)).  Same kernel, same bits as the argument form for equal words. */
+int npp_adam_step_net_pack_dev(float* d_p, float* d_m, float* d_v, const float* d_gslabs, int64_t n,
+                               int n_slabs, int64_t slab_stride, float* d_lat, float* d_lat_m,
+                               float* d_lat_v, float* d_dlat, int n_lat, float* d_zero, int n_zero,
+                               float beta1, float beta2, float eps, const float* d_hp, int K, int width,
+                               void* d_wf, void* d_wb, float* d_pl_partials, float* d_loss_cur, void* stream);
+
 /* ---- a9/a10: patch crops ---------------------------------------------------- */
 /* Replaces extract_glimpse(..., mode='nearest', padding_mode='zeros', normalized=False,
  * centered=False) as models/sampler.py:171-178,284-291 calls it (utils/extract_glimpse.py:
@@ -377,7 +387,8 @@ int npp_cx_fwd_bwd(const float* d_fx, const float* d_fy, int N, int C, int hw, f
  * d_dlatent [2C] (accumulated) may both be NULL for forward only.  C in {16, 32, 64, 128, 192,
  * 256, 384, 512}.  d_workspace: npp_lpips_workspace_bytes(C) bytes, ZEROED once by the caller and owned by one
  * stream -- the latent gradients and the loss are then summed over the launch's blocks as fixed-point integers
- * (order-independent, bit-reproducible); NULL: float atomics in arrival order.
+ * (order-independent, bit-reproducible); NULL: float atomics in arrival order.  A grouped launch (npp_lpips_layers) with
+ * workspaces adds the taps' totals to d_loss[0] in tap order, as ONE addend, from slots behind tap 0's accumulators.
  * d_latents == NULL: the PLAIN head, LPIPS.forward(use_robust=False) (lpips.py:108-109: diffs = (feats0 - feats1)^2) -- the in-loop
  * form under --use_adaptive_perceptual_loss off (train.py:241-251) -- with its gradient d_df0 (d_spline, d_dlatent NULL). */
 int64_t npp_lpips_workspace_bytes(int C);

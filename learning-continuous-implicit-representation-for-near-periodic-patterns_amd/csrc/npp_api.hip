@@ -139,6 +139,9 @@ struct AdamPackArgs {
   int64_t blob_stride, slab_img_stride, wf_stride, wb_stride;      // floats, floats, bf16 elements, bf16 elements
   int32_t lat_stride, zero_stride;                                 // floats
   int64_t pl_stride;
+  // device-word form (npp_adam_step_net_pack_dev): step_size and 1 / sqrt(1 - b2^t) from hp[0], hp[1] -- a captured launch
+  // replays with the values of the current step
+  const float* hp;
 };
 
 __global__ __launch_bounds__(256) void adam_pack_kernel(AdamPackArgs a_in, NetDesc d_arg, BwdDesc b_arg) {
@@ -156,6 +159,7 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(AdamPackArgs a_in, NetDe
     if (a.tail.pl_part) a.tail.pl_part += y * a.pl_stride;
     if (a.tail.loss_cur) a.tail.loss_cur += y * a.zero_stride;
   }
+  if (a.hp) { a.step_size = a.hp[0]; a.inv_sqrt_bc2 = a.hp[1]; }
   // the descriptors are indexed with per-lane layer numbers: LDS copies (filled with compile-time indices, so that the
   // by-value kernel arguments never need a scratch copy)
   __shared__ NetDesc d;
@@ -487,6 +491,32 @@ int npp_adam_step_net_pack(float* d_p, float* d_m, float* d_v, const float* d_gs
   hipLaunchKernelGGL(adam_pack_kernel, dim3((unsigned)((threads + 255) / 256 + 1)), dim3(256), 0, (hipStream_t)stream, a, d,
                      make_bwd_desc(K));
   return check_launch("npp_adam_step_net_pack");
+}
+
+int npp_adam_step_net_pack_dev(float* d_p, float* d_m, float* d_v, const float* d_gslabs, int64_t n, int n_slabs,
+                               int64_t slab_stride, float* d_lat, float* d_lat_m, float* d_lat_v, float* d_dlat, int n_lat,
+                               float* d_zero, int n_zero, float beta1, float beta2, float eps, const float* d_hp, int K,
+                               int width, void* d_wf, void* d_wb, float* d_pl_partials, float* d_loss_cur, void* stream) {
+  int rc = check_kw(K, width);
+  if (rc) return rc;
+  const NetDesc d = make_desc(K);
+  if (n != d.total_params || !d_p || !d_m || !d_v || !d_gslabs || !d_wf || !d_wb || !d_hp || n_slabs < 1 || n_lat < 0 ||
+      n_zero < 0 || (n_lat > 0 && (!d_lat || !d_lat_m || !d_lat_v || !d_dlat)) || (n_zero > 0 && !d_zero) || slab_stride % 4 ||
+      (((uintptr_t)d_p | (uintptr_t)d_m | (uintptr_t)d_v | (uintptr_t)d_gslabs) & 15) || ((uintptr_t)d_hp & 3)) {
+    set_error("npp_adam_step_net_pack_dev: bad arguments (n=%lld, expected %lld parameters; 16-byte aligned blobs, slab stride %% 4 == 0)",
+              (long long)n, (long long)d.total_params);
+    return NPP_ERR_ARG;
+  }
+  AdamPackArgs a{};
+  a.p = d_p; a.m = d_m; a.v = d_v; a.g = d_gslabs; a.n = n; a.n_slabs = n_slabs; a.slab_stride = slab_stride;
+  a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.hp = d_hp;
+  a.tail = AdamTail{d_lat, d_lat_m, d_lat_v, d_dlat, n_lat, d_zero, n_zero, d_pl_partials, d_loss_cur};
+  a.wf = (__bf16*)d_wf; a.wb = (__bf16*)d_wb;
+  for (int l = 0; l < kNumLayers; ++l) a.magic[l] = d.present[l] ? (uint32_t)((1ull << 32) / (uint64_t)d.n_in[l]) + 1u : 0u;
+  const int64_t threads = (n + 3) / 4;
+  hipLaunchKernelGGL(adam_pack_kernel, dim3((unsigned)((threads + 255) / 256 + 1)), dim3(256), 0, (hipStream_t)stream, a, d,
+                     make_bwd_desc(K));
+  return check_launch("npp_adam_step_net_pack_dev");
 }
 
 int npp_adam_step_net_pack_stack(float* d_p, float* d_m, float* d_v, int64_t blob_stride, const float* d_gslabs, int64_t n,

@@ -42,6 +42,7 @@ struct LpTap {
   // npp_trunk_grad_in(df0, NULL, ...) would make of df0 in a launch of its own (the tap gradient the backward pass adds in)
   __bf16* dflat; int64_t flat_nposp; int32_t fW, fS;      // fW = W, fS = (H + 2) (W + 2)
   const _Float16* yact;                                    // optional ReLU gate of the tapped layer itself: dflat *= [yact > 0]
+  unsigned long long* sum;                                 // grouped launch with workspaces: the launch's loss slots (lp_add_loss)
 };
 constexpr int kLpMaxTaps = 5;
 struct LpMulti {
@@ -52,9 +53,28 @@ struct LpMulti {
 // LDS of one tap's block (dynamic: the taps of a grouped launch differ): red[3][CL][PL + 1] | tot[4] | sdl[2 C] | slin[C] | scp[C]
 constexpr int lp_smem_bytes(int C, int PL) { return (3 * (256 / PL) * (PL + 1) + 4 + 3 * C) * 4 + C * (int)sizeof(LpChan); }
 
+// The loss word of a GROUPED launch (fixed-order form): every tap's last arriver leaves its float total in the launch's slots --
+// sum[0] = tap ticket, sum[1 + tap] = the tap's total, in tap 0's workspace behind its own accumulators -- and the last TAP to finish
+// adds them in tap order and accumulates the sum into the loss word ONCE.  The taps used to add one by one as they finished: five
+// float atomics in arrival order, next to the contextual branch's add from its own stream -- the last bit of the patch-loss word of
+// a 'same' iteration moved with the timing of the two streams (seen: a launch-by-launch LPIPS branch against its graph replay,
+// 1 ulp).  Two addends commute; six do not.
+__device__ __forceinline__ void lp_add_loss(unsigned long long* sum, int n_taps, float* loss, float v) {
+  if (n_taps <= 1 || !sum) { atomicAdd(loss, v); return; }
+  __hip_atomic_store(sum + 1 + blockIdx.y, (unsigned long long)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __threadfence();
+  if (__hip_atomic_fetch_add(sum, 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) != (unsigned long long)(n_taps - 1)) return;
+  __threadfence();
+  float s = 0.0f;
+  for (int q = 0; q < n_taps; ++q)
+    s += __uint_as_float((unsigned)__hip_atomic_load(sum + 1 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  __hip_atomic_store(sum, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  atomicAdd(loss, s);
+}
+
 template <int Q, int PL>
 __device__ __forceinline__ void lpips_layer_body(const LpTap& T, int N, const float* __restrict__ spline, int n_knots, float x_scale,
-                                                 float* __restrict__ loss, char* smem, int bid, int nb) {
+                                                 float* __restrict__ loss, char* smem, int bid, int nb, int n_taps) {
   constexpr int CL = 256 / PL, C = CL * Q;
   const float* __restrict__ f0 = T.f0;
   const float* __restrict__ f1 = T.f1;
@@ -232,7 +252,7 @@ __device__ __forceinline__ void lpips_layer_body(const LpTap& T, int N, const fl
     for (int i = threadIdx.x; i <= 2 * C; i += 256) {
       const long long s = (long long)__hip_atomic_exchange(fix + i, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const float v = (float)((double)s * (i == 2 * C ? 1.0 / kFixLoss : 1.0 / kFixLat));
-      if (i == 2 * C) atomicAdd(loss, v);                    // (the contextual branch adds to the same word from its own stream)
+      if (i == 2 * C) lp_add_loss(T.sum, n_taps, loss, v);            // (the contextual branch adds to the same word from its own stream)
       else if (grad && !plain) dlatent[i] += v;
     }
     return;
@@ -261,7 +281,7 @@ __global__ __launch_bounds__(256, MAXQ <= 8 ? NPP_LP_MINBLOCKS : 1) void lpips_m
     if (q == y) T = m.t[q];
   const int bid = blockIdx.x;
   if (bid >= T.nb) return;                                 // (whole block: no barrier is skipped)
-#define NPP_LP_CASE(Q, PL) lpips_layer_body<Q, PL>(T, m.N, m.spline, m.n_knots, m.x_scale, m.loss, lp_smem, bid, T.nb)
+#define NPP_LP_CASE(Q, PL) lpips_layer_body<Q, PL>(T, m.N, m.spline, m.n_knots, m.x_scale, m.loss, lp_smem, bid, T.nb, m.n_taps)
   if (T.few) {
     switch (T.C) {
       case 64: NPP_LP_CASE(1, 4); break;
@@ -290,8 +310,9 @@ __global__ __launch_bounds__(256, MAXQ <= 8 ? NPP_LP_MINBLOCKS : 1) void lpips_m
 
 using namespace npp;
 
-// 2 C + 1 fixed-point accumulators + the ticket counter (8 bytes each); zeroed once by the caller, owned by one stream
-extern "C" int64_t npp_lpips_workspace_bytes(int C) { return (int64_t)(2 * C + 2) * 8; }
+// 2 C + 1 fixed-point accumulators + the ticket counter + the loss slots of a grouped launch (lp_add_loss: tap ticket + one total
+// per tap, used in tap 0's workspace), 8 bytes each; zeroed once by the caller, owned by one stream
+extern "C" int64_t npp_lpips_workspace_bytes(int C) { return (int64_t)(2 * C + 2 + 1 + kLpMaxTaps) * 8; }
 
 static int lp_fill(LpTap& T, const float* f0, const float* f1, int N, int C, int hw, const float* lin, const float* latents, float scale,
                    float* df0, float* dlatent, void* ws, const char* who, void* dflat = nullptr, int N_total = 0, int H = 0, int W = 0,
@@ -380,6 +401,8 @@ extern "C" int npp_lpips_layers(int n_taps, const npp_lpips_tap* taps, int N, co
                      t.dflat, t.N_total, t.H, t.W, t.yact);
     if (rc) return rc;
   }
+  if (m.t[0].fix)                                          // (workspaces: all taps or none -- the fixed-order forms)
+    for (int i = 0; i < n_taps; ++i) m.t[i].sum = m.t[i].fix ? m.t[0].fix + 2 * m.t[0].C + 2 : nullptr;
   m.spline = d_spline; m.loss = d_loss; m.n_taps = n_taps; m.N = N; m.n_knots = n_knots; m.x_scale = x_scale;
   return lp_launch(m, stream, "npp_lpips_layers");
 }

@@ -31,6 +31,24 @@ def _hand_over(v, stream):
             _hand_over(x, stream)
 
 
+def refuse_graph_iteration(precision, trunk_precision, task, style_weight, exc, flag=False):
+    """graph_iteration is built for the default arithmetic of the completion and segmentation tasks: everything else is refused by
+    name (exc: ValueError for the constructor, SystemExit for the command line; flag: name the switches as flags)."""
+    a = (lambda k, v: f"--{k} {v}") if flag else (lambda k, v: f"{k}={v!r}")
+    me = "--graph_iteration" if flag else "graph_iteration=True"
+    if precision != "bf16":
+        raise exc(f"{me} with {a('precision', precision)}: the exact-fp32 chain is a diagnostic mode and runs launch by launch "
+                  f"(precision 'bf16' only)")
+    if trunk_precision != "fp16":
+        raise exc(f"{me} with {a('trunk_precision', trunk_precision)}: the exact-fp32 trunks are a diagnostic mode and run launch by "
+                  f"launch (trunk_precision 'fp16' only)")
+    if task == "remapping":
+        raise exc(f"{me} with {a('task', task)}: the style head still allocates per iteration and its side-stream question is open "
+                  f"(DESIGN.md section 4); completion and segmentation only")
+    if style_weight is not None:
+        raise exc(f"{me} with {a('style_weight', style_weight)}: the style term is not built into the captured iteration")
+
+
 class CompletionFit:
     def __init__(self, img, mask, angles_deg, periods, freqs, params, device="cuda", N_rand=8192,
                  ksplit=None, seed=0, lrate=5e-4, lrate_decay=500, valid_mask=None, shifts=None,
@@ -40,7 +58,7 @@ class CompletionFit:
                  prefetch=0, use_perceptual_loss=True, task="completion", clear_mask=None, style_weight=None,
                  vgg16_style_state_dict=None, masked_img=None, width=256, no_reg_sampling=False, use_patch_weight=False,
                  no_pix_loss=False, use_contextual_loss=True, loss_type="robust_loss_adaptive", use_adaptive_perceptual_loss=True, normalize_type=1,
-                 precision="bf16", trunk_precision="fp16"):
+                 precision="bf16", trunk_precision="fp16", graph_iteration=False):
         """img (H,W,3) float in [0,1]; mask (H,W,1) 1 = known (loaders.py:92-101).
         precision: the arithmetic of the coordinate MLP's training launches, 'bf16' (default) or 'fp32' (NPPNet(precision=...): the
         exact fp32 chain, the reference's own arithmetic; the iteration then takes the unfolded launch sequence -- fold_launches =
@@ -69,7 +87,11 @@ class CompletionFit:
         overlap the training loop instead of preceding it.
         "device" draws on the GPU (dev_sampler.DeviceDraws; models/sampler.py:242-354 and train.py:172 as two launches on the
         sampler stream): Philox4x32-10 keyed by `seed`, every draw a pure function of (seed, draw index) -- its own stream, the
-        same distribution; no host arithmetic per draw, so no producer thread (prefetch must be 0)."""
+        same distribution; no host arithmetic per draw, so no producer thread (prefetch must be 0).
+        graph_iteration: True replays the device side of an iteration (step_from) as ONE captured HIP graph per iteration shape
+        instead of enqueuing its launches (_step_from_graph): the bits of the launch-by-launch loop at one graph launch of host
+        time per iteration.  Built for the default arithmetic (precision='bf16', trunk_precision='fp16') of the completion and
+        segmentation tasks without a style term; the other modes are refused by name."""
         if rng_mode not in ("reference", "numpy", "fast", "device"):
             raise ValueError("rng_mode must be 'reference', 'numpy', 'fast' or 'device'")
         if rng_mode == "device" and int(prefetch) > 0:
@@ -82,6 +104,9 @@ class CompletionFit:
         self.trunk_precision = trunk_precision
         if task not in ("completion", "remapping", "segmentation"):
             raise ValueError("task must be 'completion', 'remapping' or 'segmentation'")
+        self.graph_iteration = bool(graph_iteration)
+        if self.graph_iteration:
+            refuse_graph_iteration(precision, trunk_precision, task, style_weight, ValueError)
         # False: the folded launches as separate ones (npp_pixel_loss, npp_patch_compose_bwd: the comparator of
         # tests/test_gpu_parity.py::test_folded_launches_equal_the_separate_ones).  Measured and removed in round 5 (they are in the
         # history of rounds 3-4, profiles/r03_rejected_experiments.txt #2 #5): the pixel rows as a row group of their own on a side
@@ -176,6 +201,23 @@ class CompletionFit:
             self._lp_graphs, self.lp_graph = {}, trunk_precision == "fp16"
             self._s_lp = torch.cuda.Stream(self.device)
             self.patch_loss_buf = torch.zeros(1, dtype=torch.float32, device=self.device)
+        # ---- graph_iteration (see _step_from_graph): captured iterations by key, the two sets of batch buffers per batch shape, the
+        # scalar record (device words + a small ring of pinned words, each guarded by the event behind the iteration that read it)
+        self._it_graphs, self._it_stats, self._graph_ok = {}, {"captured": 0, "replayed": 0, "eager": 0}, True
+        self._sets, self._wset, self._it_shape, self._s_it = {}, 0, None, None
+        if self.graph_iteration:
+            self._rec = torch.zeros(4, dtype=torch.float32, device=self.device)
+            self._rec_pin = torch.zeros((self._REC_SLOTS, 4), dtype=torch.float32).pin_memory()
+            self._rec_np, self._rec_ev, self._rec_i = self._rec_pin.numpy(), [None] * self._REC_SLOTS, 0
+
+    _REC_SLOTS = 32           # pinned copies of the scalar record in flight (the host may enqueue that many iterations ahead)
+    MAX_ITER_GRAPHS = 40      # live captured iterations (3 sources x 3 k x 2 buffer sets x 2 loss accumulators at most per shape)
+
+    @property
+    def graph_stats(self):
+        """graph_iteration: {"captured": graphs captured so far, "replayed": iterations run as a graph replay, "eager": iterations run
+        launch by launch (the first uses of a key, keys met while no capture is possible)}; skipped iterations count nowhere."""
+        return dict(self._it_stats)
 
     def lpips_branch(self, xy, nk, scale, loss_buf):
         """percepLoss.fused(xy, nk, scale, loss_buf) on the CURRENT stream (the loop's side stream).  The branch is 46 launches at the
@@ -210,7 +252,7 @@ class CompletionFit:
             except Exception as e:                             # a runtime that cannot capture: stay eager, say so once
                 import warnings
                 warnings.warn(f"npp_amd.fit: LPIPS branch not captured as a HIP graph ({e}); keeping the launch-by-launch form")
-                self.lp_graph = False
+                self.lp_graph = self._graph_ok = False            # (nor a whole iteration: graph_iteration stays launch by launch, too)
                 return out
             self._lp_graphs[key] = (g, gout, uses)
         return out
@@ -341,8 +383,16 @@ class CompletionFit:
             ev = torch.cuda.Event()
             ev.record(dd.stream)
             dd.launch_ahead()
-        _hand_over(b, main)
+        self._hand_over_batch(b, main)
         return d, b, ev
+
+    def _hand_over_batch(self, b, main):
+        st = None if b is None else b.get("set")
+        if st is None:
+            _hand_over(b, main)
+        elif not st["handed"]:                                    # persistent buffers (graph_iteration): once, not per iteration
+            _hand_over([v for v in st.values() if isinstance(v, torch.Tensor)], main)
+            st["handed"] = True
 
     def _next_draw(self):
         d = self._queue.get()
@@ -363,7 +413,7 @@ class CompletionFit:
             b = self.materialise_batch(d)
             ev = torch.cuda.Event()
             ev.record(self._s_smp)
-        _hand_over(b, main)
+        self._hand_over_batch(b, main)
         return d, b, ev
 
     def decay_due(self):
@@ -414,6 +464,9 @@ class CompletionFit:
         #  8-tuple would cost two more launches per iteration)
         if d["k"] == 0:
             return None
+        st = None
+        if out is None and self.graph_iteration:                  # a captured iteration reads its batch at fixed addresses
+            st = out = self._batch_set(d)
         # ONE host -> device transfer per iteration: [pixel-row indices (int64) | patch centres (int32)] through one pinned block
         if d.get("device"):                                       # rng_mode "device": both are where the launches wrote them
             pix_dev, cen_dev = d["pix"], d["cen_dev"]
@@ -438,7 +491,9 @@ class CompletionFit:
         if self.use_patch_weight and d["weights"] is not None:
             # (device draws: the record's weights, copied out of the record ring on the sampler stream)
             w_dev = d["w_dev"].clone() if d.get("device") else ops.h2d(np.ascontiguousarray(d["weights"], np.float32), self.device)
-        return dict(coords=allc, n_pix=n_pix, n=n, bp=bp, gt=gt, source=source, k=k, P=P, n_p=d["n_p"],
+            if st is not None:
+                w_dev = st["weight"][:w_dev.numel()].copy_(w_dev.reshape(-1)).view(w_dev.shape)
+        return dict(set=st, coords=allc, n_pix=n_pix, n=n, bp=bp, gt=gt, source=source, k=k, P=P, n_p=d["n_p"],
                     raw=self.patch_sampler.last_raw, pmask=pm, weight=w_dev)
 
     def sample_batch(self):
@@ -481,19 +536,37 @@ class CompletionFit:
         -> contextual loss core -> trunk data-gradient (-> the same through VGG16 / LPIPS head on 'same' iterations)
         -> npp_patch_compose_bwd -> backward chain + wgrad -> Adam."""
         ops.check_current(self.device)
-        self.last_source = source = b["source"]
-        net, P, n_p, k, n_pix, n, bp = self.net, b["P"], b["n_p"], b["k"], b["n_pix"], b["n"], b["bp"]
-        raw = b["raw"]
-        comp = self.use_comp and source == "val"                 # train.py:230-231
-        nk = n_p * k
+        if self.graph_iteration:
+            return self._step_from_graph(b)
+        self._select_xy(b["n_p"] * b["k"], b["P"])
+        self.net.zero_grad()
+        if self.percepLoss.touched:
+            self.percepLoss.zero_latent_grads()
+        self._launch_iteration(b)
+
+    def _select_xy(self, nk, P):
         key = (nk, P)
         if self._xy_key != key:                                   # one fp32 batch buffer per (n_p k, P): fixed addresses (see lpips_branch)
             if key not in self._xy_bufs:
                 if len(self._xy_bufs) >= 8:                       # (the patch size changes every patch_size_decay iterations)
                     self._xy_bufs.clear()
                     self._lp_graphs.clear()
+                    self._drop_graphs()                           # (captured iterations hold the buffers' addresses too)
                 self._xy_bufs[key] = torch.empty((2 * nk, 3, P, P), dtype=torch.float32, device=self.device)
             self._xy, self._xy_key = self._xy_bufs[key], key
+
+    def _launch_iteration(self, b, hp=None, capture=False):
+        """The launches of one iteration behind zero_grad(), on the current stream (+ the LPIPS side stream).  hp None: the loop's
+        form -- step-dependent scalars as kernel arguments, the host's counters advanced on the way.  hp = the scalar record on the
+        device (graph_iteration): the same launches with the optimisers' scalars read from hp[0:2] (network + pixel-loss latents)
+        and hp[2:4] (LPIPS latents) and NO step counter touched -- what a capture records (capture=True: the LPIPS branch as its
+        launches, too; outside a capture it goes through lpips_branch exactly as in the loop's form: a launch-by-launch iteration
+        of a graph-mode fit is the eager iteration launch for launch)."""
+        self.last_source = source = b["source"]
+        net, P, n_p, k, n_pix, n, bp = self.net, b["P"], b["n_p"], b["k"], b["n_pix"], b["n"], b["bp"]
+        raw = b["raw"]
+        comp = self.use_comp and source == "val"                 # train.py:230-231
+        nk = n_p * k
         with_lp = source == "same" and self.use_perceptual_loss
         cx = self.contextualLoss
         xy = self._xy if (with_lp or self.style is not None) else None      # fp32 batch only when another trunk reads it
@@ -504,9 +577,6 @@ class CompletionFit:
         fold_bwd = self.fold_launches
         if t32:
             xy = self._xy                                         # the fp32 batch is what the fp32 trunks read
-        net.zero_grad()
-        if self.percepLoss.touched:
-            self.percepLoss.zero_latent_grads()
         ws = net.workspace(bp)
         pred = net.forward_train(b["coords"])
         if ws.get("n_rows") != n:                                # rows >= n never receive a gradient
@@ -542,7 +612,12 @@ class CompletionFit:
         if with_lp:                                                                                 # train.py:241-250
             self._s_lp.wait_stream(main)
             with torch.cuda.stream(self._s_lp):
-                dx_b = self.lpips_branch(xy, nk, self.lp_w * (nk if weight is not None else 1), self.patch_loss_buf)
+                if not capture:
+                    dx_b = self.lpips_branch(xy, nk, self.lp_w * (nk if weight is not None else 1), self.patch_loss_buf)
+                else:                                             # (inside a capture the branch is recorded as its launches, not as
+                    #                                               a replay of its own graph)
+                    dx_b = self.percepLoss.fused(xy, nk, self.lp_w * (nk if weight is not None else 1), self.patch_loss_buf,
+                                                 normalize=True, use_robust=self.lp_robust)
         # the backward chain that follows streams this pack: requested into L2 early (bf16 chain only)
         cx.hip_trunk.final_next_pack = net.wb if net.precision == "bf16" else None
         if self.use_contextual_loss and t32:
@@ -559,6 +634,12 @@ class CompletionFit:
             dx_b = dx_s if dx_b is None else dx_b.add_(dx_s)
         self.last_patch_loss = self.patch_loss_buf
         lr_used = net.lr
+        if hp is not None:                                        # (graph_iteration: bf16 MLP, fp16 trunks, folded launches, no style term)
+            net.backward(bp, patch=(dx_a, dx_b, raw["fmask"], raw["rmask"], n_pix, n_p, k, P, comp))
+            net.optimizer_launch_dev(bp, hp[0:2])
+            if self.percepLoss.touched:
+                self.percepLoss.adam_launch_dev(hp[2:4])
+            return
         # npp_patch_compose_bwd folded into the backward launch: dL/dpred of the patch rows is formed (and written) there
         if fold_bwd:
             net.backward(bp, patch=(dx_a, dx_b, raw["fmask"], raw["rmask"], n_pix, n_p, k, P, comp))
@@ -571,6 +652,125 @@ class CompletionFit:
             self.percepLoss.adam_step(lr_used)
         if self.style is not None:                                # the style latents are in the same optimiser (helpers.py:153-159)
             self.style.adam_step(lr_used)
+
+    # ---- graph_iteration: the device side of an iteration as one captured HIP graph --------------------------------------
+    def _batch_set(self, d):
+        """The persistent buffers the next batch is materialised into (materialise_batch(out=...), the StackedFit form).  Two sets
+        per batch shape where the sampler's device half runs an iteration ahead on its own stream (producer thread, device draws):
+        the stream that fills a set first waits for the iteration that read it last.  One set where the batch is formed on the
+        loop's own stream, in order.  The sets of an earlier patch size stay allocated (a fit sees three sizes at most)."""
+        P, n_p, n_pix = d["P"], d["n_p"], self.N_rand
+        sets = self._sets.get((P, n_p))
+        if sets is None:
+            bp, nc, dev, f32 = ops.pad_rows(n_pix + n_p * P * P), n_p * (1 + self.topk), self.device, torch.float32
+            sets = self._sets[(P, n_p)] = [dict(
+                idx=i, coords=torch.zeros((bp, 2), dtype=torch.int32, device=dev), gt=torch.zeros((n_pix, 3), dtype=f32, device=dev),
+                crops=torch.zeros((nc, 3, P, P), dtype=f32, device=dev), cmasks=torch.zeros((nc, 1, P, P), dtype=f32, device=dev),
+                weight=torch.zeros(n_p * self.topk, dtype=f32, device=dev), free=None, handed=False) for i in range(2)]
+        ahead = self.rng_mode == "device" or (self._prefetch > 0 and self.side_sampler)
+        st = sets[self._wset if ahead else 0]
+        if ahead:
+            self._wset ^= 1
+            if st["free"] is not None:
+                torch.cuda.current_stream(self.device).wait_event(st["free"])
+        return st
+
+    def _drop_graphs(self, keep=None):
+        """Release captured iterations (all, or those `keep` rejects) with their private pools -- behind everything enqueued."""
+        gone = [k for k in self._it_graphs if keep is None or not keep(k)]
+        if any(self._it_graphs[k][0] is not None for k in gone):
+            torch.cuda.synchronize(self.device)
+        for k in gone:
+            del self._it_graphs[k]
+
+    def _step_from_graph(self, b):
+        """step_from() of graph_iteration=True.  A stream capture cannot begin on the default stream: called there, the iteration
+        runs on a stream of the fit's own, joined on both sides (a loop that wants the bare graph launch runs under
+        torch.cuda.stream(...), as train.py does)."""
+        main = torch.cuda.current_stream(self.device)
+        if main != torch.cuda.default_stream(self.device):
+            return self._graph_iteration(b, main)
+        if self._s_it is None:
+            self._s_it = torch.cuda.Stream(self.device)
+        self._s_it.wait_stream(main)
+        with torch.cuda.stream(self._s_it):
+            self._graph_iteration(b, self._s_it)
+        main.wait_stream(self._s_it)
+
+    def _graph_iteration(self, b, stream):
+        """One iteration on `stream` (not the default stream): what alternates or changes from step to step stays OUTSIDE the graph --
+        zero_grad()'s switch of the loss accumulator (a host index: the accumulator is part of the key), the fill of the LPIPS
+        latents' gradient after a 'same' iteration, the dpred tail rule, and the scalar record: (step_size, 1 / sqrt(1 - b2^t)) of
+        the network's and of the LPIPS latents' optimiser, computed on the host exactly as the argument forms of the launches do
+        (ops.adam_words) and copied into four device words in front of the replay.  Then ONE replay of the graph of this key -- or,
+        for the first two uses of a key, the same launches eagerly (_launch_iteration(hp=record)); the second use also captures
+        them (a capture only records).  Afterwards the host's counters are advanced once, as the eager loop leaves them."""
+        net, lp, cx = self.net, self.percepLoss, self.contextualLoss.hip_trunk
+        source, P, n_p, k, n, bp = b["source"], b["P"], b["n_p"], b["k"], b["n"], b["bp"]
+        nk = n_p * k
+        if self._it_shape != (P, n_p):                            # patch-size decay: the graphs of the old shape go
+            self._drop_graphs(keep=lambda key: key[0] == (P, n_p))
+            self._it_shape = (P, n_p)
+        self._select_xy(nk, P)
+        net.zero_grad()
+        if lp.touched:
+            lp.zero_latent_grads()
+        ws = net.workspace(bp)
+        if ws.get("n_rows") != n:                                # rows >= n never receive a gradient
+            ws["dpred"][n:].zero_()
+            ws["n_rows"] = n
+        with_lp = source == "same" and self.use_perceptual_loss
+        comp = self.use_comp and source == "val"
+        # ---- the scalar record
+        i = self._rec_i
+        self._rec_i = (i + 1) % self._REC_SLOTS
+        if self._rec_ev[i] is not None:
+            self._rec_ev[i].synchronize()                         # (long complete unless the host runs _REC_SLOTS iterations ahead)
+        w = self._rec_np[i]
+        w[0], w[1] = net.step_words()
+        w[2], w[3] = lp.step_words(net.lr)
+        self._rec.copy_(self._rec_pin[i], non_blocking=True)
+        # ---- every address and scalar a captured launch holds: shape, k, source (-> comp, LPIPS branch), buffer set, loss accumulator,
+        # fp32 batch buffer, stream (per-stream workspaces), and the switches lpips_branch's key carries
+        st = b["set"]
+        key = ((P, n_p), k, source, comp, with_lp, st["idx"], st["coords"].data_ptr(), net._loss_idx, self._xy.data_ptr(), ws["pred"].data_ptr(),
+               b.get("weight") is not None, self.lp_robust, lp._lat.data_ptr(), lp.grouped_heads, lp.flat_tap_grads,
+               int(lp.hip_trunk.fuse_pairs), lp.hip_trunk.fold_pool_bwd, lp.hip_trunk.fold_pool_fwd, int(cx.fuse_pairs), cx.fold_pool_bwd,
+               cx.fold_pool_fwd, ops.DETERMINISTIC, stream.cuda_stream)
+        ent = self._it_graphs.get(key)
+        if ent is not None and ent[0] is not None:
+            ent[0].replay()
+            self._it_stats["replayed"] += 1
+            self.last_source, self.last_patch_loss = source, self.patch_loss_buf
+            if with_lp and self.lp_robust:
+                lp.touched = True
+        else:
+            self._launch_iteration(b, hp=self._rec)
+            self._it_stats["eager"] += 1
+            uses = 1 if ent is None else ent[1] + 1
+            if ent is None and len(self._it_graphs) >= self.MAX_ITER_GRAPHS:   # each capture keeps a private pool: bound their number
+                oldest = next(iter(self._it_graphs))
+                self._drop_graphs(keep=lambda key_: key_ != oldest)
+            self._it_graphs[key] = (None, uses)
+            if uses == 2 and self._graph_ok:                      # two eager passes have created every lazy workspace: capture for the next
+                g = torch.cuda.CUDAGraph()
+                try:                                              # (a capture only RECORDS: nothing runs, no counter moves)
+                    with torch.cuda.graph(g, stream=stream, capture_error_mode="thread_local"):
+                        self._launch_iteration(b, hp=self._rec, capture=True)
+                except Exception as e:                            # a runtime that cannot capture: stay eager, say so once
+                    import warnings
+                    warnings.warn(f"npp_amd.fit: iteration not captured as a HIP graph ({e}); keeping the launch-by-launch form")
+                    self._graph_ok = self.lp_graph = False          # (the LPIPS branch would fail, and warn, the same way)
+                else:
+                    self._it_graphs[key] = (g, uses)
+                    self._it_stats["captured"] += 1
+        # ---- the host's side of optimizer.step(): what the eager loop leaves
+        net.optimizer_advance()
+        if lp.touched:
+            lp.lat_step += 1
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self._rec_ev[i] = st["free"] = ev
 
     # ---- checkpoint / resume (the reference has none: start = 0, helpers.py:166; SURVEY.md section 5) ----------------
     def state_dict(self):

@@ -730,6 +730,15 @@ class LPIPS(nn.Module):
         self.lat_step += 1
         ops.adam_step(self._lat, self._lat_m, self._lat_v, self._dlat, 1, self._lat.numel(), lr, self.lat_step)
 
+    def step_words(self, lr):
+        """(step_size, 1 / sqrt(1 - b2^t)) of the NEXT adam_step(lr), as npp_adam_step computes them: the device words of adam_launch_dev."""
+        return ops.adam_words(lr, self.lat_step + 1)
+
+    def adam_launch_dev(self, hp):
+        """The launch of adam_step() with its scalars from the device words hp[0:2] (npp_adam_step_dev); the caller advances lat_step
+        (a captured iteration, fit.CompletionFit(graph_iteration=True): a capture records, a replay runs, the host counts once)."""
+        ops.adam_step_dev(self._lat, self._lat_m, self._lat_v, self._dlat, 1, self._lat.numel(), hp)
+
 
 _VGG16_STYLE = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M"]          # vgg16.features[:17]: enc_1 | enc_2 | enc_3
 

@@ -330,6 +330,32 @@ class NPPNet:
         if self.lr_clock:
             self.global_step += 1
 
+    # ---- the same step for a captured iteration (fit.CompletionFit(graph_iteration=True)): launch and host record apart ----
+    def step_words(self):
+        """(step_size, 1 / sqrt(1 - b2^t)) of the NEXT optimizer step as npp_adam_step_net_pack would compute them from (lr, opt_step + 1):
+        what the caller writes into the device words of optimizer_launch_dev() before the launch runs."""
+        return ops.adam_words(self.lr, self.opt_step + 1)
+
+    def optimizer_launch_dev(self, Bp, hp):
+        """The launch of optimizer_step() with its step-dependent scalars read from the device words hp[0:2] (step_words()): nothing
+        on the host changes, so a capture may record it and a graph replay it; optimizer_advance() is the host half."""
+        if not self.fused_repack:
+            raise ValueError("optimizer_launch_dev: the fused Adam + re-pack launch only (precision='bf16', fused_repack)")
+        ws = self._ws[Bp]
+        gslabs = ws["gslabs"]
+        idle = self._loss_bufs[1 - self._loss_idx:2 - self._loss_idx]
+        ops.adam_step_net_pack_dev(self.params, self.m, self.v, gslabs, self.ksplit, gslabs.numel() // self.ksplit, self.latents, self.lat_m,
+                                   self.lat_v, self.dlatent, idle, hp, self.K, self.wf, self.wb, self.width,
+                                   pl_partials=getattr(self, "_pl_scratch", None), loss_cur=self.loss_buf)
+
+    def optimizer_advance(self):
+        """What optimizer_step() leaves on the host: the step count, the LR rule of train.py:253-263, global_step (:337)."""
+        self.opt_step += 1
+        self.lr = self.lrate * (0.1 ** (self.global_step / (self.lrate_decay * 100)))
+        if self.lr_clock:
+            self.global_step += 1
+        self._clean = True
+
     def _adam(self, gslabs, n_slabs, stride, idle):
         """optimizer.step() over the blob + latents and the re-pack of the bf16 MFMA packs: one launch (fused_repack, default)
         or two (npp_adam_step_net, then npp_pack_weights: the comparator)."""

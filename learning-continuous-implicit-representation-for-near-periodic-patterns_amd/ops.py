@@ -1,6 +1,7 @@
 """Thin torch-tensor wrappers over the C ABI (include/npp_hip.h).  torch is used for device
 memory and streams only; every call goes to libnpp_hip.so on the current HIP stream."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -484,6 +485,29 @@ def adam_step_net_pack(p, m, v, gslabs, n_slabs, slab_stride, lat, lat_m, lat_v,
                                             _p(lat_v), _p(dlat), lat.numel(), _p(zero), 0 if zero is None else zero.numel(),
                                             lr, b1, b2, eps, step, K, width, _p(wf), _p(wb), _p(pl_partials), _p(loss_cur), _stream()),
           "npp_adam_step_net_pack", width)
+
+
+def adam_words(lr, step, b1=0.9, b2=0.999):
+    """(step_size, 1 / sqrt(1 - b2^t)) as the argument forms of the Adam launches compute them from (lr, step) -- the float
+    arguments widened to double, pow / sqrt in double, the results rounded to float -- for the device-word forms
+    (adam_step_dev, adam_step_net_pack_dev): np.float32 pair, equal to the launches' own values bit for bit."""
+    lr, b1, b2 = float(np.float32(lr)), float(np.float32(b1)), float(np.float32(b2))
+    bc1, bc2 = 1.0 - math.pow(b1, int(step)), 1.0 - math.pow(b2, int(step))
+    return np.float32(lr / bc1), np.float32(1.0 / math.sqrt(bc2))
+
+
+def adam_step_net_pack_dev(p, m, v, gslabs, n_slabs, slab_stride, lat, lat_m, lat_v, dlat, zero, hp, K, wf, wb, width=NPP_WIDTH,
+                           b1=0.9, b2=0.999, eps=1e-8, pl_partials=None, loss_cur=None):
+    """adam_step_net_pack whose step_size / bias correction come from the device tensor hp[0:2] (adam_words): the form a captured
+    iteration replays (fit.CompletionFit(graph_iteration=True))."""
+    _req(p, torch.float32, "p")
+    _req(hp, torch.float32, "hp")
+    if hp.numel() < 2:
+        raise ValueError("hp: two floats (step_size, 1 / sqrt(1 - b2^t))")
+    check(lib(width).npp_adam_step_net_pack_dev(_p(p), _p(m), _p(v), _p(gslabs), p.numel(), n_slabs, slab_stride, _p(lat), _p(lat_m),
+                                                _p(lat_v), _p(dlat), lat.numel(), _p(zero), 0 if zero is None else zero.numel(),
+                                                b1, b2, eps, _p(hp), K, width, _p(wf), _p(wb), _p(pl_partials), _p(loss_cur), _stream()),
+          "npp_adam_step_net_pack_dev", width)
 
 
 def patch_gather(img_hwc, mask_hw, centres_yx, P, want_mask=True, out=None):

@@ -40,6 +40,9 @@ class StackedFit:
             if getattr(f, "trunk_precision", "fp16") != "fp16":
                 raise ValueError(f"StackedFit: trunk_precision='fp16' fits only (got trunk_precision={f.trunk_precision!r}: the exact-fp32 "
                                  "trunks have no stacked launches)")
+            if getattr(f, "graph_iteration", False):
+                raise ValueError("StackedFit: graph_iteration=True fits are not stacked (a captured iteration is one fit's launch "
+                                 "sequence; the stack has its own): build the fits with graph_iteration=False")
         modes = {f.rng_mode for f in fits}
         if "device" in modes and len(modes) > 1:
             raise ValueError(f"StackedFit: rng_mode='device' for every image of a stack or for none (got {sorted(modes)}): the device draws "

@@ -99,6 +99,10 @@ def parse(argv=None):
                     help="arithmetic of the VGG trunks of the patch losses: fp16 (default: fp16 activations, bf16 gradients) or fp32 (exact "
                          "fp32 convolutions -- with --precision fp32 the whole iteration runs in the reference's arithmetic; a diagnostic "
                          "mode, not stacked)")
+    ap.add_argument("--graph_iteration", action="store_true",
+                    help="replay the device side of every iteration as ONE captured HIP graph per iteration shape instead of enqueuing "
+                         "its launches (CompletionFit(graph_iteration=True)): same bits, one graph launch of host time per iteration; "
+                         "completion / segmentation with --precision bf16 --trunk_precision fp16, not stacked")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--save_model", action="store_true",
                     help="after a successful fit, write the network as model.npz into the image's result directory (npp_amd.render reads it)")
@@ -165,6 +169,9 @@ def _plan(argv=None):
         raise SystemExit("--eval_metrics judges images in [0, 1] (SSIM's data range is 1): --normalize_type 1 only")
     if args.eval_lpips is not None and not args.eval_metrics:
         raise SystemExit("--eval_lpips adds LPIPS to the report of --eval_metrics: give --eval_metrics as well")
+    if args.graph_iteration:
+        from .fit import refuse_graph_iteration
+        refuse_graph_iteration(args.precision, args.trunk_precision, args.task, None, SystemExit, flag=True)
     seg_task = args.task == "segmentation"
     from . import weights
     names = ["vgg19"] + ([] if seg_task else ["vgg16"]) + (["alexnet"] if seg_task else [])    # remapping: VGG16 is the style trunk
@@ -244,7 +251,7 @@ def _build(plan, stacked=False):
                             no_pix_loss=args.no_pix_loss, use_contextual_loss=args.use_contextual_loss, width=args.netwidth,
                             loss_type=args.loss_type, use_adaptive_perceptual_loss=args.use_adaptive_perceptual_loss,
                             normalize_type=args.normalize_type, precision=args.precision,
-                            trunk_precision=args.trunk_precision)
+                            trunk_precision=args.trunk_precision, graph_iteration=args.graph_iteration)
     except BaseException:
         import shutil
         shutil.rmtree(outroot, ignore_errors=True)          # (nothing was fitted: a re-run must not take the directory for a result)
@@ -326,9 +333,7 @@ def main(argv=None):
         return None
     failed = None
     try:
-        for i in range(1, job.args.N_iters):                                                # trange(start = 1, N_iters)
-            job.fit.step_full()
-            _after_iteration(job, i)
+        _loop(job)
     except BaseException as e:
         failed = e
         raise
@@ -337,11 +342,36 @@ def main(argv=None):
     return job.fit
 
 
+def _loop(job):
+    """The loop of one image, trange(start = 1, N_iters).  --graph_iteration: on a stream of its own -- a stream capture cannot begin
+    on the default stream, where the fit would carry every iteration over to a side stream and back -- joined with the default
+    stream on both sides, and the counts of fit.graph_stats once at the end."""
+    fit = job.fit
+    if not fit.graph_iteration:
+        for i in range(1, job.args.N_iters):
+            fit.step_full()
+            _after_iteration(job, i)
+        return
+    cur = torch.cuda.current_stream(fit.device)
+    s = torch.cuda.Stream(fit.device)
+    s.wait_stream(cur)
+    try:
+        with torch.cuda.stream(s):
+            for i in range(1, job.args.N_iters):
+                fit.step_full()
+                _after_iteration(job, i)
+    finally:
+        cur.wait_stream(s)
+    st = fit.graph_stats
+    print(f"[GRAPH] {st['replayed']} iterations replayed from {st['captured']} captured graphs, {st['eager']} launch by launch, "
+          f"{fit.skipped} skipped")
+
+
 def stack_key(job):
     """Fits that can share one launch sequence (stack.StackedFit): same network shape, batch shape, loss switches and schedule."""
     a, f = job.args, job.fit
     if (f.patch_sampler is None or f.use_patch_weight or not f.use_contextual_loss or f.net.out_act != 1 or f.net.precision != "bf16"
-            or f.trunk_precision != "fp16"):
+            or f.trunk_precision != "fp16" or f.graph_iteration):
         return None
     return (a.task, f.style is not None, f.style_w, f.pixel_mask is not None, f.net.K, f.net.width, f.N_rand, f.patch_size, f.patch_num, f.topk, f.net.quad, f.pix_w, f.use_comp, f.cx_w, f.lp_w,
             f.lp_robust, f.use_perceptual_loss, f.rng_mode, a.N_iters, a.i_testset, a.i_print, a.patch_size_decay, str(f.device))
@@ -418,9 +448,7 @@ def main_stacked(argvs, max_stack=8):
                 keys = {stack_key(j) for j in chunk}
                 if len(chunk) == 1 or len(keys) != 1 or None in keys:
                     for job in chunk:
-                        for i in range(1, job.args.N_iters):
-                            job.fit.step_full()
-                            _after_iteration(job, i)
+                        _loop(job)
                 else:
                     st = StackedFit([j.fit for j in chunk])
                     print(f"[stack] {len(chunk)} images per launch sequence: {[j.name for j in chunk]} (patch size {st.P}, wgrad split-K {st.ksplit})")
