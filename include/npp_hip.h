@@ -266,6 +266,49 @@ int npp_mlp_wgrad(const void* d_dzF, const void* d_actF, int64_t Bp, int K, int 
  * (K = 3: 21 tiles -> 12 on 256 CUs; K = 5: 25 -> 10; K = 1: 14 -> 18). */
 int npp_mlp_wgrad_tiles(int K);
 
+/* ---- stash audit: census of the 8-bit training stash (npp_tune "stash8" = 1) -----------------------------
+ * The reference trains in fp32 and has nothing to count; the 8-bit stash converts with saturation (a value out of range becomes the
+ * largest finite code, silently) and flushes what lies far below a tile's maximum.  The census scans what ONE iteration's
+ * npp_mlp_fwd* / npp_mlp_bwd* left in actF's W8 region and in dzF's bf8 arrays and counts, per array the configuration writes
+ * (rows < n_rows and real features only: 462 of an embedding's 480 slots, the 3 used features of dz_rgb, W / 2 of a_p / dz_p):
+ *   record[offsets[i] + NPP_CENSUS_ELEMENTS]   bytes counted
+ *                      NPP_CENSUS_ZERO         codes 0x00 / 0x80 (a flushed value and a true zero share them: an upper bound on flushes)
+ *                      NPP_CENSUS_SUBNORMAL    exponent field 0, mantissa != 0
+ *                      NPP_CENSUS_AT_MAX       |code| = the largest finite (e4m3 0x7E = 448, e5m2 0x7B = 57344): saturated, or exactly there
+ *                      NPP_CENSUS_NONFINITE    e4m3 0x7F (NaN); e5m2 0x7C..0x7F (infinity, NaN)
+ *                      NPP_CENSUS_HIST + e     finite codes by exponent field e (32 bins; e4m3 uses 16); bin 0 = zero + subnormal
+ * so that elements = zero + subnormal + sum of bins 1.. + nonfinite, with at_max inside its bin.  Behind the arrays, at *tile_offset:
+ * NPP_CENSUS_TILES (64-row tiles with a real row) and NPP_CENSUS_SCALE_MIN / _MAX, the smallest / largest E8M0 byte of their scale
+ * words (stored gradient * 2^(byte - 127) = gradient).  All words are int64; integer sums: the record does not depend on the schedule.
+ *
+ * npp_stash8_census_words: int64 words of the record.  npp_stash8_census_layout: the table -- names[i] (static strings: a0..a7 the
+ * snake layers' outputs, f1, a_s, f2, a_p, emb0.., dz0..dz7, dz_f1, dz_s, dz_f2, dz_p, dz_rgb; K = 1 has no a_s / f2 / dz_s / dz_f2),
+ * formats[i] (0 = fp8 e4m3, 1 = bf8 e5m2), features[i] (real features per row), offsets[i] (words into the record); any output may be
+ * NULL, arrays hold NPP_CENSUS_MAX_ARRAYS entries; returns the number of arrays.
+ * npp_stash8_census: d_actF / d_dzF are the workspace arrays of npp_train_workspace(K, width, Bp) as the launches were given them
+ * (a stacked workspace: the same entry on image m's offset pointers); 1 <= n_rows <= Bp.  Clears d_record itself (hipMemsetAsync),
+ * then one launch; allocates nothing and writes nothing else.  npp_stash8_census_host: the same counts by plain C++ on HOST copies
+ * of the same bytes (no GPU needed). */
+#define NPP_CENSUS_ELEMENTS 0
+#define NPP_CENSUS_ZERO 1
+#define NPP_CENSUS_SUBNORMAL 2
+#define NPP_CENSUS_AT_MAX 3
+#define NPP_CENSUS_NONFINITE 4
+#define NPP_CENSUS_HIST 5
+#define NPP_CENSUS_BINS 32
+#define NPP_CENSUS_ENTRY_WORDS (NPP_CENSUS_HIST + NPP_CENSUS_BINS)
+#define NPP_CENSUS_TILES 0
+#define NPP_CENSUS_SCALE_MIN 1
+#define NPP_CENSUS_SCALE_MAX 2
+#define NPP_CENSUS_TILE_WORDS 3
+#define NPP_CENSUS_MAX_ARRAYS (12 + NPP_MAX_K + 13)
+int64_t npp_stash8_census_words(int K, int width);
+int npp_stash8_census_layout(int K, int width, const char** names, int32_t* formats, int32_t* features, int64_t* offsets,
+                             int64_t* tile_offset);
+int npp_stash8_census(const void* d_actF, const void* d_dzF, int64_t Bp, int64_t n_rows, int K, int width, int64_t* d_record,
+                      void* stream);
+int npp_stash8_census_host(const void* actF, const void* dzF, int64_t Bp, int64_t n_rows, int K, int width, int64_t* record);
+
 /* d_grad[n] (+)= sum of the slabs: the parameter gradient as one blob, for optimisers other than
  * npp_adam_step (the reference hands model.parameters() to torch.optim.Adam, helpers.py:164). */
 int npp_grad_reduce(const float* d_gslabs, int n_slabs, int64_t slab_stride, int64_t n,

@@ -10,6 +10,9 @@ LIB_PATHS = {256: LIB_PATH, 512: os.environ.get("NPP_LIB_PATH_W512") or os.path.
 FUSED_WIDTHS = tuple(sorted(LIB_PATHS))
 
 NPP_MAX_K, NPP_N_OFF, NPP_N_FREQ, NPP_E, NPP_WIDTH, NPP_ROW_TILE = 5, 5, 10, 462, 256, 64
+# one array's entry of the stash-census record (include/npp_hip.h NPP_CENSUS_*): five counters, then the exponent histogram
+CENSUS_FIELDS, CENSUS_BINS, CENSUS_MAX_ARRAYS = ("elements", "zero", "subnormal", "at_max", "nonfinite"), 32, 12 + NPP_MAX_K + 13
+CENSUS_TILE_FIELDS = ("tiles", "scale_min", "scale_max")
 
 
 class NppError(RuntimeError):
@@ -131,6 +134,11 @@ SYMBOLS = {
     "npp_mlp_bwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "npp_mlp_wgrad": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "npp_mlp_wgrad_tiles": (_i32, [_i32]),
+    "npp_stash8_census_words": (_i64, [_i32, _i32]),
+    "npp_stash8_census_layout": (_i32, [_i32, _i32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_i64),
+                                        C.POINTER(_i64)]),
+    "npp_stash8_census": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "npp_stash8_census_host": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp]),
     "npp_pixel_loss": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "npp_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _f32, _f32, _f32, _f32, _i32, _vp]),
     "npp_mlp_fwd_emb": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
@@ -352,3 +360,18 @@ def param_layout(K, width=NPP_WIDTH):
     for i in range(n):
         out.append((names[i].decode(), int(offs[i]), int(rows[i]), int(cols[i])))
     return out, int(total.value)
+
+
+def census_layout(K, width=NPP_WIDTH):
+    """npp_stash8_census_layout: ([(name, format 'e4m3' | 'e5m2', features per row, offset in int64 words)], offset of the tile
+    words, words of the record) -- the library's own table of the 8-bit stash arrays it writes for (K, width)."""
+    L = lib(width)
+    names = (C.c_char_p * CENSUS_MAX_ARRAYS)()
+    fmts = (C.c_int32 * CENSUS_MAX_ARRAYS)()
+    feats = (C.c_int32 * CENSUS_MAX_ARRAYS)()
+    offs = (_i64 * CENSUS_MAX_ARRAYS)()
+    tile = _i64(0)
+    n = check(L.npp_stash8_census_layout(K, width, names, fmts, feats, offs, C.byref(tile)), "npp_stash8_census_layout", width)
+    words = check(L.npp_stash8_census_words(K, width), "npp_stash8_census_words", width)
+    return ([(names[i].decode(), "e5m2" if fmts[i] else "e4m3", int(feats[i]), int(offs[i])) for i in range(n)], int(tile.value),
+            int(words))

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "npp_common.h"
+#include "npp_stash_census.h"
 
 namespace npp {
 
@@ -562,6 +563,75 @@ int npp_train_workspace(int K, int width, int64_t Bp, int ksplit, int64_t sizes[
   sizes[1] = (int64_t)act_total_ks(K) * (Bp / kRowTile) * (2048 + 1024);
   sizes[2] = (int64_t)kDzTotalKs * (Bp / kRowTile) * 2048;
   sizes[3] = (int64_t)ksplit * slab_stride_of(make_desc(K).total_params) * 4;      // ksplit slabs, see slab_stride_of
+  return NPP_OK;
+}
+
+// ---- stash audit (npp_stash_census.h) ------------------------------------------------------------------------------------
+int64_t npp_stash8_census_words(int K, int width) {
+  if (check_kw(K, width)) return -1;
+  return census_words(K);
+}
+
+int npp_stash8_census_layout(int K, int width, const char** names, int32_t* formats, int32_t* features, int64_t* offsets,
+                             int64_t* tile_offset) {
+  int rc = check_kw(K, width);
+  if (rc) return rc;
+  static thread_local char name_buf[kCensusMaxArrays][12];
+  const CensusDesc d = make_census_desc(K, name_buf);
+  for (int i = 0; i < d.n; ++i) {
+    if (names) names[i] = name_buf[i];
+    if (formats) formats[i] = d.a[i].side;
+    if (features) features[i] = d.a[i].features;
+    if (offsets) offsets[i] = (int64_t)i * kCensusEntry;
+  }
+  if (tile_offset) *tile_offset = (int64_t)d.n * kCensusEntry;
+  return d.n;
+}
+
+static int census_check(const char* who, const void* actF, const void* dzF, int64_t Bp, int64_t n_rows, int K, int width, const void* rec) {
+  int rc = check_kw(K, width);
+  if (rc) return rc;
+  if (!actF || !dzF || !rec || (((uintptr_t)actF | (uintptr_t)dzF) & 15) || ((uintptr_t)rec & 7)) {
+    set_error("%s: null or misaligned pointer (stash arrays 16-byte, record 8-byte aligned)", who);
+    return NPP_ERR_ARG;
+  }
+  if (Bp <= 0 || Bp % kRowTile || Bp / kRowTile > 65536 || n_rows < 1 || n_rows > Bp) {
+    set_error("%s: bad Bp=%lld (a multiple of %d, <= %d rows) / n_rows=%lld (1..Bp)", who, (long long)Bp, kRowTile, 65536 * kRowTile, (long long)n_rows);
+    return NPP_ERR_ARG;
+  }
+  return NPP_OK;
+}
+
+int npp_stash8_census(const void* d_actF, const void* d_dzF, int64_t Bp, int64_t n_rows, int K, int width, int64_t* d_record,
+                      void* stream) {
+  int rc = census_check("npp_stash8_census", d_actF, d_dzF, Bp, n_rows, K, width, d_record);
+  if (rc) return rc;
+  CensusArgs A{};
+  A.n_wg = Bp / kRowTile; A.n_rows = n_rows;
+  A.act8 = (const uint8_t*)d_actF + act8_region_base(K, A.n_wg);
+  A.dz8 = (const uint8_t*)d_dzF;
+  A.rec = (unsigned long long*)d_record;
+  A.d = make_census_desc(K);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t words = (int64_t)A.d.n * kCensusEntry + NPP_CENSUS_TILE_WORDS;
+  hipError_t e = hipMemsetAsync(d_record, 0, (size_t)words * 8, s);
+  // the minimum starts from a word no scale byte reaches (0x7f7f...): every census has a tile, so it never survives
+  if (e == hipSuccess) e = hipMemsetAsync(d_record + (int64_t)A.d.n * kCensusEntry + NPP_CENSUS_SCALE_MIN, 0x7f, 8, s);
+  if (e != hipSuccess) { set_error("npp_stash8_census: hipMemsetAsync: %s", hipGetErrorString(e)); return NPP_ERR_LAUNCH; }
+  int max_nks = 0;
+  for (int i = 0; i < A.d.n; ++i) max_nks = A.d.a[i].nks > max_nks ? A.d.a[i].nks : max_nks;
+  // four 16-byte pieces per lane and slice at least; at most 64 slices per array (few workgroups -> few atomics per counter)
+  const int64_t want = ((int64_t)max_nks * A.n_wg * 64 + 4 * kCensusThreads - 1) / (4 * kCensusThreads);
+  const unsigned gx = (unsigned)(want < 1 ? 1 : (want > 64 ? 64 : want));
+  hipLaunchKernelGGL(stash8_census_kernel, dim3(gx, (unsigned)A.d.n + 1), dim3(kCensusThreads), 0, s, A);
+  return check_launch("npp_stash8_census");
+}
+
+int npp_stash8_census_host(const void* actF, const void* dzF, int64_t Bp, int64_t n_rows, int K, int width, int64_t* record) {
+  int rc = census_check("npp_stash8_census_host", actF, dzF, Bp, n_rows, K, width, record);
+  if (rc) return rc;
+  const int64_t n_wg = Bp / kRowTile;
+  stash8_census_host((const uint8_t*)actF + act8_region_base(K, n_wg), (const uint8_t*)dzF, n_wg, n_rows, K, record);
   return NPP_OK;
 }
 

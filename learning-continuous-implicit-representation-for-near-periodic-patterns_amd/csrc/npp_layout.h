@@ -336,6 +336,16 @@ NPP_HD int64_t wfmt8_unit(int nks, int64_t wg, int ks, int row64, int hh) {
   return (((wg * (nks >> 1) + (ks >> 1)) * 8 + (row64 >> 3)) * 256) + (ks & 1) * 128 + hh * 64 + (row64 & 7) * 8;
 }
 NPP_HD int64_t wfmt8_array_base(int ks_off, int64_t n_wg) { return (int64_t)ks_off * n_wg * 1024; }
+// inverse of wfmt8_unit at 16-byte granularity (the stash census walks an array linearly): the 16 bytes at byte offset 16 q of an array
+// with nks k-steps are the units of rows (row64, row64 + 1) of one (wg, ks, hh) -- byte i is element i & 7 of row row64 + (i >> 3)
+NPP_HD void wfmt8_unit16_decode(int nks, int64_t q, int64_t& wg, int& ks, int& row64, int& hh) {
+  const int64_t run = q >> 7;                    // 2-KiB (ks pair) run
+  const int in = (int)(q & 127), line = in >> 4, o = in & 15;
+  wg = run / (nks >> 1);
+  ks = 2 * (int)(run - wg * (nks >> 1)) + (o >> 3);
+  hh = (o >> 2) & 1;
+  row64 = line * 8 + (o & 3) * 2;
+}
 NPP_HD int w8_feat(int lane32) { return (lane32 & 0x13) | ((lane32 & 4) << 1) | ((lane32 & 8) >> 1); }
 // actF in stash8 mode: the 16-bit W-format region keeps the fp16 pre-activations the backward chain reads (f1 / f2 / embedding
 // arrays of that region stay unwritten); the 8-bit arrays follow it with the SAME k-step offsets (kActF1 ..., kActKsEmb0 + 30 p)

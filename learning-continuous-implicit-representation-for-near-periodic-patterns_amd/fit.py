@@ -58,7 +58,7 @@ class CompletionFit:
                  prefetch=0, use_perceptual_loss=True, task="completion", clear_mask=None, style_weight=None,
                  vgg16_style_state_dict=None, masked_img=None, width=256, no_reg_sampling=False, use_patch_weight=False,
                  no_pix_loss=False, use_contextual_loss=True, loss_type="robust_loss_adaptive", use_adaptive_perceptual_loss=True, normalize_type=1,
-                 precision="bf16", trunk_precision="fp16", graph_iteration=False):
+                 precision="bf16", trunk_precision="fp16", graph_iteration=False, stash_audit=0):
         """img (H,W,3) float in [0,1]; mask (H,W,1) 1 = known (loaders.py:92-101).
         precision: the arithmetic of the coordinate MLP's training launches, 'bf16' (default) or 'fp32' (NPPNet(precision=...): the
         exact fp32 chain, the reference's own arithmetic; the iteration then takes the unfolded launch sequence -- fold_launches =
@@ -91,7 +91,19 @@ class CompletionFit:
         graph_iteration: True replays the device side of an iteration (step_from) as ONE captured HIP graph per iteration shape
         instead of enqueuing its launches (_step_from_graph): the bits of the launch-by-launch loop at one graph launch of host
         time per iteration.  Built for the default arithmetic (precision='bf16', trunk_precision='fp16') of the completion and
-        segmentation tasks without a style term; the other modes are refused by name."""
+        segmentation tasks without a style term; the other modes are refused by name.
+        stash_audit: N > 0 audits the 8-bit training stash on every N-th iteration of step_full() (0, the default: never;
+        audit_next() arms one iteration): between the weight-gradient and the optimiser launch the iteration's stash is counted
+        (NPPNet.stash_census) and its weight gradients are compared with the 16-bit stash's (NPPNet.stash_gap).  Reports collect in
+        .stash_audits (the last MAX_STASH_AUDITS) and .last_stash_audit.  Nothing the optimiser reads is touched: an audited fit
+        ends with the bits of an unaudited one.  Refused by name for precision='fp32' and under npp_tune("stash8") = 0."""
+        self.stash_audit = int(stash_audit)
+        if self.stash_audit < 0:
+            raise ValueError("stash_audit must be >= 0 (0: never)")
+        if self.stash_audit:
+            ops.refuse_stash_audit(precision, capturing=False)
+        import collections
+        self.stash_audits, self.last_stash_audit, self._audit_armed = collections.deque(maxlen=self.MAX_STASH_AUDITS), None, False
         if rng_mode not in ("reference", "numpy", "fast", "device"):
             raise ValueError("rng_mode must be 'reference', 'numpy', 'fast' or 'device'")
         if rng_mode == "device" and int(prefetch) > 0:
@@ -210,6 +222,7 @@ class CompletionFit:
             self._rec_pin = torch.zeros((self._REC_SLOTS, 4), dtype=torch.float32).pin_memory()
             self._rec_np, self._rec_ev, self._rec_i = self._rec_pin.numpy(), [None] * self._REC_SLOTS, 0
 
+    MAX_STASH_AUDITS = 4096   # reports kept in .stash_audits (a deque: the oldest go first)
     _REC_SLOTS = 32           # pinned copies of the scalar record in flight (the host may enqueue that many iterations ahead)
     MAX_ITER_GRAPHS = 40      # live captured iterations (3 sources x 3 k x 2 buffer sets x 2 loss accumulators at most per shape)
 
@@ -218,6 +231,32 @@ class CompletionFit:
         """graph_iteration: {"captured": graphs captured so far, "replayed": iterations run as a graph replay, "eager": iterations run
         launch by launch (the first uses of a key, keys met while no capture is possible)}; skipped iterations count nowhere."""
         return dict(self._it_stats)
+
+    # ---- stash audit (DESIGN.md section 6j) ------------------------------------------------------------------------------
+    def audit_next(self):
+        """Arm the stash audit for the next iteration that runs (a skipped iteration leaves it armed)."""
+        ops.refuse_stash_audit(self.precision, capturing=False)
+        self._audit_armed = True
+
+    def _audit_due(self):
+        return self._audit_armed or (self.stash_audit > 0 and self.iteration % self.stash_audit == 0)
+
+    def _stash_audit(self, b):
+        """The audit of the iteration in flight, behind its weight-gradient launch and in front of its optimiser launch: census
+        first (the 16-bit leg of the gap overwrites the stash), then the gap.  Reads its results back: synchronises."""
+        net = self.net
+        self._audit_armed = False
+        census = net.stash_census(b["bp"], b["n"])
+        gap = net.stash_gap(b["bp"], b["coords"])
+        worst = max(gap, key=gap.get)
+        at_max = sum(c["at_max"] for c in census.values())
+        nonfinite = sum(c["nonfinite"] for c in census.values())
+        rep = {"iteration": int(self.iteration), "source": b["source"], "rows": int(b["n"]), "census": census,
+               "tile_scale": dict(net.last_tile_scale), "grad_gap": gap, "worst": [worst, gap[worst]],
+               "flags": ["saturated"] if at_max + nonfinite > 0 else []}       # exact: a code at the format's limit exists
+        self.last_stash_audit = rep
+        self.stash_audits.append(rep)
+        return rep
 
     def lpips_branch(self, xy, nk, scale, loss_buf):
         """percepLoss.fused(xy, nk, scale, loss_buf) on the CURRENT stream (the loop's side stream).  The branch is 46 launches at the
@@ -542,7 +581,7 @@ class CompletionFit:
         self.net.zero_grad()
         if self.percepLoss.touched:
             self.percepLoss.zero_latent_grads()
-        self._launch_iteration(b)
+        self._launch_iteration(b, audit=self._audit_due())
 
     def _select_xy(self, nk, P):
         key = (nk, P)
@@ -555,7 +594,7 @@ class CompletionFit:
                 self._xy_bufs[key] = torch.empty((2 * nk, 3, P, P), dtype=torch.float32, device=self.device)
             self._xy, self._xy_key = self._xy_bufs[key], key
 
-    def _launch_iteration(self, b, hp=None, capture=False):
+    def _launch_iteration(self, b, hp=None, capture=False, audit=False):
         """The launches of one iteration behind zero_grad(), on the current stream (+ the LPIPS side stream).  hp None: the loop's
         form -- step-dependent scalars as kernel arguments, the host's counters advanced on the way.  hp = the scalar record on the
         device (graph_iteration): the same launches with the optimisers' scalars read from hp[0:2] (network + pixel-loss latents)
@@ -636,6 +675,8 @@ class CompletionFit:
         lr_used = net.lr
         if hp is not None:                                        # (graph_iteration: bf16 MLP, fp16 trunks, folded launches, no style term)
             net.backward(bp, patch=(dx_a, dx_b, raw["fmask"], raw["rmask"], n_pix, n_p, k, P, comp))
+            if audit:
+                self._stash_audit(b)
             net.optimizer_launch_dev(bp, hp[0:2])
             if self.percepLoss.touched:
                 self.percepLoss.adam_launch_dev(hp[2:4])
@@ -643,11 +684,12 @@ class CompletionFit:
         # npp_patch_compose_bwd folded into the backward launch: dL/dpred of the patch rows is formed (and written) there
         if fold_bwd:
             net.backward(bp, patch=(dx_a, dx_b, raw["fmask"], raw["rmask"], n_pix, n_p, k, P, comp))
-            net.optimizer_step(bp)
         else:
             ops.patch_compose_bwd(dx_a, dx_b, raw["fmask"], raw["rmask"], n_p, k, P, comp, ws["dpred"][n_pix:n])
             net.backward(bp)
-            net.optimizer_step(bp)
+        if audit:                                                 # (in front of the optimiser launch: the slabs are what Adam will read)
+            self._stash_audit(b)
+        net.optimizer_step(bp)
         if self.percepLoss.touched:                               # only 'same' iterations give them a gradient
             self.percepLoss.adam_step(lr_used)
         if self.style is not None:                                # the style latents are in the same optimiser (helpers.py:153-159)
@@ -738,7 +780,12 @@ class CompletionFit:
                int(lp.hip_trunk.fuse_pairs), lp.hip_trunk.fold_pool_bwd, lp.hip_trunk.fold_pool_fwd, int(cx.fuse_pairs), cx.fold_pool_bwd,
                cx.fold_pool_fwd, ops.DETERMINISTIC, stream.cuda_stream)
         ent = self._it_graphs.get(key)
-        if ent is not None and ent[0] is not None:
+        if self._audit_due():
+            # an audited iteration runs launch by launch (the audit sits between two of its launches and reads back on the host);
+            # it is no use of the key: captures and replays go on around it as if it had not been audited
+            self._launch_iteration(b, hp=self._rec, audit=True)
+            self._it_stats["eager"] += 1
+        elif ent is not None and ent[0] is not None:
             ent[0].replay()
             self._it_stats["replayed"] += 1
             self.last_source, self.last_patch_loss = source, self.patch_loss_buf

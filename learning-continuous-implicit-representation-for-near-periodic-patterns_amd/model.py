@@ -303,6 +303,57 @@ class NPPNet:
             ops.mlp_bwd(ws["dpred"], ws["pred"], self.K, self.wb, self.params, ws["actT"], ws["dzT"], self.width, out_act=self.out_act)
         ops.mlp_wgrad(ws["dzT"], ws["actT"], Bp, self.K, self.ksplit, ws["gslabs"], self.width)
 
+    # ---- stash audit: what the iteration's 8-bit stash did, read back from the workspace -------------------
+    def stash_census(self, Bp, n_rows):
+        """Census of the 8-bit stash the last forward_train / backward of workspace Bp left (npp_stash8_census): {array name:
+        {"format", "features", "elements", "zero", "subnormal", "at_max", "nonfinite", "exp_hist"}} for rows < n_rows; the per-tile
+        scale summary of dzF stays in .last_tile_scale.  Call it before anything overwrites the stash (stash_gap does)."""
+        ops.refuse_stash_audit(self.precision)
+        ws = self._ws[Bp]
+        if "census" not in ws:
+            ws["census"] = ops.stash8_census(ws["actT"], ws["dzT"], Bp, n_rows, self.K, None, self.width)
+        else:
+            ops.stash8_census(ws["actT"], ws["dzT"], Bp, n_rows, self.K, ws["census"], self.width)
+        arrays, self.last_tile_scale = ops.census_decode(ws["census"].cpu().numpy(), self.K, self.width)
+        return arrays
+
+    def stash_gap(self, Bp, coords):
+        """How far the weight gradients of this iteration (the slabs backward(Bp) left: what Adam will read) are from the 16-bit
+        stash's: {tensor name: rel_l2(g8, g16)} under the reference's state_dict names.  The 16-bit leg re-runs the iteration's own
+        launches with npp_tune("stash8") = 0 -- forward_train on `coords` (the padded rows of the batch: identical pred), the plain
+        backward on the retained dL/dpred (complete after a patch-folded backward), the weight gradient into a second slab buffer
+        this net allocates once -- so pred, dpred, the slabs and the loss words are as the iteration left them; the stash is not
+        (take stash_census first).  The switch is process-wide for the duration of the three enqueues: not for fits on other host
+        threads of this process."""
+        ops.refuse_stash_audit(self.precision)
+        ws = self._ws[Bp]
+        if "gslabs16" not in ws:
+            ws["gslabs16"] = torch.empty_like(ws["gslabs"])
+        old = ops.tune("stash8", 0)
+        try:
+            ops.mlp_fwd(coords, self.cfg, self.wf, self.params, ws["pred"], ws["actT"], self.width, out_act=self.out_act)
+            ops.mlp_bwd(ws["dpred"], ws["pred"], self.K, self.wb, self.params, ws["actT"], ws["dzT"], self.width, out_act=self.out_act)
+            ops.mlp_wgrad(ws["dzT"], ws["actT"], Bp, self.K, self.ksplit, ws["gslabs16"], self.width)
+        finally:
+            ops.tune("stash8", old)
+        self._ws_gap = ws
+        g8 = ws["gslabs"].view(self.ksplit, -1)[:, :self.n_params].sum(0).double()      # the sums grads() forms, then float64
+        g16 = ws["gslabs16"].view(self.ksplit, -1)[:, :self.n_params].sum(0).double()
+        d = g8 - g16
+        num = torch.stack([torch.linalg.vector_norm(d[off:off + rows * cols]) for _, off, rows, cols in self.layout])
+        den = torch.stack([torch.linalg.vector_norm(g16[off:off + rows * cols]) for _, off, rows, cols in self.layout])
+        gap = (num / den.clamp_min(1e-30)).cpu().numpy()
+        return {name: float(gap[i]) for i, (name, *_r) in enumerate(self.layout)}
+
+    def stash_gap_grads16(self):
+        """The 16-bit leg's gradients of the last stash_gap(), in the form of grads() (for tests)."""
+        g = self._ws_gap["gslabs16"].view(self.ksplit, -1)[:, :self.n_params].sum(0).cpu().numpy()
+        out = {}
+        for name, off, rows, cols in self.layout:
+            a = g[off:off + rows * cols]
+            out[name] = a.reshape(rows, cols).copy() if name.endswith("weight") else a.copy()
+        return out
+
     def pixel_loss(self, Bp, n_rows, gt, mask=None, weight=1.0):
         """img2mse on the first n_rows rows of the current prediction (train.py:195);
         writes dL/dpred for those rows and accumulates the latent gradients."""

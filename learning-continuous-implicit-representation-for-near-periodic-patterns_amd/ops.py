@@ -412,6 +412,61 @@ def mlp_wgrad(dzT, actT, Bp, K, ksplit, gslabs, width=NPP_WIDTH):
     check(lib(width).npp_mlp_wgrad(_p(dzT), _p(actT), Bp, K, width, ksplit, _p(gslabs), _stream()), "npp_mlp_wgrad", width)
 
 
+def stash8_census(actT, dzT, Bp, n_rows, K, record=None, width=NPP_WIDTH):
+    """npp_stash8_census on one training workspace (actT / dzT as the launches were given them; a stacked workspace: image m's rows)
+    -> the int64 record on the device (census_decode reads it).  Clears the record itself; nothing else is written."""
+    from ._lib import census_layout
+    words = census_layout(K, width)[2]
+    if record is None:
+        record = torch.empty(words, dtype=torch.int64, device=actT.device)
+    _req(record, torch.int64, "record", (words,))
+    check(lib(width).npp_stash8_census(_p(actT), _p(dzT), int(Bp), int(n_rows), K, width, _p(record), _stream()), "npp_stash8_census", width)
+    return record
+
+
+def stash8_census_host(act, dz, Bp, n_rows, K, width=NPP_WIDTH):
+    """npp_stash8_census_host: the same record by plain C++ on host copies (uint8 NumPy arrays) of the same bytes."""
+    from ._lib import census_layout
+    act, dz = np.ascontiguousarray(act, np.uint8), np.ascontiguousarray(dz, np.uint8)
+    rec = np.zeros(census_layout(K, width)[2], np.int64)
+    check(lib(width).npp_stash8_census_host(C.c_void_p(act.ctypes.data), C.c_void_p(dz.ctypes.data), int(Bp), int(n_rows), K, width,
+                                            C.c_void_p(rec.ctypes.data)), "npp_stash8_census_host", width)
+    return rec
+
+
+def census_decode(record, K, width=NPP_WIDTH):
+    """An int64 census record (NumPy) -> ({array name: {"format", "features", "elements", "zero", "subnormal", "at_max", "nonfinite",
+    "exp_hist": [32]}}, {"tiles", "scale_min", "scale_max"}), by the library's own table (census_layout)."""
+    from ._lib import census_layout, CENSUS_FIELDS, CENSUS_BINS, CENSUS_TILE_FIELDS
+    table, tile_off, _ = census_layout(K, width)
+    rec = np.asarray(record, np.int64)
+    out = {}
+    for name, fmt, feats, off in table:
+        e = {"format": fmt, "features": feats}
+        for i, f in enumerate(CENSUS_FIELDS):
+            e[f] = int(rec[off + i])
+        e["exp_hist"] = [int(v) for v in rec[off + len(CENSUS_FIELDS):off + len(CENSUS_FIELDS) + CENSUS_BINS]]
+        out[name] = e
+    return out, {f: int(rec[tile_off + i]) for i, f in enumerate(CENSUS_TILE_FIELDS)}
+
+
+def refuse_stash_audit(precision, exc=ValueError, flag=False, capturing=None):
+    """The stash audit reads the 8-bit stash of the bf16 chain: refused by name where there is none (exc: ValueError for the Python
+    interface, SystemExit for the command line; flag: name the switches as flags) and while a stream capture is open (the audit
+    copies its record to the host)."""
+    me = "--audit_stash" if flag else "stash audit"
+    if precision != "bf16":
+        raise exc(f"{me} with {'--precision ' + precision if flag else 'precision=' + repr(precision)}: the exact-fp32 chain has no "
+                  f"8-bit stash (its stash is fp32, nothing is rounded)")
+    if not tune("stash8"):
+        raise exc(f"{me} with {'NPP_STASH8=0 / ' if flag else ''}npp_tune('stash8') = 0: the 16-bit stash is in use, there is nothing to audit")
+    if capturing is None:
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+    if capturing:
+        raise exc(f"{me} while a stream capture is open: an audit reads its record back on the host; run it outside "
+                  f"torch.cuda.graph / hipStreamBeginCapture")
+
+
 def load_spline(device):
     """values|tangents fp32 on the device + (n_knots, x_scale); table: resources/partition_spline.npz
     (this repo's own derivation, tools/gen_partition_spline.py; distribution.py:129-141)."""

@@ -49,7 +49,10 @@ def metrics_table(args, names):
     directory (name, PSNR and SSIM of the unknown region; with "--eval_lpips NET" among them also its LPIPS, the mean of the distance
     map over the region).  Printed only when the flag is among the train arguments."""
     import json
-    if "--eval_metrics" not in shlex.split(args.train_args) or not names:
+    targs = shlex.split(args.train_args)
+    if "--audit_stash" in targs and names:
+        return _table_with_stash(args, names, "--eval_metrics" in targs)
+    if "--eval_metrics" not in targs or not names:
         return
     from .train import parse as train_parse
     a = train_parse(["--datadir", "."] + (["--task", args.task] if args.task != "completion" else []) + shlex.split(args.train_args))
@@ -65,6 +68,37 @@ def metrics_table(args, names):
         except (OSError, ValueError, KeyError):
             cells = ["-"] * len(cols)                              # no report: the fit failed or was found in place without one
         print(f"{n:<{width}}" + "".join(f"  {c:>13}" if k == "lpips" else f"  {c:>12}" for c, (k, _, _) in zip(cells, cols)))
+    sys.stdout.flush()
+
+
+def _table_with_stash(args, names, with_metrics):
+    """metrics_table with --train-args "--audit_stash N": the same table (its metric columns only with --eval_metrics) plus one
+    column from the stash_audit.json each fit left -- the worst gradient gap over the fit's audits, marked * when any audited
+    iteration had a code at a format's limit ("saturated")."""
+    import json
+    from .train import parse as train_parse
+    a = train_parse(["--datadir", "."] + (["--task", args.task] if args.task != "completion" else []) + shlex.split(args.train_args))
+    expname = a.expname if not (args.task != "completion" and a.expname == "completion") else args.task     # train._plan's rule
+    width = max([len(n) for n in names] + [5])
+    cols = ([("psnr", "{:.2f} dB", "PSNR unknown"), ("ssim", "{:.4f}", "SSIM unknown")] + ([("lpips", "{:.4f}", "LPIPS unknown")] if a.eval_lpips else [])) if with_metrics else []
+    print(f"{'image':<{width}}" + "".join(f"  {title:>13}" if k == "lpips" else f"  {title:>12}" for k, _, title in cols) + f"  {'stash gap':>12}")
+    for n in names:
+        root = os.path.join(args.basedir, f"{expname}_top{args.p_topk}", n)
+        cells = []
+        if with_metrics:
+            try:
+                with open(os.path.join(root, "metrics.json")) as f:
+                    u = json.load(f)["unknown"]
+                cells = ["n/a" if (u.get(k) if k == "lpips" else u[k]) is None else fmt.format(u[k]) for k, fmt, _ in cols]
+            except (OSError, ValueError, KeyError):
+                cells = ["-"] * len(cols)
+        try:
+            with open(os.path.join(root, "stash_audit.json")) as f:
+                reps = json.load(f)[1:]
+            gap = "n/a" if not reps else f"{max(r['worst'][1] for r in reps):.3e}" + ("*" if any(r["flags"] for r in reps) else "")
+        except (OSError, ValueError, KeyError):
+            gap = "-"
+        print(f"{n:<{width}}" + "".join(f"  {c:>13}" if k == "lpips" else f"  {c:>12}" for c, (k, _, _) in zip(cells, cols)) + f"  {gap:>12}")
     sys.stdout.flush()
 
 

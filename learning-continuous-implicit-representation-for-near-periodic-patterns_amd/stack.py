@@ -274,6 +274,21 @@ class StackedFit:
         self._ahead = None if nxt is None else self._draw(nxt)
         return n
 
+    def stash_census(self):
+        """After step_full(): the census of the 8-bit stash (NPPNet.stash_census) of every image that took the
+        step -- a list over the images, None for one that sat the iteration out.  A stacked workspace is M single layouts: the
+        single-image launch on image m's rows of actF / dzF.  No gradient gap (the stack has no 16-bit leg); .last_tile_scales
+        holds the per-tile scale summaries."""
+        ops.refuse_stash_audit("bf16")
+        srcs = getattr(self, "last_sources", None)
+        if srcs is None:
+            raise RuntimeError("StackedFit.stash_census: no iteration has run yet (call step_full() first)")
+        recs = [None if s is None else ops.stash8_census(self.actF[m], self.dzF[m], self.Bp, self.n, self.K, None, self.width)
+                for m, s in enumerate(srcs)]
+        dec = [None if r is None else ops.census_decode(r.cpu().numpy(), self.K, self.width) for r in recs]
+        self.last_tile_scales = [None if d is None else d[1] for d in dec]
+        return [None if d is None else d[0] for d in dec]
+
     # ---- device half ---------------------------------------------------------------------------------------------------------
     def step_from(self, batches):
         ops.check_current(self.device)

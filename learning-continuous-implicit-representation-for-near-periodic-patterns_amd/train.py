@@ -103,6 +103,11 @@ def parse(argv=None):
                     help="replay the device side of every iteration as ONE captured HIP graph per iteration shape instead of enqueuing "
                          "its launches (CompletionFit(graph_iteration=True)): same bits, one graph launch of host time per iteration; "
                          "completion / segmentation with --precision bf16 --trunk_precision fp16, not stacked")
+    ap.add_argument("--audit_stash", type=int, default=0, metavar="N",
+                    help="audit the 8-bit training stash on every N-th iteration (0, default: never; CompletionFit(stash_audit=N)): "
+                         "codes at the formats' limits and the distance of the iteration's weight gradients to the 16-bit stash's, one "
+                         "[STASH] line per audit and stash_audit.json in the image's result directory; --precision bf16 with the "
+                         "8-bit stash only, not stacked")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--save_model", action="store_true",
                     help="after a successful fit, write the network as model.npz into the image's result directory (npp_amd.render reads it)")
@@ -172,6 +177,11 @@ def _plan(argv=None):
     if args.graph_iteration:
         from .fit import refuse_graph_iteration
         refuse_graph_iteration(args.precision, args.trunk_precision, args.task, None, SystemExit, flag=True)
+    if args.audit_stash < 0:
+        raise SystemExit("--audit_stash N: N >= 0 (0: never)")
+    if args.audit_stash:
+        from .ops import refuse_stash_audit
+        refuse_stash_audit(args.precision, SystemExit, flag=True, capturing=False)
     seg_task = args.task == "segmentation"
     from . import weights
     names = ["vgg19"] + ([] if seg_task else ["vgg16"]) + (["alexnet"] if seg_task else [])    # remapping: VGG16 is the style trunk
@@ -251,7 +261,8 @@ def _build(plan, stacked=False):
                             no_pix_loss=args.no_pix_loss, use_contextual_loss=args.use_contextual_loss, width=args.netwidth,
                             loss_type=args.loss_type, use_adaptive_perceptual_loss=args.use_adaptive_perceptual_loss,
                             normalize_type=args.normalize_type, precision=args.precision,
-                            trunk_precision=args.trunk_precision, graph_iteration=args.graph_iteration)
+                            trunk_precision=args.trunk_precision, graph_iteration=args.graph_iteration,
+                            stash_audit=args.audit_stash)
     except BaseException:
         import shutil
         shutil.rmtree(outroot, ignore_errors=True)          # (nothing was fitted: a re-run must not take the directory for a result)
@@ -263,6 +274,7 @@ def _build(plan, stacked=False):
     job.writer, job.pending, job.t0, job.name = ThreadPoolExecutor(1), [], time.time(), name
     job.metrics = None                                       # --eval_metrics: the report of the newest test set
     job.lpips = None                                         # --eval_lpips: its LPIPSMetric
+    job.stash_printed = 0                                    # --audit_stash: iteration of the newest [STASH] line
     if args.eval_lpips is not None:
         # (the state dict is the one object weights.load_state_dict gave the fit's own trunks: with --eval_lpips vgg and an fp32 LPIPS
         # trunk in the loop the metric finds that trunk's packed weights; there is no second copy)
@@ -310,6 +322,13 @@ def _finish(job, failed):
         except Exception as e:
             write_error = write_error or e
             print(f"[WARN] writing metrics.json failed: {e}")
+    if failed is None and getattr(job.args, "audit_stash", 0):   # --audit_stash: every report, behind the stash format they speak of
+        try:
+            with open(os.path.join(job.outroot, "stash_audit.json"), "w") as f:
+                f.write(stash_audit_dumps(job.fit.stash_audits, stash_format(job.fit.net.width)) + "\n")
+        except Exception as e:
+            write_error = write_error or e
+            print(f"[WARN] writing stash_audit.json failed: {e}")
     # first the writers: a queued dump_testset re-creates its directory (os.makedirs(..., exist_ok=True)), so nothing is
     # removed while one may still run
     for p in job.pending:
@@ -371,7 +390,7 @@ def stack_key(job):
     """Fits that can share one launch sequence (stack.StackedFit): same network shape, batch shape, loss switches and schedule."""
     a, f = job.args, job.fit
     if (f.patch_sampler is None or f.use_patch_weight or not f.use_contextual_loss or f.net.out_act != 1 or f.net.precision != "bf16"
-            or f.trunk_precision != "fp16" or f.graph_iteration):
+            or f.trunk_precision != "fp16" or f.graph_iteration or f.stash_audit):       # (an audit needs the fit's own launch sequence)
         return None
     return (a.task, f.style is not None, f.style_w, f.pixel_mask is not None, f.net.K, f.net.width, f.N_rand, f.patch_size, f.patch_num, f.topk, f.net.quad, f.pix_w, f.use_comp, f.cx_w, f.lp_w,
             f.lp_robust, f.use_perceptual_loss, f.rng_mode, a.N_iters, a.i_testset, a.i_print, a.patch_size_decay, str(f.device))
@@ -489,6 +508,30 @@ def main_stacked(argvs, max_stack=8):
     return results
 
 
+def stash_format(width):
+    """What --audit_stash audits, in words a log can carry: the first entry of stash_audit.json."""
+    return {"stash": "8-bit (npp_tune stash8 = 1)", "layer_inputs": "fp8 e4m3 (OCP), largest finite 448, saturating conversion",
+            "pre_activation_gradients": "bf8 e5m2, largest finite 57344, saturating conversion, scaled per 64-row tile by a power of two "
+                                        "from max |dL/draw| of the tile",
+            "weight_gradients": "block-scaled fp8 MFMA, fp32 accumulate", "compared_with": "16-bit stash (fp16 z, bf16 gradients, bf16 MFMA)",
+            "width": int(width)}
+
+
+def stash_audit_dumps(reports, fmt):
+    """stash_audit.json: [{"stash_format": ...}, report, report, ...] (CompletionFit.stash_audits); json.loads gives the reports back."""
+    import json
+    return json.dumps([{"stash_format": fmt}] + [dict(r) for r in reports], indent=1)
+
+
+def stash_line(rep):
+    """The [STASH] line of one audit report."""
+    cen, ts = rep["census"], rep["tile_scale"]
+    at_max, nonfinite = (sum(c[k] for c in cen.values()) for k in ("at_max", "nonfinite"))
+    return (f"[STASH] it {rep['iteration']} ({rep['source']}, {rep['rows']} rows): worst gap {rep['worst'][0]} {rep['worst'][1]:.3e}, "
+            f"at_max {at_max}, nonfinite {nonfinite}, tile scale 2^{ts['scale_min'] - 127}..2^{ts['scale_max'] - 127}"
+            + ("".join(f" [{f}]" for f in rep["flags"])))
+
+
 def _after_iteration(job, i):
     """What follows optimizer.step() in the reference's loop body at iteration i: the periodic evaluation dump (train.py:270-331;
     segmentation: NPP_segmentation/train.py:337-406) and the progress line."""
@@ -530,6 +573,10 @@ def _after_iteration(job, i):
             vis = d["img"] * 0.7 + 0.3 * (np.array([0.0, 1.0, 0.0]) * m + d["img"] * (1 - m))    # :396-404
             nio.imsave(os.path.join(tdir, "segment.png"), vis * d["valid_mask"])
             fit.segmentation = r
+    audit = getattr(fit, "last_stash_audit", None)
+    if audit is not None and audit["iteration"] > job.stash_printed:
+        job.stash_printed = audit["iteration"]
+        print(stash_line(audit))
     if i % args.i_print == 0:
         print(f"[TRAIN] Iter: {i} Loss: {float(fit.net.loss_buf[0]):.6f} Patch Loss: {float(fit.last_patch_loss[0]):.6f} "
               f"({(time.time() - t0) / i * 1e3:.2f} ms/iter, skipped {fit.skipped})")
