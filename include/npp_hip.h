@@ -362,6 +362,12 @@ int npp_adam_step_net_pack(float* d_p, float* d_m, float* d_v, const float* d_gs
  *  accumulator.) */
 int npp_pack_scatter_host(const float* params, void* wf, void* wb, int K, int width);
 
+/* Host only, launches nothing: the two step-dependent scalars of every Adam entry of this library for 1-based step `step`,
+ * out[0] = step_size = lr / (1 - beta1^step), out[1] = 1 / sqrt(1 - beta2^step) -- the float arguments widened to double,
+ * pow / sqrt in double, each result rounded to float once.  These are the words the *_dev forms read from d_hp.
+ * NPP_ERR_ARG for step < 1 or a null out. */
+int npp_adam_words(float lr, float beta1, float beta2, int step, float out[2]);
+
 /* Same step with step_size = lr / (1 - b1^t) and 1 / sqrt(1 - b2^t) read from device memory
  * (d_hp[0], d_hp[1]): lets a captured HIP graph of one optimisation iteration be replayed. */
 int npp_adam_step_dev(float* d_p, float* d_m, float* d_v, const float* d_gslabs, int64_t n,

@@ -183,40 +183,11 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(AdamPackArgs a_in, NetDe
     adam_tail_block(a.tail, a.step_size, a.b1, a.b2, a.inv_sqrt_bc2, a.eps);
     return;
   }
-  typedef float vec_t __attribute__((ext_vector_type(4)));
   const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i >= a.n) return;
   const int cnt = (int)(a.n - i < 4 ? a.n - i : 4);       // 4, or the last n % 4 parameters (the count is odd)
-  float pn[4], mi[4], vi[4], gi[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (cnt == 4) {
-    auto ld = [&](int sl) { return *(const vec_t*)(a.g + (int64_t)sl * a.slab_stride + i); };
-    vec_t gs = (vec_t)(0.0f);
-    int sl = 0;
-    for (; sl + 4 <= a.n_slabs; sl += 4) {              // same summation order as adam_kernel<4>: bit-identical
-      const vec_t a0 = ld(sl), a1 = ld(sl + 1), a2 = ld(sl + 2), a3 = ld(sl + 3);
-      gs += a0; gs += a1; gs += a2; gs += a3;
-    }
-    for (; sl < a.n_slabs; ++sl) gs += ld(sl);
-    const vec_t m4 = *(const vec_t*)(a.m + i), v4 = *(const vec_t*)(a.v + i), p4 = *(const vec_t*)(a.p + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { gi[e] = gs[e]; mi[e] = m4[e]; vi[e] = v4[e]; pn[e] = p4[e]; }
-  } else {
-    for (int e = 0; e < cnt; ++e) {
-      float ge = 0.0f;
-      for (int sl = 0; sl < a.n_slabs; ++sl) ge += a.g[(int64_t)sl * a.slab_stride + i + e];
-      gi[e] = ge; mi[e] = a.m[i + e]; vi[e] = a.v[i + e]; pn[e] = a.p[i + e];
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if (e < cnt) pn[e] = adam_update(pn[e], mi[e], vi[e], gi[e], a.step_size, a.b1, a.b2, a.inv_sqrt_bc2, a.eps);
-  if (cnt == 4) {
-    *(vec_t*)(a.m + i) = (vec_t){mi[0], mi[1], mi[2], mi[3]};
-    *(vec_t*)(a.v + i) = (vec_t){vi[0], vi[1], vi[2], vi[3]};
-    *(vec_t*)(a.p + i) = (vec_t){pn[0], pn[1], pn[2], pn[3]};
-  } else {
-    for (int e = 0; e < cnt; ++e) { a.m[i + e] = mi[e]; a.v[i + e] = vi[e]; a.p[i + e] = pn[e]; }
-  }
+  float pn[4];
+  adam_quad(a.p, a.m, a.v, a.g, i, cnt, a.n_slabs, a.slab_stride, a.step_size, a.b1, a.b2, a.inv_sqrt_bc2, a.eps, pn);
   // ---- scatter into the packs: locate (layer, row, column) of the first element, then walk
   int l = 0;
 #pragma unroll
@@ -467,31 +438,47 @@ int npp_pack_scatter_host(const float* params, void* wf, void* wb, int K, int wi
   return NPP_OK;
 }
 
+// The fused launch behind the three npp_adam_step_net_pack* forms.  What they share is checked and filled here; `a` arrives with
+// what differs already set: {step_size, inv_sqrt_bc2}, or hp, or iter + the per-image strides (M images in grid.y).
+static int adam_pack_go(AdamPackArgs a, float* d_p, float* d_m, float* d_v, const float* d_gslabs, int64_t n, int n_slabs,
+                        int64_t slab_stride, const AdamTail& tail, float beta1, float beta2, float eps, int M, int K,
+                        void* d_wf, void* d_wb, void* stream, const char* who, const char* need) {
+  const NetDesc d = make_desc(K);                         // (K, width: checked by the entry point, first of all)
+  if (n != d.total_params || !d_p || !d_m || !d_v || !d_gslabs || !d_wf || !d_wb || n_slabs < 1 || tail.n < 0 || tail.n_zero < 0 ||
+      (tail.n > 0 && (!tail.p || !tail.m || !tail.v || !tail.g)) || (tail.n_zero > 0 && !tail.zero) || slab_stride % 4 ||
+      (((uintptr_t)d_p | (uintptr_t)d_m | (uintptr_t)d_v | (uintptr_t)d_gslabs) & 15)) {
+    set_error("%s: bad arguments (n=%lld, expected %lld parameters; %s)", who, (long long)n, (long long)d.total_params, need);
+    return NPP_ERR_ARG;
+  }
+  a.p = d_p; a.m = d_m; a.v = d_v; a.g = d_gslabs; a.n = n; a.n_slabs = n_slabs; a.slab_stride = slab_stride;
+  a.b1 = beta1; a.b2 = beta2; a.eps = eps;
+  a.tail = tail;
+  a.wf = (__bf16*)d_wf; a.wb = (__bf16*)d_wb;
+  for (int l = 0; l < kNumLayers; ++l) a.magic[l] = d.present[l] ? (uint32_t)((1ull << 32) / (uint64_t)d.n_in[l]) + 1u : 0u;
+  const int64_t threads = (n + 3) / 4;
+  hipLaunchKernelGGL(adam_pack_kernel, dim3((unsigned)((threads + 255) / 256 + 1), (unsigned)M), dim3(256), 0, (hipStream_t)stream, a, d,
+                     make_bwd_desc(K));
+  return check_launch(who);
+}
+static int adam_pack_bad(const char* who, const char* what) {
+  set_error("%s: bad arguments (%s)", who, what);
+  return NPP_ERR_ARG;
+}
+static const char* const kAdamPackNeed = "16-byte aligned blobs, slab stride % 4 == 0";
+
 int npp_adam_step_net_pack(float* d_p, float* d_m, float* d_v, const float* d_gslabs, int64_t n, int n_slabs,
                            int64_t slab_stride, float* d_lat, float* d_lat_m, float* d_lat_v, float* d_dlat, int n_lat,
                            float* d_zero, int n_zero, float lr, float beta1, float beta2, float eps, int step, int K,
                            int width, void* d_wf, void* d_wb, float* d_pl_partials, float* d_loss_cur, void* stream) {
   int rc = check_kw(K, width);
   if (rc) return rc;
-  const NetDesc d = make_desc(K);
-  if (n != d.total_params || !d_p || !d_m || !d_v || !d_gslabs || !d_wf || !d_wb || n_slabs < 1 || step < 1 || n_lat < 0 ||
-      n_zero < 0 || (n_lat > 0 && (!d_lat || !d_lat_m || !d_lat_v || !d_dlat)) || (n_zero > 0 && !d_zero) || slab_stride % 4 ||
-      (((uintptr_t)d_p | (uintptr_t)d_m | (uintptr_t)d_v | (uintptr_t)d_gslabs) & 15)) {
-    set_error("npp_adam_step_net_pack: bad arguments (n=%lld, expected %lld parameters; 16-byte aligned blobs, slab stride %% 4 == 0)",
-              (long long)n, (long long)d.total_params);
-    return NPP_ERR_ARG;
-  }
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+  if (step < 1) return adam_pack_bad("npp_adam_step_net_pack", "step < 1");
+  const AdamWords w = adam_words(lr, beta1, beta2, step);
   AdamPackArgs a{};
-  a.p = d_p; a.m = d_m; a.v = d_v; a.g = d_gslabs; a.n = n; a.n_slabs = n_slabs; a.slab_stride = slab_stride;
-  a.step_size = (float)((double)lr / bc1); a.b1 = beta1; a.b2 = beta2; a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2)); a.eps = eps;
-  a.tail = AdamTail{d_lat, d_lat_m, d_lat_v, d_dlat, n_lat, d_zero, n_zero, d_pl_partials, d_loss_cur};
-  a.wf = (__bf16*)d_wf; a.wb = (__bf16*)d_wb;
-  for (int l = 0; l < kNumLayers; ++l) a.magic[l] = d.present[l] ? (uint32_t)((1ull << 32) / (uint64_t)d.n_in[l]) + 1u : 0u;
-  const int64_t threads = (n + 3) / 4;
-  hipLaunchKernelGGL(adam_pack_kernel, dim3((unsigned)((threads + 255) / 256 + 1)), dim3(256), 0, (hipStream_t)stream, a, d,
-                     make_bwd_desc(K));
-  return check_launch("npp_adam_step_net_pack");
+  a.step_size = w.step_size; a.inv_sqrt_bc2 = w.inv_sqrt_bc2;
+  return adam_pack_go(a, d_p, d_m, d_v, d_gslabs, n, n_slabs, slab_stride,
+                      AdamTail{d_lat, d_lat_m, d_lat_v, d_dlat, n_lat, d_zero, n_zero, d_pl_partials, d_loss_cur}, beta1, beta2, eps,
+                      1, K, d_wf, d_wb, stream, "npp_adam_step_net_pack", kAdamPackNeed);
 }
 
 int npp_adam_step_net_pack_dev(float* d_p, float* d_m, float* d_v, const float* d_gslabs, int64_t n, int n_slabs,
@@ -500,24 +487,12 @@ int npp_adam_step_net_pack_dev(float* d_p, float* d_m, float* d_v, const float* 
                                int width, void* d_wf, void* d_wb, float* d_pl_partials, float* d_loss_cur, void* stream) {
   int rc = check_kw(K, width);
   if (rc) return rc;
-  const NetDesc d = make_desc(K);
-  if (n != d.total_params || !d_p || !d_m || !d_v || !d_gslabs || !d_wf || !d_wb || !d_hp || n_slabs < 1 || n_lat < 0 ||
-      n_zero < 0 || (n_lat > 0 && (!d_lat || !d_lat_m || !d_lat_v || !d_dlat)) || (n_zero > 0 && !d_zero) || slab_stride % 4 ||
-      (((uintptr_t)d_p | (uintptr_t)d_m | (uintptr_t)d_v | (uintptr_t)d_gslabs) & 15) || ((uintptr_t)d_hp & 3)) {
-    set_error("npp_adam_step_net_pack_dev: bad arguments (n=%lld, expected %lld parameters; 16-byte aligned blobs, slab stride %% 4 == 0)",
-              (long long)n, (long long)d.total_params);
-    return NPP_ERR_ARG;
-  }
+  if (!d_hp || ((uintptr_t)d_hp & 3)) return adam_pack_bad("npp_adam_step_net_pack_dev", "the device words: null or not 4-byte aligned");
   AdamPackArgs a{};
-  a.p = d_p; a.m = d_m; a.v = d_v; a.g = d_gslabs; a.n = n; a.n_slabs = n_slabs; a.slab_stride = slab_stride;
-  a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.hp = d_hp;
-  a.tail = AdamTail{d_lat, d_lat_m, d_lat_v, d_dlat, n_lat, d_zero, n_zero, d_pl_partials, d_loss_cur};
-  a.wf = (__bf16*)d_wf; a.wb = (__bf16*)d_wb;
-  for (int l = 0; l < kNumLayers; ++l) a.magic[l] = d.present[l] ? (uint32_t)((1ull << 32) / (uint64_t)d.n_in[l]) + 1u : 0u;
-  const int64_t threads = (n + 3) / 4;
-  hipLaunchKernelGGL(adam_pack_kernel, dim3((unsigned)((threads + 255) / 256 + 1)), dim3(256), 0, (hipStream_t)stream, a, d,
-                     make_bwd_desc(K));
-  return check_launch("npp_adam_step_net_pack_dev");
+  a.hp = d_hp;
+  return adam_pack_go(a, d_p, d_m, d_v, d_gslabs, n, n_slabs, slab_stride,
+                      AdamTail{d_lat, d_lat_m, d_lat_v, d_dlat, n_lat, d_zero, n_zero, d_pl_partials, d_loss_cur}, beta1, beta2, eps,
+                      1, K, d_wf, d_wb, stream, "npp_adam_step_net_pack_dev", kAdamPackNeed);
 }
 
 int npp_adam_step_net_pack_stack(float* d_p, float* d_m, float* d_v, int64_t blob_stride, const float* d_gslabs, int64_t n,
@@ -528,29 +503,16 @@ int npp_adam_step_net_pack_stack(float* d_p, float* d_m, float* d_v, int64_t blo
                                  int64_t pl_stride, float* d_loss_cur, const void* d_iter, void* stream) {
   int rc = check_kw(K, width);
   if (rc) return rc;
-  const NetDesc d = make_desc(K);
-  if (n != d.total_params || !d_p || !d_m || !d_v || !d_gslabs || !d_wf || !d_wb || !d_iter || n_slabs < 1 || n_lat < 0 || n_zero < 0 ||
-      M < 1 || M > NPP_MAX_STACK || (n_lat > 0 && (!d_lat || !d_lat_m || !d_lat_v || !d_dlat)) || (n_zero > 0 && !d_zero) ||
-      slab_stride % 4 || blob_stride % 4 || slab_img_stride % 4 || blob_stride < n || wf_stride_bytes % 16 || wb_stride_bytes % 16 ||
-      (((uintptr_t)d_p | (uintptr_t)d_m | (uintptr_t)d_v | (uintptr_t)d_gslabs) & 15)) {
-    set_error("npp_adam_step_net_pack_stack: bad arguments (n=%lld, expected %lld parameters; 16-byte aligned blobs and strides)",
-              (long long)n, (long long)d.total_params);
-    return NPP_ERR_ARG;
-  }
+  if (!d_iter || M < 1 || M > NPP_MAX_STACK || blob_stride % 4 || slab_img_stride % 4 || blob_stride < n || wf_stride_bytes % 16 ||
+      wb_stride_bytes % 16)
+    return adam_pack_bad("npp_adam_step_net_pack_stack", "M, the iteration records or the per-image strides");
   AdamPackArgs a{};
-  a.p = d_p; a.m = d_m; a.v = d_v; a.g = d_gslabs; a.n = n; a.n_slabs = n_slabs; a.slab_stride = slab_stride;
-  a.b1 = beta1; a.b2 = beta2; a.eps = eps;
-  a.tail = AdamTail{d_lat, d_lat_m, d_lat_v, d_dlat, n_lat, d_zero, n_zero, d_pl_partials, d_loss_cur};
-  a.pl_stride = pl_stride;
-  a.wf = (__bf16*)d_wf; a.wb = (__bf16*)d_wb;
   a.iter = (const StackIter*)d_iter;
   a.blob_stride = blob_stride; a.slab_img_stride = slab_img_stride; a.wf_stride = wf_stride_bytes / 2; a.wb_stride = wb_stride_bytes / 2;
-  a.lat_stride = lat_stride; a.zero_stride = zero_stride;
-  for (int l = 0; l < kNumLayers; ++l) a.magic[l] = d.present[l] ? (uint32_t)((1ull << 32) / (uint64_t)d.n_in[l]) + 1u : 0u;
-  const int64_t threads = (n + 3) / 4;
-  hipLaunchKernelGGL(adam_pack_kernel, dim3((unsigned)((threads + 255) / 256 + 1), (unsigned)M), dim3(256), 0, (hipStream_t)stream, a, d,
-                     make_bwd_desc(K));
-  return check_launch("npp_adam_step_net_pack_stack");
+  a.lat_stride = lat_stride; a.zero_stride = zero_stride; a.pl_stride = pl_stride;
+  return adam_pack_go(a, d_p, d_m, d_v, d_gslabs, n, n_slabs, slab_stride,
+                      AdamTail{d_lat, d_lat_m, d_lat_v, d_dlat, n_lat, d_zero, n_zero, d_pl_partials, d_loss_cur}, beta1, beta2, eps,
+                      M, K, d_wf, d_wb, stream, "npp_adam_step_net_pack_stack", "16-byte aligned blobs and strides");
 }
 
 int npp_train_workspace(int K, int width, int64_t Bp, int ksplit, int64_t sizes[4]) {

@@ -121,12 +121,11 @@ struct LightLatentArgs {
   float step_size, b1, b2, inv_sqrt_bc2, eps;             // torch.optim.Adam's single-tensor maths (adam_update, npp_common.h): the weights' too
   const float* part; int32_t n_part; float* loss_cur;     // the _det forms: the blocks' partial sums of light_loss_head, added here in block order
 };
-// Adam's step-dependent scalars as npp_adam_step computes them on the host
+// Adam's step-dependent scalars: adam_words (npp_common.h), as in npp_adam_step
 static inline LightLatentArgs light_latent_args(float* d_lat, float* d_lat_m, float* d_lat_v, float* d_dlat, float* d_zero, float lr, float beta1,
                                          float beta2, float eps, int step, const float* d_part, int n_part, float* d_loss_cur) {
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  return LightLatentArgs{d_lat, d_lat_m, d_lat_v, d_dlat, d_zero, (float)((double)lr / bc1), beta1, beta2, (float)(1.0 / sqrt(bc2)), eps,
-                         d_part, n_part, d_loss_cur};
+  const AdamWords w = adam_words(lr, beta1, beta2, step);
+  return LightLatentArgs{d_lat, d_lat_m, d_lat_v, d_dlat, d_zero, w.step_size, beta1, beta2, w.inv_sqrt_bc2, eps, d_part, n_part, d_loss_cur};
 }
 // steps candidate c's six adaptive-loss latents and clears one loss word
 __device__ __forceinline__ void light_latent_step(const LightLatentArgs& a, int c) {

@@ -33,9 +33,9 @@ __global__ __launch_bounds__(256) void pixel_loss_batched_kernel(PixelLossArgs a
 // latents, whose gradient accumulator is consumed and cleared -- and an accumulator to clear for the
 // next iteration, so that one launch replaces optimizer.step() over both groups plus zero_grad().
 // (AdamTail, adam_tail_block: npp_common.h -- shared with the fused Adam + re-pack launch of npp_api.hip)
-// VEC = 4: one float4 per thread and array (n, slab_stride multiples of 4, 16-byte aligned pointers), four slab loads in
-// flight before the (order-preserving, hence bit-identical) summation: the kernel is a pure HBM stream of
-// (n_slabs + 5) * 4 B per parameter.
+// VEC = 4: one float4 per thread and array (slab_stride a multiple of 4, 16-byte aligned pointers; the last n % 4 elements go
+// one by one), four slab loads in flight before the order-preserving summation: the kernel is a pure HBM stream of
+// (n_slabs + 5) * 4 B per parameter.  VEC = 1: an element per thread.  (adam_quad, slab_sum: npp_common.h)
 template <int VEC>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ m,
                                                    float* __restrict__ v, const float* __restrict__ g,
@@ -47,43 +47,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
     adam_tail_block(tail, step_size, b1, b2, inv_sqrt_bc2, eps);
     return;
   }
-  typedef float vec_t __attribute__((ext_vector_type(VEC)));
   const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
   if (i >= n) return;
-  if (VEC > 1 && i + VEC > n) {                            // the last n % VEC elements (the parameter count is odd): scalar
-    for (int64_t e = i; e < n; ++e) {
-      float ge = 0.0f;
-      for (int sl = 0; sl < n_slabs; ++sl) ge += g[(int64_t)sl * slab_stride + e];
-      const float me = b1 * m[e] + (1.0f - b1) * ge;
-      const float ve = b2 * v[e] + (1.0f - b2) * ge * ge;
-      m[e] = me;
-      v[e] = ve;
-      p[e] = p[e] - step_size * (me / (sqrtf(ve) * inv_sqrt_bc2 + eps));
-    }
-    return;
-  }
-  auto ld = [&](int sl) { return *(const vec_t*)(g + (int64_t)sl * slab_stride + i); };
-  vec_t gi = (vec_t)(0.0f);
-  int sl = 0;
-  for (; sl + 4 <= n_slabs; sl += 4) {
-    const vec_t a0 = ld(sl), a1 = ld(sl + 1), a2 = ld(sl + 2), a3 = ld(sl + 3);
-    gi += a0; gi += a1; gi += a2; gi += a3;
-  }
-  for (; sl < n_slabs; ++sl) gi += ld(sl);
-  vec_t mi = *(const vec_t*)(m + i), vi = *(const vec_t*)(v + i), pi = *(const vec_t*)(p + i);
-#pragma unroll
-  for (int e = 0; e < VEC; ++e) {
-    const float ge = gi[e];
-    const float me = b1 * mi[e] + (1.0f - b1) * ge;
-    const float ve = b2 * vi[e] + (1.0f - b2) * ge * ge;
-    mi[e] = me;
-    vi[e] = ve;
-    const float denom = sqrtf(ve) * inv_sqrt_bc2 + eps;
-    pi[e] = pi[e] - step_size * (me / denom);
-  }
-  *(vec_t*)(m + i) = mi;
-  *(vec_t*)(v + i) = vi;
-  *(vec_t*)(p + i) = pi;
+  float pn[4];
+  adam_quad(p, m, v, g, i, (int)(n - i < VEC ? n - i : VEC), n_slabs, slab_stride, step_size, b1, b2, inv_sqrt_bc2, eps, pn);
 }
 
 static void adam_launch(float* p, float* m, float* v, const float* g, int64_t n, int n_slabs, int64_t slab_stride,
@@ -190,10 +157,8 @@ extern "C" int npp_adam_step(float* d_p, float* d_m, float* d_v, const float* d_
     set_error("npp_adam_step: bad arguments");
     return NPP_ERR_ARG;
   }
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  const float step_size = (float)((double)lr / bc1);
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  adam_launch(d_p, d_m, d_v, d_gslabs, n, n_slabs, slab_stride, step_size, beta1, beta2, inv_sqrt_bc2, eps, nullptr,
+  const AdamWords w = adam_words(lr, beta1, beta2, step);
+  adam_launch(d_p, d_m, d_v, d_gslabs, n, n_slabs, slab_stride, w.step_size, beta1, beta2, w.inv_sqrt_bc2, eps, nullptr,
               AdamTail{}, false, (hipStream_t)stream);
   return check_launch("npp_adam_step");
 }
@@ -207,11 +172,9 @@ extern "C" int npp_adam_step_net(float* d_p, float* d_m, float* d_v, const float
     set_error("npp_adam_step_net: bad arguments");
     return NPP_ERR_ARG;
   }
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  const float step_size = (float)((double)lr / bc1);
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  const AdamWords w = adam_words(lr, beta1, beta2, step);
   const AdamTail tail{d_lat, d_lat_m, d_lat_v, d_dlat, n_lat, d_zero, n_zero};
-  adam_launch(d_p, d_m, d_v, d_gslabs, n, n_slabs, slab_stride, step_size, beta1, beta2, inv_sqrt_bc2, eps, nullptr, tail,
+  adam_launch(d_p, d_m, d_v, d_gslabs, n, n_slabs, slab_stride, w.step_size, beta1, beta2, w.inv_sqrt_bc2, eps, nullptr, tail,
               true, (hipStream_t)stream);
   return check_launch("npp_adam_step_net");
 }
@@ -226,6 +189,17 @@ extern "C" int npp_adam_step_dev(float* d_p, float* d_m, float* d_v, const float
   adam_launch(d_p, d_m, d_v, d_gslabs, n, n_slabs, slab_stride, 0.0f, beta1, beta2, 0.0f, eps, d_hp, AdamTail{}, false,
               (hipStream_t)stream);
   return check_launch("npp_adam_step_dev");
+}
+
+extern "C" int npp_adam_words(float lr, float beta1, float beta2, int step, float out[2]) {
+  if (step < 1 || !out) {
+    set_error("npp_adam_words: bad arguments (step=%d)", step);
+    return NPP_ERR_ARG;
+  }
+  const AdamWords w = adam_words(lr, beta1, beta2, step);
+  out[0] = w.step_size;
+  out[1] = w.inv_sqrt_bc2;
+  return NPP_OK;
 }
 
 extern "C" int npp_grad_reduce(const float* d_gslabs, int n_slabs, int64_t slab_stride, int64_t n, float* d_grad,

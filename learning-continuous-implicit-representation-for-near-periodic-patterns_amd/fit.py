@@ -618,9 +618,7 @@ class CompletionFit:
             xy = self._xy                                         # the fp32 batch is what the fp32 trunks read
         ws = net.workspace(bp)
         pred = net.forward_train(b["coords"])
-        if ws.get("n_rows") != n:                                # rows >= n never receive a gradient
-            ws["dpred"][n:].zero_()
-            ws["n_rows"] = n
+        net.clear_dpred_tail(bp, n)
         # The consumers of the prediction are independent and each under-fills the chip (small grids, dependent
         # launches): on 'same' iterations the LPIPS branch runs on a side stream next to the contextual branch and
         # joins before npp_patch_compose_bwd (1.30 -> 1.17 ms).  Measured negative (event record / wait costs more than is
@@ -758,9 +756,7 @@ class CompletionFit:
         if lp.touched:
             lp.zero_latent_grads()
         ws = net.workspace(bp)
-        if ws.get("n_rows") != n:                                # rows >= n never receive a gradient
-            ws["dpred"][n:].zero_()
-            ws["n_rows"] = n
+        net.clear_dpred_tail(bp, n)
         with_lp = source == "same" and self.use_perceptual_loss
         comp = self.use_comp and source == "val"
         # ---- the scalar record
@@ -814,7 +810,7 @@ class CompletionFit:
         # ---- the host's side of optimizer.step(): what the eager loop leaves
         net.optimizer_advance()
         if lp.touched:
-            lp.lat_step += 1
+            lp.adam_advance()
         ev = torch.cuda.Event()
         ev.record(stream)
         self._rec_ev[i] = st["free"] = ev

@@ -199,20 +199,18 @@ class NPPNetLight:
 
     def advance_clock(self):
         """The host half of an optimiser step: the LR rule of search.py:139-147 (set AFTER the step) and global_step += 1."""
-        self.lr = self.lrate * (0.1 ** (self.global_step / (self.lrate_decay * 100)))
+        self.lr = ops.lr_rule(self.lrate, self.lrate_decay, self.global_step)
         self.global_step += 1
 
     def adam_scalars(self, n_steps, b1=0.9, b2=0.999):
-        """(n_steps, 2) float32: [lr_t / (1 - b1^t), 1 / sqrt(1 - b2^t)] of the NEXT n_steps optimiser steps -- exactly the values
-        npp_adam_step computes on the host from (lr, step) -- without advancing the clock."""
+        """(n_steps, 2) float32: [lr_t / (1 - b1^t), 1 / sqrt(1 - b2^t)] of the NEXT n_steps optimiser steps, without advancing the
+        clock: row i is ops.adam_words(lr, opt_step + 1 + i) -- npp_adam_step's own host values, bit for bit -- for the lr that
+        advance_clock() will have set by then."""
         out = np.zeros((n_steps, 2), np.float32)
         lr, gs = self.lr, self.global_step
         for i in range(n_steps):
-            t = self.opt_step + 1 + i
-            out[i, 0] = np.float32(float(lr) / (1.0 - b1 ** t))
-            out[i, 1] = np.float32(1.0 / np.sqrt(1.0 - b2 ** t))
-            lr = self.lrate * (0.1 ** (gs / (self.lrate_decay * 100)))
-            gs += 1
+            out[i] = ops.adam_words(lr, self.opt_step + 1 + i, b1, b2)
+            lr, gs = ops.lr_rule(self.lrate, self.lrate_decay, gs), gs + 1
         return out
 
     @torch.no_grad()
@@ -405,8 +403,7 @@ class NPPNetLightBatch:
             if log is not None:
                 log.append(self._loss2[li].clone())
             li ^= 1
-            lr = n0.lrate * (0.1 ** (gstp / (n0.lrate_decay * 100)))                          # NPPNetLight.advance_clock
-            gstp += 1
+            lr, gstp = ops.lr_rule(n0.lrate, n0.lrate_decay, gstp), gstp + 1                  # NPPNetLight.advance_clock
         self._li = li
         self._pack16_valid, self._pack_valid = True, False
         for net in self.nets:
@@ -708,9 +705,10 @@ class ProposalRanker:
         layer-by-layer path below: ~40 small dependent launches on 2048 rows, 0.39 ms per iteration.
         use_graph=True: iterations 2 .. N replay ONE captured HIP graph (torch.cuda.CUDAGraph: the same
         kernels in the same order; the iteration's inputs -- pixel-row indices, Adam's step-dependent scalars -- are read from
-        fixed device buffers).  Built in round 3 on the hypothesis that the host's enqueue rate bounded the loop; MEASURED: it does
-        not -- eager 0.400 ms per iteration, graph replay 0.417-0.44 (profiles/r03_rejected_experiments.txt): the device time of the
-        twenty 2048 x 256 x 256 exact-fp32 GEMM launches (14-18 us each) is the bound.  Kept as an option (parity-tested), off."""
+        fixed device buffers; the scalars are adam_scalars(): the eager loop's own words).  Built in round 3 on the hypothesis
+        that the host's enqueue rate bounded the loop; MEASURED: it does not -- eager 0.400 ms per iteration, graph replay 0.417-0.44
+        (profiles/r03_rejected_experiments.txt): the device time of the twenty 2048 x 256 x 256 exact-fp32 GEMM launches (14-18 us
+        each) is the bound.  Kept as an option (parity-tested), off."""
         use_graph = bool(use_graph)
         if fused is None:
             fused = (not use_graph and self.Wn == 256 and self.D == 4

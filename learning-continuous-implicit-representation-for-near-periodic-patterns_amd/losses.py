@@ -575,19 +575,47 @@ class _LPIPSLayerFunction(torch.autograd.Function):
         return df0 * g, None, None, None, None
 
 
-def _latent_blobs(inits, dev):
-    """The adaptive-loss latents of several taps / levels as views of ONE blob each for the values, their gradients and the two Adam
-    moments: optimizer.step() and zero_grad() over them are one launch each instead of one per tap (found in the kernel trace of the
-    'same'-source iterations: 5 Adam launches + 5 fills of ~4.8 us for 2944 latents)."""
-    sizes = [int(t.numel()) for t in inits]
-    lat = torch.cat([t.reshape(-1).to(torch.float32) for t in inits]).to(dev)
-    blobs = (lat, torch.zeros_like(lat), torch.zeros_like(lat), torch.zeros_like(lat))
-    offs = np.concatenate([[0], np.cumsum(sizes)])
-    views = tuple([b[int(offs[i]):int(offs[i + 1])] for i in range(len(sizes))] for b in blobs)
-    return blobs, views
+class LatentGroup:
+    """One group of adaptive-loss latents with its Adam state (a parameter group of the reference's optimiser, helpers.py:153-159;
+    mixed into LPIPS and StyleLoss, or used by itself).  The latents of the taps / levels are views of ONE blob each for the values,
+    their gradients and the two Adam moments -- _lat, _dlat, _lat_m, _lat_v; per tap: latents, dlatents, lat_m, lat_v -- so that
+    optimizer.step() and zero_grad() over them are one launch each instead of one per tap (found in the kernel trace of the
+    'same'-source iterations: 5 Adam launches + 5 fills of ~4.8 us for 2944 latents).  lat_step: the group's Adam step count."""
+
+    def __init__(self, inits, dev):
+        sizes = [int(t.numel()) for t in inits]
+        lat = torch.cat([t.reshape(-1).to(torch.float32) for t in inits]).to(dev)
+        blobs = (lat, torch.zeros_like(lat), torch.zeros_like(lat), torch.zeros_like(lat))
+        offs = np.concatenate([[0], np.cumsum(sizes)])
+        views = tuple([b[int(offs[i]):int(offs[i + 1])] for i in range(len(sizes))] for b in blobs)
+        self._lat, self._dlat, self._lat_m, self._lat_v = blobs
+        self.latents, self.dlatents, self.lat_m, self.lat_v = views
+        self.lat_step = 0
+
+    def zero_latent_grads(self):
+        self._dlat.zero_()                              # one fill over the blob
+
+    def adam_step(self, lr):
+        """Adam over the group, one launch; a group is only stepped when it received a gradient this iteration (torch skips parameters
+        whose grad is None: their step count does not advance)."""
+        ops.adam_step(self._lat, self._lat_m, self._lat_v, self._dlat, 1, self._lat.numel(), lr, self.lat_step + 1)
+        self.adam_advance()
+
+    # the same step for a captured iteration (fit.CompletionFit(graph_iteration=True)): a capture records the launch, a replay runs
+    # it, the host counts once
+    def step_words(self, lr):
+        """(step_size, 1 / sqrt(1 - b2^t)) of the NEXT adam_step(lr) (ops.adam_words): the device words of adam_launch_dev."""
+        return ops.adam_words(lr, self.lat_step + 1)
+
+    def adam_launch_dev(self, hp):
+        """The launch of adam_step() with its scalars from the device words hp[0:2] (npp_adam_step_dev); adam_advance() is the host half."""
+        ops.adam_step_dev(self._lat, self._lat_m, self._lat_v, self._dlat, 1, self._lat.numel(), hp)
+
+    def adam_advance(self):
+        self.lat_step += 1
 
 
-class LPIPS(nn.Module):
+class LPIPS(nn.Module, LatentGroup):
     """LPIPS(net='vgg') with the reference's adaptive-robust head.  forward(in0, in1, use_robust,
     normalize) returns the batch MEAN as a scalar (the caller's torch.mean, train.py:249, is folded in)."""
     chns = [64, 128, 256, 512, 512]
@@ -607,9 +635,7 @@ class LPIPS(nn.Module):
             lin_weights = [np.abs(rng.randn(c)).astype(np.float32) * 0.05 for c in self.chns]
         self.lins = [torch.as_tensor(np.asarray(w, np.float32).reshape(-1)).to(dev) for w in lin_weights]
         # AdaptiveLossFunction(num_dims=chn) per tap (lpips.py:57-61): [latent_alpha(C) | latent_scale(C)]
-        (self._lat, self._dlat, self._lat_m, self._lat_v), (self.latents, self.dlatents, self.lat_m, self.lat_v) = _latent_blobs(
-            [torch.cat([torch.full((c,), 2.3841858e-07), torch.zeros(c)]) for c in self.chns], dev)
-        self.lat_step = 0
+        LatentGroup.__init__(self, [torch.cat([torch.full((c,), 2.3841858e-07), torch.zeros(c)]) for c in self.chns], dev)
         self.touched = False
         # comparator switches of tests/test_gpu_parity.py (all bit-identical; the defaults are the measured-best forms): one launch per
         # head; tap gradients as fp32 tensors through npp_trunk_grad_in instead of written flat by the heads launch
@@ -721,29 +747,14 @@ class LPIPS(nn.Module):
         return out
 
     def zero_latent_grads(self):
-        self._dlat.zero_()                              # one fill: the per-tap vectors are views of one blob (_latent_blobs)
+        LatentGroup.zero_latent_grads(self)
         self.touched = False
-
-    def adam_step(self, lr):
-        """Adam over the robust latents; only called when they received a gradient this iteration
-        (torch skips parameters whose grad is None: their step count does not advance).  One launch over the blob of all taps."""
-        self.lat_step += 1
-        ops.adam_step(self._lat, self._lat_m, self._lat_v, self._dlat, 1, self._lat.numel(), lr, self.lat_step)
-
-    def step_words(self, lr):
-        """(step_size, 1 / sqrt(1 - b2^t)) of the NEXT adam_step(lr), as npp_adam_step computes them: the device words of adam_launch_dev."""
-        return ops.adam_words(lr, self.lat_step + 1)
-
-    def adam_launch_dev(self, hp):
-        """The launch of adam_step() with its scalars from the device words hp[0:2] (npp_adam_step_dev); the caller advances lat_step
-        (a captured iteration, fit.CompletionFit(graph_iteration=True): a capture records, a replay runs, the host counts once)."""
-        ops.adam_step_dev(self._lat, self._lat_m, self._lat_v, self._dlat, 1, self._lat.numel(), hp)
 
 
 _VGG16_STYLE = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M"]          # vgg16.features[:17]: enc_1 | enc_2 | enc_3
 
 
-class StyleLoss:
+class StyleLoss(LatentGroup):
     """models/style_loss.py VGG16FeatureExtractor.style_loss with use_adaptive=True (the remapping task's extra patch loss,
     NPP_remapping/train.py:253-261): VGG16 features[:5], [5:10], [10:17] (the three POOLED tensors; inputs are used as
     they are, no mean / std normalisation) -> Gram matrices -> per-element adaptive robust NLL of their difference with
@@ -756,9 +767,7 @@ class StyleLoss:
         self.trunk_precision = trunk_precision
         self.hip_trunk = _trunk_class(trunk_precision)(_VGG16_STYLE, taps=(4, 9, 16), state_dict=vgg_state_dict, seed=seed, device=self.device)
         # AdaptiveLossFunction(num_dims = chn ** 2) per level (style_loss.py:23-27): [latent_alpha(D) | latent_scale(D)]
-        (self._lat, self._dlat, self._lat_m, self._lat_v), (self.latents, self.dlatents, self.lat_m, self.lat_v) = _latent_blobs(
-            [torch.cat([torch.full((c * c,), 2.3841858e-07), torch.zeros(c * c)]) for c in self.chns], self.device)
-        self.lat_step = 0
+        LatentGroup.__init__(self, [torch.cat([torch.full((c * c,), 2.3841858e-07), torch.zeros(c * c)]) for c in self.chns], self.device)
         self.spline, self.n_knots, self.x_scale = ops.load_spline(self.device)
 
     def head(self, feats, n, scale, loss_buf, weight=None, want_grad=True):
@@ -787,10 +796,3 @@ class StyleLoss:
         feats = t._forward(xy, ones, zeros, n_keep=n)
         dfs = self.head(feats, n, scale, loss_buf, weight)
         return t._backward(dfs, n, ones, tuple(xy.shape), zero_rest=False)
-
-    def zero_latent_grads(self):
-        self._dlat.zero_()
-
-    def adam_step(self, lr):
-        self.lat_step += 1
-        ops.adam_step(self._lat, self._lat_m, self._lat_v, self._dlat, 1, self._lat.numel(), lr, self.lat_step)

@@ -119,23 +119,24 @@ class NPPNet:
         self.params.copy_(torch.from_numpy(flat))
         self.repack()
 
-    def state_dict(self):
-        flat = self.params.detach().cpu().numpy()
+    def _named(self, flat):
+        """A host blob as a reference-named dict: weights (rows, cols), biases flat."""
         out = {}
         for name, off, rows, cols in self.layout:
             a = flat[off:off + rows * cols]
             out[name] = a.reshape(rows, cols).copy() if name.endswith("weight") else a.copy()
         return out
 
+    def state_dict(self):
+        return self._named(self.params.detach().cpu().numpy())
+
+    def _slab_sum(self, gslabs):
+        """The gradient blob a slab buffer holds: the sum of its split-K slabs (slab stride = n_params rounded up to 4)."""
+        return gslabs.view(self.ksplit, -1)[:, :self.n_params].sum(0)
+
     def grads(self):
         """Sum of the split-K slabs, as a reference-named dict (for tests)."""
-        ws = self._ws_last
-        g = ws["gslabs"].view(self.ksplit, -1)[:, :self.n_params].sum(0).cpu().numpy()     # slab stride = n_params rounded up to 4
-        out = {}
-        for name, off, rows, cols in self.layout:
-            a = g[off:off + rows * cols]
-            out[name] = a.reshape(rows, cols).copy() if name.endswith("weight") else a.copy()
-        return out
+        return self._named(self._slab_sum(self._ws_last["gslabs"]).cpu().numpy())
 
     def repack(self):
         if self.precision == "fp32":
@@ -173,6 +174,13 @@ class NPPNet:
             self._ws[Bp] = ws
         self._ws_last = ws
         return ws
+
+    def clear_dpred_tail(self, Bp, n_rows):
+        """Rows >= n_rows of workspace Bp's dL/dpred never receive a gradient: cleared when the batch's row count changes."""
+        ws = self._ws[Bp]
+        if ws.get("n_rows") != n_rows:
+            ws["dpred"][n_rows:].zero_()
+            ws["n_rows"] = n_rows
 
     # ---- the path ---------------------------------------------------------------------
     def render(self, coords):
@@ -337,8 +345,8 @@ class NPPNet:
         finally:
             ops.tune("stash8", old)
         self._ws_gap = ws
-        g8 = ws["gslabs"].view(self.ksplit, -1)[:, :self.n_params].sum(0).double()      # the sums grads() forms, then float64
-        g16 = ws["gslabs16"].view(self.ksplit, -1)[:, :self.n_params].sum(0).double()
+        g8 = self._slab_sum(ws["gslabs"]).double()      # the sums grads() forms, then float64
+        g16 = self._slab_sum(ws["gslabs16"]).double()
         d = g8 - g16
         num = torch.stack([torch.linalg.vector_norm(d[off:off + rows * cols]) for _, off, rows, cols in self.layout])
         den = torch.stack([torch.linalg.vector_norm(g16[off:off + rows * cols]) for _, off, rows, cols in self.layout])
@@ -347,12 +355,7 @@ class NPPNet:
 
     def stash_gap_grads16(self):
         """The 16-bit leg's gradients of the last stash_gap(), in the form of grads() (for tests)."""
-        g = self._ws_gap["gslabs16"].view(self.ksplit, -1)[:, :self.n_params].sum(0).cpu().numpy()
-        out = {}
-        for name, off, rows, cols in self.layout:
-            a = g[off:off + rows * cols]
-            out[name] = a.reshape(rows, cols).copy() if name.endswith("weight") else a.copy()
-        return out
+        return self._named(self._slab_sum(self._ws_gap["gslabs16"]).cpu().numpy())
 
     def pixel_loss(self, Bp, n_rows, gt, mask=None, weight=1.0):
         """img2mse on the first n_rows rows of the current prediction (train.py:195);
@@ -374,12 +377,11 @@ class NPPNet:
     def optimizer_step(self, Bp):
         """optimizer.step() + the LR rule of train.py:253-263 + global_step += 1 (:337)."""
         ws = self._ws[Bp]
-        self.opt_step += 1
         idle = self._loss_bufs[1 - self._loss_idx:2 - self._loss_idx]
         self._adam(ws["gslabs"], self.ksplit, ws["gslabs"].numel() // self.ksplit, idle)
-        self.lr = self.lrate * (0.1 ** (self.global_step / (self.lrate_decay * 100)))
-        if self.lr_clock:
-            self.global_step += 1
+        self.optimizer_advance()
+        if not self.fused_repack:
+            self.repack()                # after the advance: the fp32 packs are stamped with the step count they belong to
 
     # ---- the same step for a captured iteration (fit.CompletionFit(graph_iteration=True)): launch and host record apart ----
     def step_words(self):
@@ -402,25 +404,24 @@ class NPPNet:
     def optimizer_advance(self):
         """What optimizer_step() leaves on the host: the step count, the LR rule of train.py:253-263, global_step (:337)."""
         self.opt_step += 1
-        self.lr = self.lrate * (0.1 ** (self.global_step / (self.lrate_decay * 100)))
+        self.lr = ops.lr_rule(self.lrate, self.lrate_decay, self.global_step)
         if self.lr_clock:
             self.global_step += 1
         self._clean = True
 
     def _adam(self, gslabs, n_slabs, stride, idle):
-        """optimizer.step() over the blob + latents and the re-pack of the bf16 MFMA packs: one launch (fused_repack, default)
-        or two (npp_adam_step_net, then npp_pack_weights: the comparator)."""
+        """The launch of optimizer.step() number opt_step + 1 over the blob + latents: with the re-pack of the bf16 MFMA packs
+        in it (fused_repack, default), or npp_adam_step_net alone (the comparator: optimizer_step() re-packs after it).  The
+        caller advances the host record (optimizer_advance)."""
         if self.fused_repack:
             # (the pixel-loss launch of a folded iteration left its block partials in _pl_scratch: summed here in block order;
             #  the buffer's count word is zero whenever no such launch ran since the last step)
             ops.adam_step_net_pack(self.params, self.m, self.v, gslabs, n_slabs, stride, self.latents, self.lat_m, self.lat_v,
-                                   self.dlatent, idle, self.lr, self.opt_step, self.K, self.wf, self.wb, self.width,
+                                   self.dlatent, idle, self.lr, self.opt_step + 1, self.K, self.wf, self.wb, self.width,
                                    pl_partials=getattr(self, "_pl_scratch", None), loss_cur=self.loss_buf)
         else:
             ops.adam_step_net(self.params, self.m, self.v, gslabs, n_slabs, stride, self.latents, self.lat_m, self.lat_v,
-                              self.dlatent, idle, self.lr, self.opt_step)
-            self.repack()
-        self._clean = True
+                              self.dlatent, idle, self.lr, self.opt_step + 1)
 
     @property
     def loss_buf(self):

@@ -551,6 +551,12 @@ def adam_words(lr, step, b1=0.9, b2=0.999):
     return np.float32(lr / bc1), np.float32(1.0 / math.sqrt(bc2))
 
 
+def lr_rule(lrate, lrate_decay, global_step):
+    """The learning rate of the step after `global_step` schedule ticks (train.py:256-262): the one statement of the schedule; the
+    fits' clocks (NPPNet.optimizer_advance, NPPNetLight.advance_clock) call it and then tick."""
+    return lrate * (0.1 ** (global_step / (lrate_decay * 100)))
+
+
 def adam_step_net_pack_dev(p, m, v, gslabs, n_slabs, slab_stride, lat, lat_m, lat_v, dlat, zero, hp, K, wf, wb, width=NPP_WIDTH,
                            b1=0.9, b2=0.999, eps=1e-8, pl_partials=None, loss_cur=None):
     """adam_step_net_pack whose step_size / bias correction come from the device tensor hp[0:2] (adam_words): the form a captured

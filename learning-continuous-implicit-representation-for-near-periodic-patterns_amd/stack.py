@@ -14,7 +14,6 @@ working) and replaces CompletionFit.step_full for all of them.  Per image the ar
 launch; tests/test_gpu_stack.py compares the parameters after 20 iterations with each image's stand-alone fit.
 """
 import ctypes as C
-import math
 
 import numpy as np
 import torch
@@ -320,13 +319,7 @@ class StackedFit:
             # with_lp: the image has a second patch-gradient term (LPIPS on 'same' iterations, the style term on every one) and
             # its fp32 batch is written for that branch
             e.with_lp = int((src == "same" and f.use_perceptual_loss) or f.style is not None)
-            net.opt_step += 1
-            step = net.opt_step
-            # npp_adam_step_net_pack's host arithmetic: float arguments widened to double, pow / sqrt in double, result to float
-            b1, b2 = float(np.float32(0.9)), float(np.float32(0.999))
-            bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
-            e.step_size = float(np.float32(net.lr)) / bc1
-            e.inv_sqrt_bc2 = 1.0 / math.sqrt(bc2)
+            e.step_size, e.inv_sqrt_bc2 = map(float, net.step_words())      # of step opt_step + 1; the counters move after the launch
             lr_used[i] = net.lr
             x0 += e.nk
         X = x0
@@ -429,11 +422,7 @@ class StackedFit:
         for i, (f, b) in enumerate(zip(fits, batches)):
             if b is None:
                 continue
-            net = f.net
-            net.lr = net.lrate * (0.1 ** (net.global_step / (net.lrate_decay * 100)))      # train.py:256-262, NPPNet.optimizer_step
-            if net.lr_clock:
-                net.global_step += 1
-            net._clean = True
+            f.net.optimizer_advance()
             f.last_source = b["source"]
             f.last_patch_loss = self.patch_loss[i:i + 1]
             if f.percepLoss.touched:                      # only 'same' iterations give the LPIPS latents a gradient

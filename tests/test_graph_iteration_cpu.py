@@ -78,3 +78,92 @@ def test_adam_words_are_the_argument_forms_host_arithmetic():
             assert ss.dtype == np.float32 and inv.dtype == np.float32
             assert ss == np.float32(float(np.float32(lr)) / (1.0 - b1 ** step))
             assert inv == np.float32(1.0 / math.sqrt(1.0 - b2 ** step))
+
+
+_WORD_LRS = (5e-4, 5e-4 * 0.1 ** (1234 / 50000), 1.0, 1e-7)
+_WORD_STEPS = tuple(range(1, 3001)) + (10000, 50000)
+
+
+@pytest.mark.parametrize("width", npp_amd.FUSED_WIDTHS)
+def test_adam_words_equal_the_librarys_rule_as_bits(width):
+    """ops.adam_words is the Python statement of the one C rule (adam_words in csrc/npp_common.h, exported as npp_adam_words, which
+    every argument-form Adam entry calls): equal as bits over the fits' whole step range, in both libraries."""
+    import ctypes
+    L = npp_amd.lib(width)
+    out = (ctypes.c_float * 2)()
+    for lr in _WORD_LRS:
+        got = np.empty((len(_WORD_STEPS), 2), np.float32)
+        want = np.empty_like(got)
+        for i, step in enumerate(_WORD_STEPS):
+            assert L.npp_adam_words(lr, 0.9, 0.999, step, out) == 0
+            got[i] = out[0], out[1]
+            want[i] = ops.adam_words(lr, step)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), lr
+
+
+@pytest.mark.parametrize("width", npp_amd.FUSED_WIDTHS)
+def test_adam_words_entry_checks_its_arguments(width):
+    import ctypes
+    L = npp_amd.lib(width)
+    assert "npp_adam_words" in SYMBOLS
+    out = (ctypes.c_float * 2)()
+    for args in ((5e-4, 0.9, 0.999, 0, out), (5e-4, 0.9, 0.999, -3, out), (5e-4, 0.9, 0.999, 1, None)):
+        assert L.npp_adam_words(*args) == -1                     # NPP_ERR_ARG (include/npp_hip.h)
+        assert b"npp_adam_words" in L.npp_last_error_string()
+
+
+def test_light_adam_scalars_are_adam_words_along_the_clock():
+    """NPPNetLight.adam_scalars (the word table a graphed candidate fit replays) is the sequence "ops.adam_words(net.lr, net.opt_step + 1),
+    then advance the clock" -- the eager loop's own values -- and leaves the clock where it was.  The two methods read plain
+    attributes only, so no device is needed."""
+    from npp_amd.light import NPPNetLight
+    net = object.__new__(NPPNetLight)
+    net.lrate, net.lrate_decay, net.lr, net.global_step, net.opt_step = 5e-4, 500, 5e-4, 0, 0
+    for _ in range(7):                                   # a clock that has run: lr is no longer lrate
+        net.opt_step += 1
+        net.advance_clock()
+    before = (net.lr, net.global_step, net.opt_step)
+    n = 3000
+    tab = net.adam_scalars(n)
+    assert tab.dtype == np.float32 and tab.shape == (n, 2) and (net.lr, net.global_step, net.opt_step) == before
+    want = np.empty_like(tab)
+    for i in range(n):
+        want[i] = ops.adam_words(net.lr, net.opt_step + 1)
+        net.opt_step += 1
+        net.advance_clock()
+    assert np.array_equal(tab.view(np.uint32), want.view(np.uint32))
+
+
+def test_lr_rule_is_the_reference_schedule():
+    assert ops.lr_rule(5e-4, 500, 0) == 5e-4
+    assert ops.lr_rule(5e-4, 500, 1234) == 5e-4 * (0.1 ** (1234 / (500 * 100)))
+
+
+@pytest.mark.parametrize("width", npp_amd.FUSED_WIDTHS)
+def test_fused_adam_entries_keep_their_own_checks_and_texts(width):
+    """The three forms of the fused Adam + re-pack launch share a launcher (adam_pack_go) but each reports its own rule under its own
+    name, on the host, before anything is launched: step < 1 only in the argument form, the device words only in the device-word
+    form, M / the strides only in the stacked form; what they share (blobs, parameter count, alignment) names the caller."""
+    L = npp_amd.lib(width)
+    N = None
+
+    def pack(step):
+        return L.npp_adam_step_net_pack(N, N, N, N, 0, 1, 0, N, N, N, N, 0, N, 0, 5e-4, 0.9, 0.999, 1e-8, step, 3, width, N, N, N, N, N)
+
+    def pack_dev(hp):
+        return L.npp_adam_step_net_pack_dev(N, N, N, N, 0, 1, 0, N, N, N, N, 0, N, 0, 0.9, 0.999, 1e-8, hp, 3, width, N, N, N, N, N)
+
+    def pack_stack(M, it):
+        return L.npp_adam_step_net_pack_stack(N, N, N, 0, N, 0, 1, 0, 0, N, N, N, N, 0, 6, N, 0, 1, 0.9, 0.999, 1e-8, M, 3, width, N, 0, N, 0,
+                                              N, 0, N, it, N)
+    words = (__import__("ctypes").c_float * 4)()
+    for call, name, text in ((lambda: pack(0), "npp_adam_step_net_pack:", "step < 1"),
+                             (lambda: pack(1), "npp_adam_step_net_pack:", "16-byte aligned blobs"),
+                             (lambda: pack_dev(None), "npp_adam_step_net_pack_dev:", "device words"),
+                             (lambda: pack_dev(words), "npp_adam_step_net_pack_dev:", "16-byte aligned blobs"),
+                             (lambda: pack_stack(0, words), "npp_adam_step_net_pack_stack:", "per-image strides"),
+                             (lambda: pack_stack(2, None), "npp_adam_step_net_pack_stack:", "per-image strides"),
+                             (lambda: pack_stack(2, words), "npp_adam_step_net_pack_stack:", "16-byte aligned blobs and strides")):
+        assert call() == -1                          # NPP_ERR_ARG
+        msg = L.npp_last_error_string().decode()
+        assert msg.startswith(name) and text in msg, msg
