@@ -611,6 +611,33 @@ int npp_trunk_grad_in_pf(const float* d_df_nchw, const void* d_y, int N_total, i
 int npp_trunk_export(const void* d_act, int N_total, int n_run, int C, int H, int W,
                      float* d_out_nchw, int is_f16, void* stream);
 
+/* ---- trunk audit: census of a stored fp16 trunk tensor (csrc/npp_trunk_census.hip) --------------------
+ * The numeric contract of csrc/npp_conv.hip: forward activations and weights are fp16, SATURATED at +-65504 (silently: the
+ * epilogue clamps, nothing is flagged), gradients are bf16, ReLU gates are taken from the fp16 activations.  The reference runs
+ * its trunks in fp32 and has nothing to count.  The census scans what a forward pass left in ONE flat padded fp16 tensor of
+ * logical shape (N_total, C, H, W) -- [C/8 chunks][nposp][8], csrc/npp_trunk_layout.h -- and counts the INTERIOR positions
+ * (y, x in 1..H, 1..W of the padded image) of images < n and the true channels conv_chan(chunk, j) < c_real; guard, border, tail
+ * and padded-channel units are never counted, whatever they hold (the trunk input x0: C = 16, c_real = 3).  The record, int64:
+ *   NPP_CENSUS_ELEMENTS, _ZERO (codes 0x0000 / 0x8000), _SUBNORMAL (exponent field 0, mantissa != 0), _AT_MAX (|code| = 0x7BFF =
+ *   65504: saturated, or exactly there -- an upper bound on saturations), _NONFINITE (exponent field 0x1F), NPP_CENSUS_HIST + e
+ *   (finite codes by exponent field e, 32 bins; bin 0 = zero + subnormal) -- the entry of npp_stash8_census, so that
+ *   elements = zero + subnormal + sum of bins 1..30 + nonfinite with at_max inside bin 30 -- then, with d_ref32 given,
+ *   NPP_TRUNK_CENSUS_GATE_ON    #(fp16 value > 0): the ReLU gates the data-gradient pass opens
+ *   NPP_TRUNK_CENSUS_GATE_FLIPS #((fp16 value > 0) != (fp32 value > 0)), the fp32 partner d_ref32 a plain (>= n, c_real, H, W)
+ *                               NCHW tensor (what the exact-fp32 trunk stored for the same layer); both 0 when d_ref32 is NULL.
+ * Integer sums only: the record does not depend on the schedule.  npp_trunk16_census clears d_record itself (hipMemsetAsync),
+ * then one launch; it allocates nothing and writes nothing else.  npp_trunk16_census_host: the same counts by plain C++ on HOST
+ * copies (no GPU needed); it walks the layout's forward map where the kernel inverts it.  1 <= n <= N_total, C % 16 == 0,
+ * 1 <= c_real <= C; d_act 16-byte, d_ref32 4-byte, d_record 8-byte aligned. */
+#define NPP_TRUNK_CENSUS_GATE_ON NPP_CENSUS_ENTRY_WORDS
+#define NPP_TRUNK_CENSUS_GATE_FLIPS (NPP_CENSUS_ENTRY_WORDS + 1)
+#define NPP_TRUNK_CENSUS_WORDS (NPP_CENSUS_ENTRY_WORDS + 2)
+int64_t npp_trunk16_census_words(void);
+int npp_trunk16_census(const void* d_act, int N_total, int n, int C, int c_real, int H, int W, const float* d_ref32,
+                       int64_t* d_record, void* stream);
+int npp_trunk16_census_host(const void* act, int N_total, int n, int C, int c_real, int H, int W, const float* ref32,
+                            int64_t* record);
+
 /* ---- the same trunks in exact fp32 (trunk_precision = "fp32"; csrc/npp_conv32.hip) ------------------------------
  * The diagnostic twin of the launches above: the stacks of externel_lib/contextual_loss/modules/vgg.py:30-36,
  * externel_lib/lpips/pretrained_networks.py:119-134 and models/style_loss.py:11-14 in the arithmetic torch runs them in on

@@ -13,6 +13,9 @@ NPP_MAX_K, NPP_N_OFF, NPP_N_FREQ, NPP_E, NPP_WIDTH, NPP_ROW_TILE = 5, 5, 10, 462
 # one array's entry of the stash-census record (include/npp_hip.h NPP_CENSUS_*): five counters, then the exponent histogram
 CENSUS_FIELDS, CENSUS_BINS, CENSUS_MAX_ARRAYS = ("elements", "zero", "subnormal", "at_max", "nonfinite"), 32, 12 + NPP_MAX_K + 13
 CENSUS_TILE_FIELDS = ("tiles", "scale_min", "scale_max")
+# the trunk-census record (NPP_TRUNK_CENSUS_*): one such entry, then the two ReLU-gate counters
+TRUNK_CENSUS_GATE_FIELDS = ("gate_on", "gate_flips")
+TRUNK_CENSUS_WORDS = len(CENSUS_FIELDS) + CENSUS_BINS + len(TRUNK_CENSUS_GATE_FIELDS)
 
 
 class NppError(RuntimeError):
@@ -290,6 +293,9 @@ SYMBOLS = {
     "npp_robust_elem_workspace_bytes": (_i64, [_i32]),
     "npp_robust_elem": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _f32, C.POINTER(C.c_float), _vp, _vp, _vp, _vp, _vp, _vp]),
     "npp_trunk_export": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "npp_trunk16_census_words": (_i64, []),
+    "npp_trunk16_census": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "npp_trunk16_census_host": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "npp_conv32_pack_bytes": (_i64, [_i32, _i32, _i32]),
     "npp_conv32_pack": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "npp_conv32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp,

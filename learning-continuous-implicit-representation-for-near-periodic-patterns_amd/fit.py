@@ -58,7 +58,7 @@ class CompletionFit:
                  prefetch=0, use_perceptual_loss=True, task="completion", clear_mask=None, style_weight=None,
                  vgg16_style_state_dict=None, masked_img=None, width=256, no_reg_sampling=False, use_patch_weight=False,
                  no_pix_loss=False, use_contextual_loss=True, loss_type="robust_loss_adaptive", use_adaptive_perceptual_loss=True, normalize_type=1,
-                 precision="bf16", trunk_precision="fp16", graph_iteration=False, stash_audit=0):
+                 precision="bf16", trunk_precision="fp16", graph_iteration=False, stash_audit=0, trunk_audit=0):
         """img (H,W,3) float in [0,1]; mask (H,W,1) 1 = known (loaders.py:92-101).
         precision: the arithmetic of the coordinate MLP's training launches, 'bf16' (default) or 'fp32' (NPPNet(precision=...): the
         exact fp32 chain, the reference's own arithmetic; the iteration then takes the unfolded launch sequence -- fold_launches =
@@ -96,7 +96,18 @@ class CompletionFit:
         audit_next() arms one iteration): between the weight-gradient and the optimiser launch the iteration's stash is counted
         (NPPNet.stash_census) and its weight gradients are compared with the 16-bit stash's (NPPNet.stash_gap).  Reports collect in
         .stash_audits (the last MAX_STASH_AUDITS) and .last_stash_audit.  Nothing the optimiser reads is touched: an audited fit
-        ends with the bits of an unaudited one.  Refused by name for precision='fp32' and under npp_tune("stash8") = 0."""
+        ends with the bits of an unaudited one.  Refused by name for precision='fp32' and under npp_tune("stash8") = 0.
+        trunk_audit: N > 0 audits the fp16 VGG trunks of the patch losses on every N-th iteration (0, the default: never;
+        audit_trunk_next() arms one iteration): behind the backward launch and in front of the optimiser
+        launches every tensor the iteration's trunks stored is counted (HipTrunk.census) and each patch-loss term that ran is run
+        again on exact-fp32 twins of the trunks (_trunk_audit).  Reports collect in .trunk_audits (the last MAX_TRUNK_AUDITS) and
+        .last_trunk_audit.  Nothing the optimiser reads is written: an audited fit ends with the bits of an unaudited one.
+        Refused by name for trunk_precision='fp32' and for a fit without patch losses (shifts=None)."""
+        self.trunk_audit = int(trunk_audit)
+        if self.trunk_audit < 0:
+            raise ValueError("trunk_audit must be >= 0 (0: never)")
+        if self.trunk_audit:
+            ops.refuse_trunk_audit(trunk_precision, capturing=False, patch_losses=shifts is not None)
         self.stash_audit = int(stash_audit)
         if self.stash_audit < 0:
             raise ValueError("stash_audit must be >= 0 (0: never)")
@@ -104,6 +115,11 @@ class CompletionFit:
             ops.refuse_stash_audit(precision, capturing=False)
         import collections
         self.stash_audits, self.last_stash_audit, self._audit_armed = collections.deque(maxlen=self.MAX_STASH_AUDITS), None, False
+        self.trunk_audits, self.last_trunk_audit, self._trunk_armed = collections.deque(maxlen=self.MAX_TRUNK_AUDITS), None, False
+        # what the fp32 twins of the trunk audit are built from: the caller's own objects, by reference (the shared weight cache is
+        # keyed by the state dict's identity)
+        self._trunk_sd = dict(vgg19=vgg19_state_dict, vgg16=vgg16_state_dict, lins=lpips_lin_weights, style=vgg16_style_state_dict)
+        self._twins, self._audit_xy, self._audit_loss, self.trunk_audit_tensors = {}, {}, None, None
         if rng_mode not in ("reference", "numpy", "fast", "device"):
             raise ValueError("rng_mode must be 'reference', 'numpy', 'fast' or 'device'")
         if rng_mode == "device" and int(prefetch) > 0:
@@ -223,6 +239,7 @@ class CompletionFit:
             self._rec_np, self._rec_ev, self._rec_i = self._rec_pin.numpy(), [None] * self._REC_SLOTS, 0
 
     MAX_STASH_AUDITS = 4096   # reports kept in .stash_audits (a deque: the oldest go first)
+    MAX_TRUNK_AUDITS = 4096   # reports kept in .trunk_audits
     _REC_SLOTS = 32           # pinned copies of the scalar record in flight (the host may enqueue that many iterations ahead)
     MAX_ITER_GRAPHS = 40      # live captured iterations (3 sources x 3 k x 2 buffer sets x 2 loss accumulators at most per shape)
 
@@ -239,7 +256,13 @@ class CompletionFit:
         self._audit_armed = True
 
     def _audit_due(self):
-        return self._audit_armed or (self.stash_audit > 0 and self.iteration % self.stash_audit == 0)
+        """The audits of the iteration about to run: a tuple of "stash" / "trunk" (empty: none)."""
+        due = ()
+        if self._audit_armed or (self.stash_audit > 0 and self.iteration % self.stash_audit == 0):
+            due += ("stash",)
+        if self._trunk_armed or (self.trunk_audit > 0 and self.iteration % self.trunk_audit == 0):
+            due += ("trunk",)
+        return due
 
     def _stash_audit(self, b):
         """The audit of the iteration in flight, behind its weight-gradient launch and in front of its optimiser launch: census
@@ -256,6 +279,89 @@ class CompletionFit:
                "flags": ["saturated"] if at_max + nonfinite > 0 else []}       # exact: a code at the format's limit exists
         self.last_stash_audit = rep
         self.stash_audits.append(rep)
+        return rep
+
+    # ---- trunk audit -------------------------------------------------------------------------------
+    def audit_trunk_next(self):
+        """Arm the trunk audit for the next iteration that runs (a skipped iteration leaves it armed)."""
+        ops.refuse_trunk_audit(self.trunk_precision, capturing=False, patch_losses=self.patch_sampler is not None)
+        self._trunk_armed = True
+
+    def _trunk_twin(self, term):
+        """The exact-fp32 twin of one patch-loss term, built on first use from the state dicts the fit was given."""
+        tw = self._twins.get(term)
+        if tw is None:
+            sd = self._trunk_sd
+            if term == "contextual":
+                tw = ContextualLoss(use_vgg=True, vgg_state_dict=sd["vgg19"], device=self.device, trunk_precision="fp32").to(self.device)
+            elif term == "lpips":
+                tw = LPIPS(net="vgg", lin_weights=sd["lins"], vgg_state_dict=sd["vgg16"], device=self.device, trunk_precision="fp32")
+            else:
+                from .losses import StyleLoss
+                tw = StyleLoss(vgg_state_dict=sd["style"], device=self.device, trunk_precision="fp32")
+            self._twins[term] = tw
+        return tw
+
+    def _trunk_audit(self, b, grads):
+        """The trunk audit of the iteration in flight, behind its backward launch and in front of its optimiser launches (the
+        adaptive latents are still the ones its terms used).  grads: {term: the patch gradient dL/dxy the term returned} for the
+        terms that ran ("contextual", "lpips" on 'same' iterations, "style" where the fit has one) -- the 16-bit leg.  The fp32 leg:
+        the batch composed again from the iteration's prediction (npp_patch_compose_fwd into a buffer of the audit's own), the
+        term's exact-fp32 twin with the fit's current latents and the iteration's scale, writing into a scratch loss word and the
+        twin's own latent gradients.  Per term: dx_gap = rel_l2(dx16[:nk], dx32[:nk]), the census of every stored layer with the
+        ReLU gates the two trunks disagree on, feat_gap = rel_l2(fp16 layer, fp32 layer) over the kept images, and the layer with
+        the largest share of flipped gates.  Reported, not judged; "saturated" is exact (a value at 65504 or a non-finite one
+        exists).  Reads its results back: synchronises."""
+        ops.refuse_trunk_audit(self.trunk_precision, patch_losses=self.patch_sampler is not None)
+        self._trunk_armed = False
+        net, P, n_p, k, n_pix, n, raw = self.net, b["P"], b["n_p"], b["k"], b["n_pix"], b["n"], b["raw"]
+        nk = n_p * k
+        comp = self.use_comp and b["source"] == "val"
+        xy = self._audit_xy.get((nk, P))
+        if xy is None:
+            if len(self._audit_xy) >= 8:
+                self._audit_xy.clear()
+            xy = self._audit_xy[(nk, P)] = torch.empty((2 * nk, 3, P, P), dtype=torch.float32, device=self.device)
+        if self._audit_loss is None:
+            self._audit_loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        pred = net.workspace(b["bp"])["pred"]
+        ops.patch_compose_fwd(pred[n_pix:n], raw["fake"], raw["fmask"], raw["real"], raw["rmask"], n_p, k, P, comp, xy)
+        weight = b.get("weight")
+        terms, kept = {}, {"xy": xy, "dx16": {}, "dx32": {}}
+        for term, dx16 in grads.items():
+            tw = self._trunk_twin(term)
+            if term == "contextual":
+                t16 = self.contextualLoss.hip_trunk
+                dx32 = tw.fused(xy, nk, self.cx_w, self._audit_loss, weight=weight)
+            elif term == "lpips":
+                t16 = self.percepLoss.hip_trunk
+                tw._lat.copy_(self.percepLoss._lat)
+                tw.zero_latent_grads()
+                dx32 = tw.fused(xy, nk, self.lp_w * (nk if weight is not None else 1), self._audit_loss, normalize=True,
+                                use_robust=self.lp_robust)
+            else:
+                t16 = self.style.hip_trunk
+                tw._lat.copy_(self.style._lat)
+                tw.zero_latent_grads()
+                dx32 = tw.fused(xy, nk, self.style_w, self._audit_loss)
+            t32 = tw.hip_trunk
+            layers = t16.census(ref=t32)
+            gaps = [ops.rel_l2(dx16[:nk], dx32[:nk])]
+            names = t16.layer_names()
+            for j, (y, c, H, W) in enumerate(t16._geom):
+                gaps.append(ops.rel_l2(ops.trunk_export(y, t16._N, nk, c, H, W, is_f16=True), t32._acts[j][:nk]))
+            gaps = torch.stack(gaps).cpu().numpy()
+            for name in layers:
+                layers[name]["feat_gap"] = float(gaps[1 + names.index(name)]) if name in names else None
+            worst_layer = max(names, key=lambda nm: layers[nm]["gate_flips"] / max(layers[nm]["elements"], 1))
+            terms[term] = {"dx_gap": float(gaps[0]), "layers": layers, "worst_layer": worst_layer}
+            kept["dx16"][term], kept["dx32"][term] = dx16, dx32
+        worst = max(terms, key=lambda t: terms[t]["dx_gap"])
+        rep = {"iteration": int(self.iteration), "source": b["source"], "patches": int(nk), "terms": terms,
+               "worst": [worst, terms[worst]["dx_gap"]], "flags": ["saturated"] if any(ops.trunk_census_flags(t["layers"]) for t in terms.values()) else []}
+        self.last_trunk_audit = rep
+        self.trunk_audits.append(rep)
+        self.trunk_audit_tensors = kept                          # (device tensors of the newest audit: xy, both legs' dL/dxy; for tests)
         return rep
 
     def lpips_branch(self, xy, nk, scale, loss_buf):
@@ -601,6 +707,8 @@ class CompletionFit:
         and hp[2:4] (LPIPS latents) and NO step counter touched -- what a capture records (capture=True: the LPIPS branch as its
         launches, too; outside a capture it goes through lpips_branch exactly as in the loop's form: a launch-by-launch iteration
         of a graph-mode fit is the eager iteration launch for launch)."""
+        audit = ("stash",) if audit is True else tuple(audit or ())     # (True: the stash audit alone, the form before the trunk audit)
+        audit_trunk = "trunk" in audit
         self.last_source = source = b["source"]
         net, P, n_p, k, n_pix, n, bp = self.net, b["P"], b["n_p"], b["k"], b["n_pix"], b["n"], b["bp"]
         raw = b["raw"]
@@ -649,10 +757,11 @@ class CompletionFit:
         if with_lp:                                                                                 # train.py:241-250
             self._s_lp.wait_stream(main)
             with torch.cuda.stream(self._s_lp):
-                if not capture:
+                if not capture and not audit_trunk:
                     dx_b = self.lpips_branch(xy, nk, self.lp_w * (nk if weight is not None else 1), self.patch_loss_buf)
                 else:                                             # (inside a capture the branch is recorded as its launches, not as
-                    #                                               a replay of its own graph)
+                    #                                               a replay of its own graph; a trunk audit reads what THIS pass of
+                    #                                               the trunk stored: the same launches, outside lpips_branch's graphs)
                     dx_b = self.percepLoss.fused(xy, nk, self.lp_w * (nk if weight is not None else 1), self.patch_loss_buf,
                                                  normalize=True, use_robust=self.lp_robust)
         # the backward chain that follows streams this pack: requested into L2 early (bf16 chain only)
@@ -665,15 +774,25 @@ class CompletionFit:
             dx_a = torch.zeros((2 * nk, 3, P, P), dtype=torch.float32, device=self.device)
         if dx_b is not None:
             main.wait_stream(self._s_lp)
+        grads16 = {}
+        if audit_trunk:                                           # each term's patch gradient as the term returned it
+            if self.use_contextual_loss:
+                grads16["contextual"] = dx_a
+            if dx_b is not None:                                  # (a copy where the style term is added in place below)
+                grads16["lpips"] = dx_b.clone() if self.style is not None else dx_b
         if self.style is not None:                                                                  # NPP_remapping/train.py:253-261
             self.style.zero_latent_grads()
             dx_s = self.style.fused(xy, nk, self.style_w, self.patch_loss_buf)
+            if audit_trunk:
+                grads16["style"] = dx_s
             dx_b = dx_s if dx_b is None else dx_b.add_(dx_s)
         self.last_patch_loss = self.patch_loss_buf
         lr_used = net.lr
         if hp is not None:                                        # (graph_iteration: bf16 MLP, fp16 trunks, folded launches, no style term)
             net.backward(bp, patch=(dx_a, dx_b, raw["fmask"], raw["rmask"], n_pix, n_p, k, P, comp))
-            if audit:
+            if audit_trunk and grads16:
+                self._trunk_audit(b, grads16)
+            if "stash" in audit:
                 self._stash_audit(b)
             net.optimizer_launch_dev(bp, hp[0:2])
             if self.percepLoss.touched:
@@ -685,7 +804,9 @@ class CompletionFit:
         else:
             ops.patch_compose_bwd(dx_a, dx_b, raw["fmask"], raw["rmask"], n_p, k, P, comp, ws["dpred"][n_pix:n])
             net.backward(bp)
-        if audit:                                                 # (in front of the optimiser launch: the slabs are what Adam will read)
+        if audit_trunk and grads16:                               # (in front of the optimiser launches: the latents are the iteration's)
+            self._trunk_audit(b, grads16)
+        if "stash" in audit:                                      # (in front of the optimiser launch: the slabs are what Adam will read)
             self._stash_audit(b)
         net.optimizer_step(bp)
         if self.percepLoss.touched:                               # only 'same' iterations give them a gradient
@@ -776,10 +897,11 @@ class CompletionFit:
                int(lp.hip_trunk.fuse_pairs), lp.hip_trunk.fold_pool_bwd, lp.hip_trunk.fold_pool_fwd, int(cx.fuse_pairs), cx.fold_pool_bwd,
                cx.fold_pool_fwd, ops.DETERMINISTIC, stream.cuda_stream)
         ent = self._it_graphs.get(key)
-        if self._audit_due():
+        due = self._audit_due()
+        if due:
             # an audited iteration runs launch by launch (the audit sits between two of its launches and reads back on the host);
             # it is no use of the key: captures and replays go on around it as if it had not been audited
-            self._launch_iteration(b, hp=self._rec, audit=True)
+            self._launch_iteration(b, hp=self._rec, audit=due)
             self._it_stats["eager"] += 1
         elif ent is not None and ent[0] is not None:
             ent[0].replay()

@@ -216,6 +216,9 @@ class HipTrunk:
         cur = self._flat("x0", N, 16, H, W)
         if not x0_ready:
             ops.trunk_image_in(x, scale, shift, cur)
+        # (census(): the batch size the buffers were laid out for, and the flat input where this pass has one -- composed inside the
+        # first block's launch, x0_src, it is never written)
+        self._N, self._x0 = N, (None if x0_src is not None else (cur, 16, H, W))
         c, outs, pooled = 16, [], None
         for j, L in enumerate(self.layers):
             if skip:                                                  # layers j-1 .. of a fused pair: already run
@@ -275,6 +278,45 @@ class HipTrunk:
             self._geom.append((y, c, H, W))
             cur = y
         return outs
+
+    def layer_names(self):
+        """torchvision-style names of self.layers, in order: relu<block>_<i> for a convolution layer (its stored output is the ReLU's),
+        pool<block> for a pool."""
+        names, blk, i = [], 1, 1
+        for L in self.layers:
+            if L["kind"] == "conv":
+                names.append(f"relu{blk}_{i}")
+                i += 1
+            else:
+                names.append(f"pool{blk}")
+                blk, i = blk + 1, 1
+        return names
+
+    def census(self, ref=None):
+        """After a _forward(): the census (ops.trunk16_census) of every tensor the pass stored -- one launch
+        per entry of self._geom, pooled tensors included, plus the flat input x0 where the pass wrote one -- over the images a
+        backward may follow (self._n_keep: what a fused layer pair stores).  ref: a HipTrunk32 of the same layers whose _forward ran
+        on the same batch; its _acts[j] is layer j's partner for the ReLU-gate counters (None: both stay 0; x0 has no partner).
+        -> {layer name: decoded census}; one read-back serves all layers (synchronises).  Refused while a stream capture is open."""
+        ops.refuse_trunk_audit("fp16")
+        geom = getattr(self, "_geom", None)
+        if not geom or len(geom) != len(self.layers):
+            raise RuntimeError("HipTrunk.census: no complete forward pass has run on this trunk yet")
+        n = int(self._n_keep)
+        if n < 1:
+            raise RuntimeError("HipTrunk.census: the last forward kept the layer outputs of no image (n_keep = 0): nothing to count")
+        if ref is not None and (len(ref._acts) != len(geom) or any(tuple(a.shape[1:]) != (c, H, W) or a.shape[0] < n
+                                                                  for a, (_, c, H, W) in zip(ref._acts, geom))):
+            raise ValueError("HipTrunk.census: ref must be a HipTrunk32 of the same layers after a _forward on the same batch")
+        from ._lib import TRUNK_CENSUS_WORDS
+        items = ([("x0", self._x0[0], 16, 3, self._x0[2], self._x0[3], None)] if self._x0 is not None else [])
+        items += [(name, y, c, c, H, W, None if ref is None else ref._acts[j])
+                  for j, (name, (y, c, H, W)) in enumerate(zip(self.layer_names(), geom))]
+        rec = torch.empty((len(items), TRUNK_CENSUS_WORDS), dtype=torch.int64, device=self.device)
+        for i, (_, y, c, c_real, H, W, partner) in enumerate(items):
+            ops.trunk16_census(y, self._N, n, c, c_real, H, W, partner, rec[i])
+        host = rec.cpu().numpy()
+        return {it[0]: ops.trunk16_census_decode(host[i]) for i, it in enumerate(items)}
 
     def _tap_addend(self, g, N, n, c, H, W):
         """A tap gradient on a pre-pool layer as the flat bf16 tensor the pool's backward adds in: g is either that tensor already

@@ -467,6 +467,105 @@ def refuse_stash_audit(precision, exc=ValueError, flag=False, capturing=None):
                   f"torch.cuda.graph / hipStreamBeginCapture")
 
 
+# ---- trunk audit: census of a stored fp16 trunk tensor ---------------------------------------------------
+def trunk16_census(act, N_total, n, C, c_real, H, W, ref32=None, record=None):
+    """npp_trunk16_census on one flat padded fp16 tensor (trunk_alloc's layout; logical (N_total, C, H, W)): the interior
+    positions of images < n and the true channels < c_real -> the int64 record on the device (trunk16_census_decode reads it).
+    ref32: the exact-fp32 trunk's tensor of the same layer, fp32 (>= n, c_real, H, W), for the ReLU-gate counters (None: both 0).
+    Clears the record itself; nothing else is written."""
+    from ._lib import TRUNK_CENSUS_WORDS
+    nbytes = int(check(lib().npp_trunk_act_bytes(N_total, C, H, W), "npp_trunk_act_bytes"))
+    if not (isinstance(act, torch.Tensor) and act.is_cuda and act.is_contiguous() and act.numel() * act.element_size() >= nbytes):
+        raise ValueError(f"act: expected a contiguous flat trunk tensor of >= {nbytes} bytes on the GPU")
+    if ref32 is not None:
+        _req(ref32, torch.float32, "ref32")
+        if ref32.dim() != 4 or ref32.shape[0] < n or tuple(ref32.shape[1:]) != (c_real, H, W):
+            raise ValueError(f"ref32: expected shape (>= {n}, {c_real}, {H}, {W}), got {tuple(ref32.shape)}")
+    if record is None:
+        record = torch.empty(TRUNK_CENSUS_WORDS, dtype=torch.int64, device=act.device)
+    _req(record, torch.int64, "record", (TRUNK_CENSUS_WORDS,))
+    check(lib().npp_trunk16_census(_p(act), int(N_total), int(n), int(C), int(c_real), int(H), int(W), _p(ref32), _p(record), _stream()),
+          "npp_trunk16_census")
+    return record
+
+
+def trunk16_census_host(act, N_total, n, C, c_real, H, W, ref32=None):
+    """npp_trunk16_census_host: the same record by plain C++ on host copies (act: the tensor's bytes as a NumPy array of uint8 or
+    uint16 codes; ref32: NumPy fp32 (>= n, c_real, H, W))."""
+    import ctypes as ct                                       # (the parameter C, the channel count, shadows the module alias)
+    from ._lib import TRUNK_CENSUS_WORDS
+    act = np.ascontiguousarray(act)
+    nbytes = int(check(lib().npp_trunk_act_bytes(N_total, C, H, W), "npp_trunk_act_bytes"))
+    if act.dtype not in (np.uint8, np.uint16) or act.nbytes < nbytes:
+        raise ValueError(f"act: expected >= {nbytes} bytes of uint8 / uint16 codes")
+    rp = None
+    if ref32 is not None:
+        ref32 = np.ascontiguousarray(ref32, np.float32)
+        if ref32.ndim != 4 or ref32.shape[0] < n or tuple(ref32.shape[1:]) != (c_real, H, W):
+            raise ValueError(f"ref32: expected shape (>= {n}, {c_real}, {H}, {W}), got {tuple(ref32.shape)}")
+        rp = ct.c_void_p(ref32.ctypes.data)
+    rec = np.zeros(TRUNK_CENSUS_WORDS, np.int64)
+    check(lib().npp_trunk16_census_host(ct.c_void_p(act.ctypes.data), int(N_total), int(n), int(C), int(c_real), int(H), int(W), rp,
+                                        ct.c_void_p(rec.ctypes.data)), "npp_trunk16_census_host")
+    return rec
+
+
+def trunk16_census_decode(record):
+    """An int64 trunk-census record (NumPy, TRUNK_CENSUS_WORDS words) -> {"format": "fp16", "elements", "zero", "subnormal", "at_max",
+    "nonfinite", "exp_hist": [32], "gate_on", "gate_flips"}."""
+    from ._lib import CENSUS_FIELDS, CENSUS_BINS, TRUNK_CENSUS_GATE_FIELDS, TRUNK_CENSUS_WORDS
+    rec = np.asarray(record, np.int64).reshape(-1)
+    if rec.shape[0] != TRUNK_CENSUS_WORDS:
+        raise ValueError(f"record: expected {TRUNK_CENSUS_WORDS} int64 words, got {rec.shape[0]}")
+    e = {"format": "fp16"}
+    for i, f in enumerate(CENSUS_FIELDS):
+        e[f] = int(rec[i])
+    nf = len(CENSUS_FIELDS)
+    e["exp_hist"] = [int(v) for v in rec[nf:nf + CENSUS_BINS]]
+    for i, f in enumerate(TRUNK_CENSUS_GATE_FIELDS):
+        e[f] = int(rec[nf + CENSUS_BINS + i])
+    return e
+
+
+def trunk16_census_encode(entry):
+    """The inverse of trunk16_census_decode: a decoded census -> its int64 record (NumPy)."""
+    from ._lib import CENSUS_FIELDS, TRUNK_CENSUS_GATE_FIELDS
+    return np.asarray([entry[f] for f in CENSUS_FIELDS] + list(entry["exp_hist"]) + [entry[f] for f in TRUNK_CENSUS_GATE_FIELDS], np.int64)
+
+
+def trunk_census_flags(layers):
+    """["saturated"] exactly when some layer of {name: decoded census} holds a value at 65504 or a non-finite one, else []."""
+    return ["saturated"] if any(L["at_max"] + L["nonfinite"] > 0 for L in layers.values()) else []
+
+
+def rel_l2(a, b):
+    """||a - b||_2 / ||b||_2 in float64 on the device -> a 0-dim float64 tensor (no read-back)."""
+    a, b = a.double(), b.double()
+    return torch.linalg.vector_norm(a - b) / torch.linalg.vector_norm(b).clamp_min(1e-300)
+
+
+def refuse_trunk_audit(trunk_precision="fp16", exc=ValueError, flag=False, capturing=None, patch_losses=True, stacked=False):
+    """The trunk audit counts what the fp16 trunks of the patch losses stored and compares their patch gradients with the exact-fp32
+    trunks': refused by name where there is nothing 16-bit to audit, for a fit without patch losses, for stacked fits and while a
+    stream capture is open -- the audit copies its records to the host.  (exc: ValueError for the Python interface, SystemExit
+    for the command line; flag: name the switches as flags.)"""
+    me = "--audit_trunk" if flag else "trunk audit (trunk_audit)"
+    if stacked:
+        raise exc(f"{me}: stacked fits share one launch sequence and cannot be audited; "
+                  f"{'drop --stack or --audit_trunk' if flag else 'pass fits built with trunk_audit=0'}")
+    if trunk_precision != "fp16":
+        raise exc(f"{me} with {'--trunk_precision ' + str(trunk_precision) if flag else 'trunk_precision=' + repr(trunk_precision)}: "
+                  f"the trunks already run in exact fp32, there is nothing 16-bit to audit")
+    if not patch_losses:
+        raise exc(f"{me} on a fit without patch losses ({'no periodicity shifts were found' if flag else 'shifts=None'}): no VGG trunk "
+                  f"runs, there is nothing to audit")
+    if capturing is None:
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+    if capturing:
+        raise exc(f"{me} while a stream capture is open: an audit reads its records back on the host; run it outside "
+                  f"torch.cuda.graph / hipStreamBeginCapture")
+
+
 def load_spline(device):
     """values|tangents fp32 on the device + (n_knots, x_scale); table: resources/partition_spline.npz
     (this repo's own derivation, tools/gen_partition_spline.py; distribution.py:129-141)."""

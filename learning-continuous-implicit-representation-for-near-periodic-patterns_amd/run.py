@@ -50,8 +50,10 @@ def metrics_table(args, names):
     map over the region).  Printed only when the flag is among the train arguments."""
     import json
     targs = shlex.split(args.train_args)
-    if "--audit_stash" in targs and names:
-        return _table_with_stash(args, names, "--eval_metrics" in targs)
+    audits = [(f, title) for flag, f, title in (("--audit_stash", "stash_audit.json", "stash gap"), ("--audit_trunk", "trunk_audit.json", "trunk gap"))
+              if flag in targs]
+    if audits and names:
+        return _table_with_stash(args, names, "--eval_metrics" in targs, audits)
     if "--eval_metrics" not in targs or not names:
         return
     from .train import parse as train_parse
@@ -71,17 +73,17 @@ def metrics_table(args, names):
     sys.stdout.flush()
 
 
-def _table_with_stash(args, names, with_metrics):
-    """metrics_table with --train-args "--audit_stash N": the same table (its metric columns only with --eval_metrics) plus one
-    column from the stash_audit.json each fit left -- the worst gradient gap over the fit's audits, marked * when any audited
-    iteration had a code at a format's limit ("saturated")."""
+def _table_with_stash(args, names, with_metrics, audits=(("stash_audit.json", "stash gap"),)):
+    """metrics_table with --train-args "--audit_stash N" / "--audit_trunk N": the same table (its metric columns only with
+    --eval_metrics) plus one column per audit from the stash_audit.json / trunk_audit.json each fit left -- the worst gradient gap
+    over the fit's audits, marked * when any audited iteration had a code at a format's limit ("saturated")."""
     import json
     from .train import parse as train_parse
     a = train_parse(["--datadir", "."] + (["--task", args.task] if args.task != "completion" else []) + shlex.split(args.train_args))
     expname = a.expname if not (args.task != "completion" and a.expname == "completion") else args.task     # train._plan's rule
     width = max([len(n) for n in names] + [5])
     cols = ([("psnr", "{:.2f} dB", "PSNR unknown"), ("ssim", "{:.4f}", "SSIM unknown")] + ([("lpips", "{:.4f}", "LPIPS unknown")] if a.eval_lpips else [])) if with_metrics else []
-    print(f"{'image':<{width}}" + "".join(f"  {title:>13}" if k == "lpips" else f"  {title:>12}" for k, _, title in cols) + f"  {'stash gap':>12}")
+    print(f"{'image':<{width}}" + "".join(f"  {title:>13}" if k == "lpips" else f"  {title:>12}" for k, _, title in cols) + "".join(f"  {title:>12}" for _, title in audits))
     for n in names:
         root = os.path.join(args.basedir, f"{expname}_top{args.p_topk}", n)
         cells = []
@@ -92,13 +94,16 @@ def _table_with_stash(args, names, with_metrics):
                 cells = ["n/a" if (u.get(k) if k == "lpips" else u[k]) is None else fmt.format(u[k]) for k, fmt, _ in cols]
             except (OSError, ValueError, KeyError):
                 cells = ["-"] * len(cols)
-        try:
-            with open(os.path.join(root, "stash_audit.json")) as f:
-                reps = json.load(f)[1:]
-            gap = "n/a" if not reps else f"{max(r['worst'][1] for r in reps):.3e}" + ("*" if any(r["flags"] for r in reps) else "")
-        except (OSError, ValueError, KeyError):
-            gap = "-"
-        print(f"{n:<{width}}" + "".join(f"  {c:>13}" if k == "lpips" else f"  {c:>12}" for c, (k, _, _) in zip(cells, cols)) + f"  {gap:>12}")
+        gaps = []
+        for fname, _ in audits:
+            try:
+                with open(os.path.join(root, fname)) as f:
+                    reps = json.load(f)[1:]
+                gaps.append("n/a" if not reps else f"{max(r['worst'][1] for r in reps):.3e}" + ("*" if any(r["flags"] for r in reps) else ""))
+            except (OSError, ValueError, KeyError):
+                gaps.append("-")
+        print(f"{n:<{width}}" + "".join(f"  {c:>13}" if k == "lpips" else f"  {c:>12}" for c, (k, _, _) in zip(cells, cols))
+              + "".join(f"  {g:>12}" for g in gaps))
     sys.stdout.flush()
 
 

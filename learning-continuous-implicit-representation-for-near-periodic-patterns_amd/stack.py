@@ -42,7 +42,9 @@ class StackedFit:
             if getattr(f, "graph_iteration", False):
                 raise ValueError("StackedFit: graph_iteration=True fits are not stacked (a captured iteration is one fit's launch "
                                  "sequence; the stack has its own): build the fits with graph_iteration=False")
-        modes = {f.rng_mode for f in fits}
+            if getattr(f, "trunk_audit", 0):                # (an audit needs the fit's own launch sequence)
+                ops.refuse_trunk_audit(stacked=True)
+        modes ={f.rng_mode for f in fits}
         if "device" in modes and len(modes) > 1:
             raise ValueError(f"StackedFit: rng_mode='device' for every image of a stack or for none (got {sorted(modes)}): the device draws "
                              "are one launch for all images")

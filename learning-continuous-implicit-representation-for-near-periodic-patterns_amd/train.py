@@ -108,6 +108,11 @@ def parse(argv=None):
                          "codes at the formats' limits and the distance of the iteration's weight gradients to the 16-bit stash's, one "
                          "[STASH] line per audit and stash_audit.json in the image's result directory; --precision bf16 with the "
                          "8-bit stash only, not stacked")
+    ap.add_argument("--audit_trunk", type=int, default=0, metavar="N",
+                    help="audit the fp16 VGG trunks of the patch losses on every N-th iteration (0, default: never; "
+                         "CompletionFit(trunk_audit=N)): values at fp16's limits and flipped ReLU gates per stored layer, and the distance "
+                         "of each term's patch gradient to the exact-fp32 trunks', one [TRUNK] line per audit and trunk_audit.json in "
+                         "the image's result directory; --trunk_precision fp16 only, not stacked")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--save_model", action="store_true",
                     help="after a successful fit, write the network as model.npz into the image's result directory (npp_amd.render reads it)")
@@ -182,6 +187,11 @@ def _plan(argv=None):
     if args.audit_stash:
         from .ops import refuse_stash_audit
         refuse_stash_audit(args.precision, SystemExit, flag=True, capturing=False)
+    if args.audit_trunk < 0:
+        raise SystemExit("--audit_trunk N: N >= 0 (0: never)")
+    if args.audit_trunk:
+        from .ops import refuse_trunk_audit
+        refuse_trunk_audit(args.trunk_precision, SystemExit, flag=True, capturing=False)
     seg_task = args.task == "segmentation"
     from . import weights
     names = ["vgg19"] + ([] if seg_task else ["vgg16"]) + (["alexnet"] if seg_task else [])    # remapping: VGG16 is the style trunk
@@ -242,6 +252,9 @@ def _build(plan, stacked=False):
     load = weights.load_state_dict                           # (one read per file and process: shared dicts -> shared packed trunk weights)
     lin = None if (args.random_trunks and args.lpips_lin is None and args.vgg16 is None) else weights.lpips_lin("vgg", args.lpips_lin)
     try:
+        if args.audit_trunk and d["shifts"] is None:
+            from .ops import refuse_trunk_audit
+            refuse_trunk_audit(args.trunk_precision, SystemExit, flag=True, capturing=False, patch_losses=False)
         fit = CompletionFit(d["img"], d["mask"], d["angles"], d["periods"], freqs, params, device=args.device, N_rand=args.N_rand,
                             seed=args.seed, lrate=args.lrate, lrate_decay=args.lrate_decay, valid_mask=d["valid_mask"],
                             shifts=d["shifts"], patch_size=d["patch_size"], patch_num=args.patch_num,
@@ -262,7 +275,7 @@ def _build(plan, stacked=False):
                             loss_type=args.loss_type, use_adaptive_perceptual_loss=args.use_adaptive_perceptual_loss,
                             normalize_type=args.normalize_type, precision=args.precision,
                             trunk_precision=args.trunk_precision, graph_iteration=args.graph_iteration,
-                            stash_audit=args.audit_stash)
+                            stash_audit=args.audit_stash, trunk_audit=args.audit_trunk)
     except BaseException:
         import shutil
         shutil.rmtree(outroot, ignore_errors=True)          # (nothing was fitted: a re-run must not take the directory for a result)
@@ -275,6 +288,7 @@ def _build(plan, stacked=False):
     job.metrics = None                                       # --eval_metrics: the report of the newest test set
     job.lpips = None                                         # --eval_lpips: its LPIPSMetric
     job.stash_printed = 0                                    # --audit_stash: iteration of the newest [STASH] line
+    job.trunk_printed = 0                                    # --audit_trunk: iteration of the newest [TRUNK] line
     if args.eval_lpips is not None:
         # (the state dict is the one object weights.load_state_dict gave the fit's own trunks: with --eval_lpips vgg and an fp32 LPIPS
         # trunk in the loop the metric finds that trunk's packed weights; there is no second copy)
@@ -329,6 +343,13 @@ def _finish(job, failed):
         except Exception as e:
             write_error = write_error or e
             print(f"[WARN] writing stash_audit.json failed: {e}")
+    if failed is None and getattr(job.args, "audit_trunk", 0):   # --audit_trunk: every report, behind the formats they speak of
+        try:
+            with open(os.path.join(job.outroot, "trunk_audit.json"), "w") as f:
+                f.write(trunk_audit_dumps(job.fit.trunk_audits, trunk_format()) + "\n")
+        except Exception as e:
+            write_error = write_error or e
+            print(f"[WARN] writing trunk_audit.json failed: {e}")
     # first the writers: a queued dump_testset re-creates its directory (os.makedirs(..., exist_ok=True)), so nothing is
     # removed while one may still run
     for p in job.pending:
@@ -390,7 +411,7 @@ def stack_key(job):
     """Fits that can share one launch sequence (stack.StackedFit): same network shape, batch shape, loss switches and schedule."""
     a, f = job.args, job.fit
     if (f.patch_sampler is None or f.use_patch_weight or not f.use_contextual_loss or f.net.out_act != 1 or f.net.precision != "bf16"
-            or f.trunk_precision != "fp16" or f.graph_iteration or f.stash_audit):       # (an audit needs the fit's own launch sequence)
+            or f.trunk_precision != "fp16" or f.graph_iteration or f.stash_audit or f.trunk_audit):       # (an audit needs the fit's own launch sequence)
         return None
     return (a.task, f.style is not None, f.style_w, f.pixel_mask is not None, f.net.K, f.net.width, f.N_rand, f.patch_size, f.patch_num, f.topk, f.net.quad, f.pix_w, f.use_comp, f.cx_w, f.lp_w,
             f.lp_robust, f.use_perceptual_loss, f.rng_mode, a.N_iters, a.i_testset, a.i_print, a.patch_size_decay, str(f.device))
@@ -532,6 +553,32 @@ def stash_line(rep):
             + ("".join(f" [{f}]" for f in rep["flags"])))
 
 
+def trunk_format():
+    """What --audit_trunk audits, in words a log can carry: the first entry of trunk_audit.json."""
+    return {"trunks": "frozen VGG stacks of the patch losses (contextual VGG19[0:18], LPIPS VGG16, style VGG16[0:17])",
+            "forward": "fp16 activations and weights, fp32 accumulation, saturated at +-65504 without a flag",
+            "gradients": "bf16, ReLU gates taken from the fp16 activations",
+            "counted": "every stored layer over the images that carry a gradient: interior positions, true channels",
+            "compared_with": "exact-fp32 trunks on the same weights (trunk_precision fp32)"}
+
+
+def trunk_audit_dumps(reports, fmt):
+    """trunk_audit.json: [{"trunk_format": ...}, report, report, ...] (CompletionFit.trunk_audits); json.loads gives the reports back."""
+    import json
+    return json.dumps([{"trunk_format": fmt}] + [dict(r) for r in reports], indent=1)
+
+
+def trunk_line(rep):
+    """The [TRUNK] line of one audit report: the worst patch-gradient gap, the layer with the largest share of flipped gates over
+    all terms, and the values at fp16's limits over all layers."""
+    layers = [(t, n, L) for t, T in rep["terms"].items() for n, L in T["layers"].items()]
+    at_max, nonfinite = (sum(L[k] for _, _, L in layers) for k in ("at_max", "nonfinite"))
+    _, wl, wL = max(layers, key=lambda e: e[2]["gate_flips"] / max(e[2]["elements"], 1))
+    return (f"[TRUNK] it {rep['iteration']} ({rep['source']}, {rep['patches']} patches): worst gap {rep['worst'][0]} {rep['worst'][1]:.1e}, "
+            f"gate flips {100.0 * wL['gate_flips'] / max(wL['elements'], 1):.2f} % at {wl}, at_max {at_max}, nonfinite {nonfinite}"
+            + ("".join(f" [{f}]" for f in rep["flags"])))
+
+
 def _after_iteration(job, i):
     """What follows optimizer.step() in the reference's loop body at iteration i: the periodic evaluation dump (train.py:270-331;
     segmentation: NPP_segmentation/train.py:337-406) and the progress line."""
@@ -577,6 +624,10 @@ def _after_iteration(job, i):
     if audit is not None and audit["iteration"] > job.stash_printed:
         job.stash_printed = audit["iteration"]
         print(stash_line(audit))
+    audit = getattr(fit, "last_trunk_audit", None)
+    if audit is not None and audit["iteration"] > job.trunk_printed:
+        job.trunk_printed = audit["iteration"]
+        print(trunk_line(audit))
     if i % args.i_print == 0:
         print(f"[TRAIN] Iter: {i} Loss: {float(fit.net.loss_buf[0]):.6f} Patch Loss: {float(fit.last_patch_loss[0]):.6f} "
               f"({(time.time() - t0) / i * 1e3:.2f} ms/iter, skipped {fit.skipped})")
