@@ -6,13 +6,12 @@
 // npp_mlp_fwd / npp_mlp_bwd write for this K, in the order they lie in memory.  A census never writes the stash and the hot
 // kernels carry no counters: it is a scan of what they left.
 #pragma once
-#include "npp_common.h"
+#include "npp_census.h"
 
 namespace npp {
 
 enum CensusKind : int { kCensusAll = 0, kCensusEmb, kCensusRgb };   // which of an array's 16 nks feature slots are real
 constexpr int kCensusMaxArrays = 12 + NPP_MAX_K + 13;
-constexpr int kCensusEntry = NPP_CENSUS_ENTRY_WORDS, kCensusHist = NPP_CENSUS_HIST, kCensusBins = NPP_CENSUS_BINS;
 
 struct CensusArray {
   int32_t side;       // 0: actF's W8 region (fp8 e4m3), 1: dzF (bf8 e5m2) -- the side fixes the format
@@ -58,10 +57,7 @@ NPP_HD uint32_t census_jmask(int kind, int ks, int hh) {
   return m;
 }
 
-// the classes of one code (sign dropped): side 0 e4m3 (OCP: 0x7E = 448 the largest finite, 0x7F NaN, no infinity), side 1 e5m2
-// (0x7B = 57344 the largest finite, 0x7C infinity, 0x7D..0x7F NaN)
-struct CensusFmt { uint32_t mbits, max_code, nonfinite_from; };
-NPP_HD CensusFmt census_fmt(int side) { return side ? CensusFmt{2u, 0x7Bu, 0x7Cu} : CensusFmt{3u, 0x7Eu, 0x7Fu}; }
+NPP_HD CensusFmt census_fmt(int side) { return side ? kFmtE5M2 : kFmtE4M3; }
 
 struct CensusArgs {
   const uint8_t* act8;          // actF + act8_region_base(K, n_wg)
@@ -71,13 +67,9 @@ struct CensusArgs {
   CensusDesc d;
 };
 
-constexpr int kCensusThreads = 256, kCensusWaves = kCensusThreads / 64;
-
-// grid: (x: slices of an array's 16-byte pieces, y: array; y == d.n: the tile scale words).  Every lane counts in a column of its own
-// (five registers + 32 LDS words [bin][lane]: its bank is its lane, no conflict whatever the data), the columns are summed per wave,
-// the waves in LDS, and the workgroup issues one 64-bit integer atomic per non-zero counter.
+// grid: (x: slices of an array's 16-byte pieces, y: array; y == d.n: the tile scale words); counted by CensusLane (npp_census.h)
 __global__ __launch_bounds__(kCensusThreads) void stash8_census_kernel(CensusArgs A) {
-  __shared__ uint32_t sHist[kCensusWaves][kCensusBins][64];
+  __shared__ CensusHist sHist[kCensusWaves];
   __shared__ uint32_t sPart[kCensusWaves][kCensusEntry];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int a = blockIdx.y;
@@ -115,10 +107,8 @@ __global__ __launch_bounds__(kCensusThreads) void stash8_census_kernel(CensusArg
   if ((int64_t)blockIdx.x * kCensusThreads >= nq) return;
   const uint8_t* base = (ar.side ? A.dz8 : A.act8) + wfmt8_array_base(ar.ks0, A.n_wg);
   const CensusFmt F = census_fmt(ar.side);
-  uint32_t* col = &sHist[wave][0][lane];
-#pragma unroll
-  for (int b = 0; b < kCensusBins; ++b) col[b * 64] = 0;
-  uint32_t n_el = 0, n_zero = 0, n_max = 0, n_nf = 0, n_nan = 0;
+  CensusLane L(sHist);
+  L.clear();
   // the bytes of piece q that count: rows < n_rows, real features (wfmt8_unit16_decode: two rows x the 8 elements of one unit)
   auto valid = [&](int64_t q) -> uint32_t {
     if (q >= nq) return 0u;
@@ -130,15 +120,15 @@ __global__ __launch_bounds__(kCensusThreads) void stash8_census_kernel(CensusArg
   };
   // a piece with only some of its bytes counted (the ragged last rows, embedding padding, dz_rgb): byte by byte
   auto count = [&](const u32x4& v, uint32_t vm) {
-    n_el += __popc(vm);
+    L.n_el += __popc(vm);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       if ((vm >> i) & 1u) {
-        const uint32_t c = (v[i >> 2] >> (8 * (i & 3))) & 0x7fu;
-        n_zero += c == 0u;
-        n_max += c == F.max_code;
-        if (c >= F.nonfinite_from) ++n_nf;
-        else __hip_atomic_fetch_add(col + (c >> F.mbits) * 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // (no other lane adds here)
+        const CensusClass k = census_classify(F, (v[i >> 2] >> (8 * (i & 3))) & F.mask);
+        L.n_zero += k.zero;
+        L.n_max += k.at_max;
+        if (k.nonfinite) ++L.n_nf;
+        else L.add(k.bin);
       }
     }
   };
@@ -150,16 +140,15 @@ __global__ __launch_bounds__(kCensusThreads) void stash8_census_kernel(CensusArg
   const uint32_t ebits = 7u - F.mbits;
   auto zero_bytes = [](uint32_t x7) -> uint32_t { return 4u - __popc((x7 + 0x7f7f7f7fu) & 0x80808080u); };
   auto count_all = [&](const u32x4& v) {
-    n_el += 16u;
+    L.n_el += 16u;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
       const uint32_t x = v[w], x7 = x & 0x7f7f7f7fu;
-      n_zero += zero_bytes(x7);
-      n_max += zero_bytes(x7 ^ max4);
-      if (ar.side == 0) n_nan += zero_bytes(x7 ^ 0x7f7f7f7fu);
+      L.n_zero += zero_bytes(x7);
+      L.n_max += zero_bytes(x7 ^ max4);
+      if (ar.side == 0) L.n_nan += zero_bytes(x7 ^ 0x7f7f7f7fu);
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
-        __hip_atomic_fetch_add(col + __builtin_amdgcn_ubfe(x, 8u * k + F.mbits, ebits) * 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      for (int k = 0; k < 4; ++k) L.add(__builtin_amdgcn_ubfe(x, 8u * k + F.mbits, ebits));
     }
   };
   for (int64_t q = (int64_t)blockIdx.x * kCensusThreads + tid; q < nq; q += 2 * stride) {
@@ -170,42 +159,7 @@ __global__ __launch_bounds__(kCensusThreads) void stash8_census_kernel(CensusArg
     if (vm0 == 0xffffu) count_all(v0); else if (vm0) count(v0, vm0);
     if (vm1 == 0xffffu) count_all(v1); else if (vm1) count(v1, vm1);
   }
-  __syncthreads();
-  // the wave's 64 columns -> 32 bin totals: lane l sums bin l & 31 over half the columns, skewed so that the 64 lanes read 64 banks
-  uint32_t s = 0;
-  {
-    const int bin = lane & 31, half = lane >> 5;
-#pragma unroll 8
-    for (int k = 0; k < 32; ++k) s += sHist[wave][bin][half * 32 + ((k + lane) & 31)];
-    s += __shfl_xor(s, 32, 64);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    n_el += __shfl_xor(n_el, off, 64); n_zero += __shfl_xor(n_zero, off, 64); n_max += __shfl_xor(n_max, off, 64);
-    n_nf += __shfl_xor(n_nf, off, 64); n_nan += __shfl_xor(n_nan, off, 64);
-  }
-  // the non-finite codes of the whole pieces leave the histogram: e4m3's NaNs (counted above) sat in bin 15, e5m2's are bin 31
-  if (ar.side == 0) {
-    n_nf += n_nan;
-    if ((lane & 31) == 15) s -= n_nan;
-  } else {
-    n_nf += __shfl(s, 31, 64);
-    if ((lane & 31) == 31) s = 0;
-  }
-  if (lane < kCensusBins) sPart[wave][kCensusHist + lane] = s;
-  if (lane == 0) {
-    sPart[wave][NPP_CENSUS_ELEMENTS] = n_el; sPart[wave][NPP_CENSUS_ZERO] = n_zero; sPart[wave][NPP_CENSUS_SUBNORMAL] = 0;
-    sPart[wave][NPP_CENSUS_AT_MAX] = n_max; sPart[wave][NPP_CENSUS_NONFINITE] = n_nf;
-  }
-  __syncthreads();
-  if (tid < kCensusEntry) {
-    unsigned long long t = 0;
-    for (int w = 0; w < kCensusWaves; ++w) {
-      // exponent field 0 holds the zeros and the subnormals: subnormal = that bin - zero
-      t += tid == NPP_CENSUS_SUBNORMAL ? sPart[w][kCensusHist] - sPart[w][NPP_CENSUS_ZERO] : sPart[w][tid];
-    }
-    if (t) atomicAdd(A.rec + (int64_t)a * kCensusEntry + tid, t);
-  }
+  L.finish<0>(sHist, sPart, ar.side == 0, nullptr, A.rec + (int64_t)a * kCensusEntry);
 }
 
 inline int64_t census_words(int K) { return (int64_t)make_census_desc(K).n * kCensusEntry + NPP_CENSUS_TILE_WORDS; }
@@ -224,16 +178,8 @@ inline void stash8_census_host(const uint8_t* act8, const uint8_t* dz8, int64_t 
         for (int hh = 0; hh < 2; ++hh) {
           const uint32_t jm = census_jmask(ar.kind, ks, hh);
           const uint8_t* u = base + wfmt8_unit(ar.nks, row / kRowTile, ks, (int)(row % kRowTile), hh);
-          for (int j = 0; j < 8; ++j) {
-            if (!((jm >> j) & 1u)) continue;
-            const uint32_t c = u[j] & 0x7fu;
-            ++r[NPP_CENSUS_ELEMENTS];
-            if (c >= F.nonfinite_from) { ++r[NPP_CENSUS_NONFINITE]; continue; }
-            if (c == 0) ++r[NPP_CENSUS_ZERO];
-            else if ((c >> F.mbits) == 0) ++r[NPP_CENSUS_SUBNORMAL];
-            if (c == F.max_code) ++r[NPP_CENSUS_AT_MAX];
-            ++r[kCensusHist + (c >> F.mbits)];
-          }
+          for (int j = 0; j < 8; ++j)
+            if ((jm >> j) & 1u) census_tally(F, u[j] & F.mask, r);
         }
   }
   int64_t* t = rec + (int64_t)d.n * kCensusEntry;

@@ -8,14 +8,12 @@
 // one-pixel border per image, element j of chunk c8 = true channel conv_chan(c8, j).  The kernel walks a chunk's positions linearly
 // and INVERTS that map (position -> image, y, x; interior or not); the host twin walks (image, channel, y, x) through the FORWARD
 // map: the two check each other.
-#include "npp_common.h"
+#include "npp_census.h"
 #include "npp_trunk_layout.h"
 
 namespace npp {
 
-constexpr int kTcThreads = 256, kTcWaves = kTcThreads / 64;
-constexpr int kTcHist = NPP_CENSUS_HIST, kTcBins = NPP_CENSUS_BINS, kTcWords = NPP_TRUNK_CENSUS_WORDS;
-constexpr uint32_t kF16Max = 0x7BFFu;      // 65504, the largest finite code (sign dropped)
+constexpr int kTcWords = NPP_TRUNK_CENSUS_WORDS;
 
 // bit j: element j of chunk c8 is one of the c_real true channels (the trunk input x0 carries 3 of its 16)
 NPP_HD uint32_t trunk_census_jmask(int c8, int c_real) {
@@ -24,7 +22,7 @@ NPP_HD uint32_t trunk_census_jmask(int c8, int c_real) {
   return m;
 }
 // (fp16 value > 0) from the code: positive sign, not zero, not NaN -- the gate the data-gradient launches take ([y > 0])
-NPP_HD bool f16_code_positive(uint32_t c) { return !(c & 0x8000u) && (c & 0x7fffu) != 0u && (c & 0x7fffu) <= 0x7c00u; }
+NPP_HD bool f16_code_positive(uint32_t c) { return !(c & 0x8000u) && (c & kFmtF16.mask) != 0u && (c & kFmtF16.mask) <= kFmtF16.nonfinite_from; }
 
 struct TrunkCensusArgs {
   const u32x4* act;             // the flat tensor
@@ -34,25 +32,22 @@ struct TrunkCensusArgs {
   int32_t n, c_real, H, W;
 };
 
-// grid: (x: slices of a chunk's positions, y: chunk).  Every lane counts in a column of its own (registers + 32 LDS words
-// [bin][lane]: its bank is its lane, no conflict whatever the data), the columns are summed per wave, the waves in LDS, and the
-// workgroup issues one 64-bit integer atomic per non-zero counter (the form of stash8_census_kernel).
-__global__ __launch_bounds__(kTcThreads) void trunk16_census_kernel(TrunkCensusArgs A) {
-  __shared__ uint32_t sHist[kTcWaves][kTcBins][64];
-  __shared__ uint32_t sPart[kTcWaves][kTcWords];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+// grid: (x: slices of a chunk's positions, y: chunk); counted by CensusLane (npp_census.h), the two gate counters as its extra words
+__global__ __launch_bounds__(kCensusThreads) void trunk16_census_kernel(TrunkCensusArgs A) {
+  __shared__ CensusHist sHist[kCensusWaves];
+  __shared__ uint32_t sPart[kCensusWaves][kTcWords];
+  const int tid = threadIdx.x;
   const int c8 = blockIdx.y;
   const uint32_t jm = trunk_census_jmask(c8, A.c_real);
   if (!jm) return;                                                      // a chunk of padded channels only (uniform per workgroup)
   const uint32_t Wp = (uint32_t)A.W + 2u, S = ((uint32_t)A.H + 2u) * Wp;
   const uint32_t npos = (uint32_t)A.n * S;                             // (<= nposp < 2^21: the launcher's geometry check)
-  const uint32_t stride = gridDim.x * kTcThreads;
-  if (blockIdx.x * kTcThreads >= npos) return;
+  const uint32_t stride = gridDim.x * kCensusThreads;
+  if (blockIdx.x * kCensusThreads >= npos) return;
   const u32x4* base = A.act + (int64_t)c8 * A.nposp + kConvGuard;
-  uint32_t* col = &sHist[wave][0][lane];
-#pragma unroll
-  for (int b = 0; b < kTcBins; ++b) col[b * 64] = 0;
-  uint32_t n_el = 0, n_zero = 0, n_max = 0, n_on = 0, n_flip = 0;
+  CensusLane L(sHist);
+  L.clear();
+  uint32_t gate[2] = {0, 0};                                            // NPP_TRUNK_CENSUS_GATE_ON, _GATE_FLIPS
   // position p of the image axis -> (image, y, x) of the padded image; 0 when it is a border position (or past the counted images)
   auto interior = [&](uint32_t p, uint32_t& img, uint32_t& y, uint32_t& x) -> bool {
     if (p >= npos) return false;
@@ -63,24 +58,24 @@ __global__ __launch_bounds__(kTcThreads) void trunk16_census_kernel(TrunkCensusA
     return y >= 1u && y <= (uint32_t)A.H && x >= 1u && x <= (uint32_t)A.W;
   };
   auto count = [&](const u32x4& v, uint32_t img, uint32_t y, uint32_t x) {
-    n_el += __popc(jm);
+    L.n_el += __popc(jm);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       if (!((jm >> j) & 1u)) continue;                                  // (uniform: jm is the workgroup's)
-      const uint32_t c = (v[j >> 1] >> (16 * (j & 1))) & 0xffffu, a = c & 0x7fffu;
-      n_zero += a == 0u;
-      n_max += a == kF16Max;
-      // every code goes to the bin of its exponent field -- the non-finite ones (field 31) with it, taken out again below
-      __hip_atomic_fetch_add(col + (a >> 10) * 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // (no other lane adds here)
+      const uint32_t c = (v[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+      const CensusClass k = census_classify(kFmtF16, c & kFmtF16.mask);
+      L.n_zero += k.zero;
+      L.n_max += k.at_max;
+      L.add(k.bin);            // every code goes to the bin of its exponent field -- the non-finite ones (field 31) with it: finish()
       if (A.ref) {
         const float f = A.ref[(((int64_t)img * A.c_real + conv_chan(c8, j)) * A.H + (y - 1u)) * A.W + (x - 1u)];
         const bool on = f16_code_positive(c);
-        n_on += on;
-        n_flip += on != (f > 0.0f);
+        gate[0] += on;
+        gate[1] += on != (f > 0.0f);
       }
     }
   };
-  for (uint32_t p = blockIdx.x * kTcThreads + tid; p < npos; p += 2 * stride) {
+  for (uint32_t p = blockIdx.x * kCensusThreads + tid; p < npos; p += 2 * stride) {
     uint32_t i0 = 0, y0 = 0, x0 = 0, i1 = 0, y1 = 0, x1 = 0;
     const bool in0 = interior(p, i0, y0, x0), in1 = interior(p + stride, i1, y1, x1);
     u32x4 v0 = u32x4{0, 0, 0, 0}, v1 = v0;
@@ -89,37 +84,7 @@ __global__ __launch_bounds__(kTcThreads) void trunk16_census_kernel(TrunkCensusA
     if (in0) count(v0, i0, y0, x0);
     if (in1) count(v1, i1, y1, x1);
   }
-  __syncthreads();
-  // the wave's 64 columns -> 32 bin totals: lane l sums bin l & 31 over half the columns, skewed so that the 64 lanes read 64 banks
-  uint32_t s = 0;
-  {
-    const int bin = lane & 31, half = lane >> 5;
-#pragma unroll 8
-    for (int k = 0; k < 32; ++k) s += sHist[wave][bin][half * 32 + ((k + lane) & 31)];
-    s += __shfl_xor(s, 32, 64);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    n_el += __shfl_xor(n_el, off, 64); n_zero += __shfl_xor(n_zero, off, 64); n_max += __shfl_xor(n_max, off, 64);
-    n_on += __shfl_xor(n_on, off, 64); n_flip += __shfl_xor(n_flip, off, 64);
-  }
-  const uint32_t n_nf = __shfl(s, 31, 64);                              // exponent field 31: infinity and NaN leave the histogram
-  if ((lane & 31) == 31) s = 0;
-  if (lane < kTcBins) sPart[wave][kTcHist + lane] = s;
-  if (lane == 0) {
-    sPart[wave][NPP_CENSUS_ELEMENTS] = n_el; sPart[wave][NPP_CENSUS_ZERO] = n_zero; sPart[wave][NPP_CENSUS_SUBNORMAL] = 0;
-    sPart[wave][NPP_CENSUS_AT_MAX] = n_max; sPart[wave][NPP_CENSUS_NONFINITE] = n_nf;
-    sPart[wave][NPP_TRUNK_CENSUS_GATE_ON] = n_on; sPart[wave][NPP_TRUNK_CENSUS_GATE_FLIPS] = n_flip;
-  }
-  __syncthreads();
-  if (tid < kTcWords) {
-    unsigned long long t = 0;
-    for (int w = 0; w < kTcWaves; ++w) {
-      // exponent field 0 holds the zeros and the subnormals: subnormal = that bin - zero
-      t += tid == NPP_CENSUS_SUBNORMAL ? sPart[w][kTcHist] - sPart[w][NPP_CENSUS_ZERO] : sPart[w][tid];
-    }
-    if (t) atomicAdd(A.rec + tid, t);
-  }
+  L.finish<2>(sHist, sPart, false, gate, A.rec);
 }
 
 // plain C++ twin on host copies: (image, chunk, element, y, x) through the FORWARD map of the layout
@@ -135,18 +100,13 @@ static void trunk16_census_host(const uint16_t* act, int n, int C, int c_real, i
         for (int y = 0; y < H; ++y)
           for (int x = 0; x < W; ++x) {
             const int64_t pos = kConvGuard + img * S + (int64_t)(y + 1) * (W + 2) + (x + 1);
-            const uint32_t c = act[((int64_t)c8 * nposp + pos) * 8 + j], a = c & 0x7fffu;
-            ++rec[NPP_CENSUS_ELEMENTS];
+            const uint32_t c = act[((int64_t)c8 * nposp + pos) * 8 + j];
             if (ref) {
               const bool on = f16_code_positive(c);
               rec[NPP_TRUNK_CENSUS_GATE_ON] += on;
               rec[NPP_TRUNK_CENSUS_GATE_FLIPS] += on != (ref[(((int64_t)img * c_real + ch) * H + y) * W + x] > 0.0f);
             }
-            if ((a >> 10) == 31u) { ++rec[NPP_CENSUS_NONFINITE]; continue; }
-            if (a == 0u) ++rec[NPP_CENSUS_ZERO];
-            else if ((a >> 10) == 0u) ++rec[NPP_CENSUS_SUBNORMAL];
-            if (a == kF16Max) ++rec[NPP_CENSUS_AT_MAX];
-            ++rec[kTcHist + (a >> 10)];
+            census_tally(kFmtF16, c & kFmtF16.mask, rec);
           }
       }
 }
@@ -188,9 +148,9 @@ extern "C" int npp_trunk16_census(const void* d_act, int N_total, int n, int C, 
   // two 16-byte units in flight per lane and pass; about 2048 workgroups at most over the chunks (few atomics per counter)
   const int chunks = C / 8;
   const int64_t npos = (int64_t)n * (H + 2) * (W + 2);
-  const int64_t want = (npos + 2 * kTcThreads - 1) / (2 * kTcThreads), cap = 2048 / chunks > 1 ? 2048 / chunks : 1;
+  const int64_t want = (npos + 2 * kCensusThreads - 1) / (2 * kCensusThreads), cap = 2048 / chunks > 1 ? 2048 / chunks : 1;
   const unsigned gx = (unsigned)(want < 1 ? 1 : (want > cap ? cap : want));
-  hipLaunchKernelGGL(trunk16_census_kernel, dim3(gx, (unsigned)chunks), dim3(kTcThreads), 0, s, A);
+  hipLaunchKernelGGL(trunk16_census_kernel, dim3(gx, (unsigned)chunks), dim3(kCensusThreads), 0, s, A);
   return check_launch("npp_trunk16_census");
 }
 

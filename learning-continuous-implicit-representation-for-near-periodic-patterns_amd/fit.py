@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .audit import AuditSchedule, saturated, refuse as refuse_audit
 from .model import NPPNet
 from .sampler import GridPatchSampler
 from .losses import ContextualLoss, LPIPS
@@ -103,19 +104,12 @@ class CompletionFit:
         again on exact-fp32 twins of the trunks (_trunk_audit).  Reports collect in .trunk_audits (the last MAX_TRUNK_AUDITS) and
         .last_trunk_audit.  Nothing the optimiser reads is written: an audited fit ends with the bits of an unaudited one.
         Refused by name for trunk_precision='fp32' and for a fit without patch losses (shifts=None)."""
-        self.trunk_audit = int(trunk_audit)
-        if self.trunk_audit < 0:
-            raise ValueError("trunk_audit must be >= 0 (0: never)")
-        if self.trunk_audit:
-            ops.refuse_trunk_audit(trunk_precision, capturing=False, patch_losses=shifts is not None)
-        self.stash_audit = int(stash_audit)
-        if self.stash_audit < 0:
-            raise ValueError("stash_audit must be >= 0 (0: never)")
-        if self.stash_audit:
-            ops.refuse_stash_audit(precision, capturing=False)
-        import collections
-        self.stash_audits, self.last_stash_audit, self._audit_armed = collections.deque(maxlen=self.MAX_STASH_AUDITS), None, False
-        self.trunk_audits, self.last_trunk_audit, self._trunk_armed = collections.deque(maxlen=self.MAX_TRUNK_AUDITS), None, False
+        for kind, every in (("trunk", int(trunk_audit)), ("stash", int(stash_audit))):
+            if every < 0:
+                raise ValueError(f"{kind}_audit must be >= 0 (0: never)")
+            if every:
+                refuse_audit(kind, capturing=False, precision=precision, trunk_precision=trunk_precision, patch_losses=shifts is not None)
+        self._audits = {"trunk": AuditSchedule(trunk_audit, self.MAX_TRUNK_AUDITS), "stash": AuditSchedule(stash_audit, self.MAX_STASH_AUDITS)}
         # what the fp32 twins of the trunk audit are built from: the caller's own objects, by reference (the shared weight cache is
         # keyed by the state dict's identity)
         self._trunk_sd = dict(vgg19=vgg19_state_dict, vgg16=vgg16_state_dict, lins=lpips_lin_weights, style=vgg16_style_state_dict)
@@ -249,43 +243,47 @@ class CompletionFit:
         launch by launch (the first uses of a key, keys met while no capture is possible)}; skipped iterations count nowhere."""
         return dict(self._it_stats)
 
+    stash_audit = property(lambda self: self._audits["stash"].every)      # (the schedules under their public names)
+    trunk_audit = property(lambda self: self._audits["trunk"].every)
+    stash_audits = property(lambda self: self._audits["stash"].reports)
+    trunk_audits = property(lambda self: self._audits["trunk"].reports)
+    last_stash_audit = property(lambda self: self._audits["stash"].last)
+    last_trunk_audit = property(lambda self: self._audits["trunk"].last)
+
+    def _audit_due(self):
+        """The audits of the iteration about to run: a tuple of "trunk" / "stash" (empty: none)."""
+        return tuple(kind for kind, sched in self._audits.items() if sched.due(self.iteration))
+
+    def _run_audits(self, due, b, grads16):
+        """The audits of the iteration in flight, in front of its optimiser launches: the latents and the slabs are the iteration's."""
+        if "trunk" in due and grads16:
+            self._trunk_audit(b, grads16)
+        if "stash" in due:
+            self._stash_audit(b)
+
     # ---- stash audit (DESIGN.md section 6j) ------------------------------------------------------------------------------
     def audit_next(self):
         """Arm the stash audit for the next iteration that runs (a skipped iteration leaves it armed)."""
         ops.refuse_stash_audit(self.precision, capturing=False)
-        self._audit_armed = True
-
-    def _audit_due(self):
-        """The audits of the iteration about to run: a tuple of "stash" / "trunk" (empty: none)."""
-        due = ()
-        if self._audit_armed or (self.stash_audit > 0 and self.iteration % self.stash_audit == 0):
-            due += ("stash",)
-        if self._trunk_armed or (self.trunk_audit > 0 and self.iteration % self.trunk_audit == 0):
-            due += ("trunk",)
-        return due
+        self._audits["stash"].arm()
 
     def _stash_audit(self, b):
         """The audit of the iteration in flight, behind its weight-gradient launch and in front of its optimiser launch: census
         first (the 16-bit leg of the gap overwrites the stash), then the gap.  Reads its results back: synchronises."""
         net = self.net
-        self._audit_armed = False
         census = net.stash_census(b["bp"], b["n"])
         gap = net.stash_gap(b["bp"], b["coords"])
         worst = max(gap, key=gap.get)
-        at_max = sum(c["at_max"] for c in census.values())
-        nonfinite = sum(c["nonfinite"] for c in census.values())
         rep = {"iteration": int(self.iteration), "source": b["source"], "rows": int(b["n"]), "census": census,
                "tile_scale": dict(net.last_tile_scale), "grad_gap": gap, "worst": [worst, gap[worst]],
-               "flags": ["saturated"] if at_max + nonfinite > 0 else []}       # exact: a code at the format's limit exists
-        self.last_stash_audit = rep
-        self.stash_audits.append(rep)
-        return rep
+               "flags": ["saturated"] if saturated(census.values()) else []}
+        return self._audits["stash"].record(rep)
 
     # ---- trunk audit (DESIGN.md section 6l) -------------------------------------------------------------------------------
     def audit_trunk_next(self):
         """Arm the trunk audit for the next iteration that runs (a skipped iteration leaves it armed)."""
         ops.refuse_trunk_audit(self.trunk_precision, capturing=False, patch_losses=self.patch_sampler is not None)
-        self._trunk_armed = True
+        self._audits["trunk"].arm()
 
     def _trunk_twin(self, term):
         """The exact-fp32 twin of one patch-loss term, built on first use from the state dicts the fit was given."""
@@ -313,7 +311,6 @@ class CompletionFit:
         the largest share of flipped gates.  Reported, not judged; "saturated" is exact (a value at 65504 or a non-finite one
         exists).  Reads its results back: synchronises."""
         ops.refuse_trunk_audit(self.trunk_precision, patch_losses=self.patch_sampler is not None)
-        self._trunk_armed = False
         net, P, n_p, k, n_pix, n, raw = self.net, b["P"], b["n_p"], b["k"], b["n_pix"], b["n"], b["raw"]
         nk = n_p * k
         comp = self.use_comp and b["source"] == "val"
@@ -359,10 +356,8 @@ class CompletionFit:
         worst = max(terms, key=lambda t: terms[t]["dx_gap"])
         rep = {"iteration": int(self.iteration), "source": b["source"], "patches": int(nk), "terms": terms,
                "worst": [worst, terms[worst]["dx_gap"]], "flags": ["saturated"] if any(ops.trunk_census_flags(t["layers"]) for t in terms.values()) else []}
-        self.last_trunk_audit = rep
-        self.trunk_audits.append(rep)
         self.trunk_audit_tensors = kept                          # (device tensors of the newest audit: xy, both legs' dL/dxy; for tests)
-        return rep
+        return self._audits["trunk"].record(rep)
 
     def lpips_branch(self, xy, nk, scale, loss_buf):
         """percepLoss.fused(xy, nk, scale, loss_buf) on the CURRENT stream (the loop's side stream).  The branch is 46 launches at the
@@ -700,14 +695,13 @@ class CompletionFit:
                 self._xy_bufs[key] = torch.empty((2 * nk, 3, P, P), dtype=torch.float32, device=self.device)
             self._xy, self._xy_key = self._xy_bufs[key], key
 
-    def _launch_iteration(self, b, hp=None, capture=False, audit=False):
+    def _launch_iteration(self, b, hp=None, capture=False, audit=()):
         """The launches of one iteration behind zero_grad(), on the current stream (+ the LPIPS side stream).  hp None: the loop's
         form -- step-dependent scalars as kernel arguments, the host's counters advanced on the way.  hp = the scalar record on the
         device (graph_iteration): the same launches with the optimisers' scalars read from hp[0:2] (network + pixel-loss latents)
         and hp[2:4] (LPIPS latents) and NO step counter touched -- what a capture records (capture=True: the LPIPS branch as its
         launches, too; outside a capture it goes through lpips_branch exactly as in the loop's form: a launch-by-launch iteration
         of a graph-mode fit is the eager iteration launch for launch)."""
-        audit = ("stash",) if audit is True else tuple(audit or ())     # (True: the stash audit alone, the form before the trunk audit)
         audit_trunk = "trunk" in audit
         self.last_source = source = b["source"]
         net, P, n_p, k, n_pix, n, bp = self.net, b["P"], b["n_p"], b["k"], b["n_pix"], b["n"], b["bp"]
@@ -790,10 +784,7 @@ class CompletionFit:
         lr_used = net.lr
         if hp is not None:                                        # (graph_iteration: bf16 MLP, fp16 trunks, folded launches, no style term)
             net.backward(bp, patch=(dx_a, dx_b, raw["fmask"], raw["rmask"], n_pix, n_p, k, P, comp))
-            if audit_trunk and grads16:
-                self._trunk_audit(b, grads16)
-            if "stash" in audit:
-                self._stash_audit(b)
+            self._run_audits(audit, b, grads16)
             net.optimizer_launch_dev(bp, hp[0:2])
             if self.percepLoss.touched:
                 self.percepLoss.adam_launch_dev(hp[2:4])
@@ -804,10 +795,7 @@ class CompletionFit:
         else:
             ops.patch_compose_bwd(dx_a, dx_b, raw["fmask"], raw["rmask"], n_p, k, P, comp, ws["dpred"][n_pix:n])
             net.backward(bp)
-        if audit_trunk and grads16:                               # (in front of the optimiser launches: the latents are the iteration's)
-            self._trunk_audit(b, grads16)
-        if "stash" in audit:                                      # (in front of the optimiser launch: the slabs are what Adam will read)
-            self._stash_audit(b)
+        self._run_audits(audit, b, grads16)
         net.optimizer_step(bp)
         if self.percepLoss.touched:                               # only 'same' iterations give them a gradient
             self.percepLoss.adam_step(lr_used)

@@ -6,6 +6,7 @@ import math
 import numpy as np
 import torch
 
+from . import audit
 from ._lib import lib, check, EmbedCfg, param_layout, NPP_ROW_TILE, NPP_E, NPP_WIDTH  # noqa: F401
 
 
@@ -437,34 +438,16 @@ def stash8_census_host(act, dz, Bp, n_rows, K, width=NPP_WIDTH):
 def census_decode(record, K, width=NPP_WIDTH):
     """An int64 census record (NumPy) -> ({array name: {"format", "features", "elements", "zero", "subnormal", "at_max", "nonfinite",
     "exp_hist": [32]}}, {"tiles", "scale_min", "scale_max"}), by the library's own table (census_layout)."""
-    from ._lib import census_layout, CENSUS_FIELDS, CENSUS_BINS, CENSUS_TILE_FIELDS
+    from ._lib import census_layout, CENSUS_TILE_FIELDS
     table, tile_off, _ = census_layout(K, width)
     rec = np.asarray(record, np.int64)
-    out = {}
-    for name, fmt, feats, off in table:
-        e = {"format": fmt, "features": feats}
-        for i, f in enumerate(CENSUS_FIELDS):
-            e[f] = int(rec[off + i])
-        e["exp_hist"] = [int(v) for v in rec[off + len(CENSUS_FIELDS):off + len(CENSUS_FIELDS) + CENSUS_BINS]]
-        out[name] = e
+    out = {name: {"format": fmt, "features": feats, **audit.decode_entry(rec, off)} for name, fmt, feats, off in table}
     return out, {f: int(rec[tile_off + i]) for i, f in enumerate(CENSUS_TILE_FIELDS)}
 
 
 def refuse_stash_audit(precision, exc=ValueError, flag=False, capturing=None):
-    """The stash audit reads the 8-bit stash of the bf16 chain: refused by name where there is none (exc: ValueError for the Python
-    interface, SystemExit for the command line; flag: name the switches as flags) and while a stream capture is open (the audit
-    copies its record to the host)."""
-    me = "--audit_stash" if flag else "stash audit"
-    if precision != "bf16":
-        raise exc(f"{me} with {'--precision ' + precision if flag else 'precision=' + repr(precision)}: the exact-fp32 chain has no "
-                  f"8-bit stash (its stash is fp32, nothing is rounded)")
-    if not tune("stash8"):
-        raise exc(f"{me} with {'NPP_STASH8=0 / ' if flag else ''}npp_tune('stash8') = 0: the 16-bit stash is in use, there is nothing to audit")
-    if capturing is None:
-        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-    if capturing:
-        raise exc(f"{me} while a stream capture is open: an audit reads its record back on the host; run it outside "
-                  f"torch.cuda.graph / hipStreamBeginCapture")
+    """The stash audit reads the 8-bit stash of the bf16 chain: refused by name where there is none (audit.refuse)."""
+    audit.refuse("stash", exc, flag, capturing, precision=precision)
 
 
 # ---- trunk audit (DESIGN.md section 6l): census of a stored fp16 trunk tensor ---------------------------------------------------
@@ -513,18 +496,11 @@ def trunk16_census_host(act, N_total, n, C, c_real, H, W, ref32=None):
 def trunk16_census_decode(record):
     """An int64 trunk-census record (NumPy, TRUNK_CENSUS_WORDS words) -> {"format": "fp16", "elements", "zero", "subnormal", "at_max",
     "nonfinite", "exp_hist": [32], "gate_on", "gate_flips"}."""
-    from ._lib import CENSUS_FIELDS, CENSUS_BINS, TRUNK_CENSUS_GATE_FIELDS, TRUNK_CENSUS_WORDS
+    from ._lib import TRUNK_CENSUS_GATE_FIELDS, TRUNK_CENSUS_WORDS
     rec = np.asarray(record, np.int64).reshape(-1)
     if rec.shape[0] != TRUNK_CENSUS_WORDS:
         raise ValueError(f"record: expected {TRUNK_CENSUS_WORDS} int64 words, got {rec.shape[0]}")
-    e = {"format": "fp16"}
-    for i, f in enumerate(CENSUS_FIELDS):
-        e[f] = int(rec[i])
-    nf = len(CENSUS_FIELDS)
-    e["exp_hist"] = [int(v) for v in rec[nf:nf + CENSUS_BINS]]
-    for i, f in enumerate(TRUNK_CENSUS_GATE_FIELDS):
-        e[f] = int(rec[nf + CENSUS_BINS + i])
-    return e
+    return {"format": "fp16", **audit.decode_entry(rec), **dict(zip(TRUNK_CENSUS_GATE_FIELDS, rec[-len(TRUNK_CENSUS_GATE_FIELDS):].tolist()))}
 
 
 def trunk16_census_encode(entry):
@@ -535,7 +511,7 @@ def trunk16_census_encode(entry):
 
 def trunk_census_flags(layers):
     """["saturated"] exactly when some layer of {name: decoded census} holds a value at 65504 or a non-finite one, else []."""
-    return ["saturated"] if any(L["at_max"] + L["nonfinite"] > 0 for L in layers.values()) else []
+    return ["saturated"] if audit.saturated(layers.values()) else []
 
 
 def rel_l2(a, b):
@@ -545,25 +521,9 @@ def rel_l2(a, b):
 
 
 def refuse_trunk_audit(trunk_precision="fp16", exc=ValueError, flag=False, capturing=None, patch_losses=True, stacked=False):
-    """The trunk audit counts what the fp16 trunks of the patch losses stored and compares their patch gradients with the exact-fp32
-    trunks': refused by name where there is nothing 16-bit to audit, for a fit without patch losses, for stacked fits and while a
-    stream capture is open -- the audit copies its records to the host.  (exc: ValueError for the Python interface, SystemExit
-    for the command line; flag: name the switches as flags.)"""
-    me = "--audit_trunk" if flag else "trunk audit (trunk_audit)"
-    if stacked:
-        raise exc(f"{me}: stacked fits share one launch sequence and cannot be audited; "
-                  f"{'drop --stack or --audit_trunk' if flag else 'pass fits built with trunk_audit=0'}")
-    if trunk_precision != "fp16":
-        raise exc(f"{me} with {'--trunk_precision ' + str(trunk_precision) if flag else 'trunk_precision=' + repr(trunk_precision)}: "
-                  f"the trunks already run in exact fp32, there is nothing 16-bit to audit")
-    if not patch_losses:
-        raise exc(f"{me} on a fit without patch losses ({'no periodicity shifts were found' if flag else 'shifts=None'}): no VGG trunk "
-                  f"runs, there is nothing to audit")
-    if capturing is None:
-        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-    if capturing:
-        raise exc(f"{me} while a stream capture is open: an audit reads its records back on the host; run it outside "
-                  f"torch.cuda.graph / hipStreamBeginCapture")
+    """The trunk audit compares the fp16 trunks of the patch losses with the exact-fp32 trunks: refused by name where there is nothing
+    16-bit to audit, for a fit without patch losses and for stacked fits (audit.refuse)."""
+    audit.refuse("trunk", exc, flag, capturing, trunk_precision=trunk_precision, patch_losses=patch_losses, stacked=stacked)
 
 
 def load_spline(device):

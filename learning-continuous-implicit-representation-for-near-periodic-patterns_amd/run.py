@@ -45,45 +45,27 @@ def my_share(items):
 
 
 def metrics_table(args, names):
-    """--train-args "--eval_metrics": one table over the images of this rank from the metrics.json each fit left in its result
-    directory (name, PSNR and SSIM of the unknown region; with "--eval_lpips NET" among them also its LPIPS, the mean of the distance
-    map over the region).  Printed only when the flag is among the train arguments."""
+    """The closing table over the images of this rank, from the files each fit left in its result directory.  --train-args
+    "--eval_metrics": name, PSNR and SSIM of the unknown region from metrics.json (with "--eval_lpips NET" among them also its LPIPS,
+    the mean of the distance map over the region).  "--audit_stash N" / "--audit_trunk N": one column per audit from stash_audit.json /
+    trunk_audit.json -- the worst gradient gap over the fit's audits, marked * when any audited iteration had a code at a format's
+    limit ("saturated").  Printed only when one of the flags is among the train arguments."""
     import json
+    from .train import AUDITS, parse as train_parse
     targs = shlex.split(args.train_args)
-    audits = [(f, title) for flag, f, title in (("--audit_stash", "stash_audit.json", "stash gap"), ("--audit_trunk", "trunk_audit.json", "trunk gap"))
-              if flag in targs]
-    if audits and names:
-        return _table_with_stash(args, names, "--eval_metrics" in targs, audits)
-    if "--eval_metrics" not in targs or not names:
+    audits = [a for a in AUDITS if a.flag in targs]
+    with_metrics = "--eval_metrics" in targs
+    if not (audits or with_metrics) or not names:
         return
-    from .train import parse as train_parse
-    a = train_parse(["--datadir", "."] + (["--task", args.task] if args.task != "completion" else []) + shlex.split(args.train_args))
-    expname = a.expname if not (args.task != "completion" and a.expname == "completion") else args.task     # train._plan's rule
-    width = max([len(n) for n in names] + [5])
-    cols = [("psnr", "{:.2f} dB", "PSNR unknown"), ("ssim", "{:.4f}", "SSIM unknown")] + ([("lpips", "{:.4f}", "LPIPS unknown")] if a.eval_lpips else [])
-    print(f"{'image':<{width}}" + "".join(f"  {title:>13}" if k == "lpips" else f"  {title:>12}" for k, _, title in cols))
-    for n in names:
-        try:
-            with open(os.path.join(args.basedir, f"{expname}_top{args.p_topk}", n, "metrics.json")) as f:
-                u = json.load(f)["unknown"]
-            cells = ["n/a" if (u.get(k) if k == "lpips" else u[k]) is None else fmt.format(u[k]) for k, fmt, _ in cols]
-        except (OSError, ValueError, KeyError):
-            cells = ["-"] * len(cols)                              # no report: the fit failed or was found in place without one
-        print(f"{n:<{width}}" + "".join(f"  {c:>13}" if k == "lpips" else f"  {c:>12}" for c, (k, _, _) in zip(cells, cols)))
-    sys.stdout.flush()
-
-
-def _table_with_stash(args, names, with_metrics, audits=(("stash_audit.json", "stash gap"),)):
-    """metrics_table with --train-args "--audit_stash N" / "--audit_trunk N": the same table (its metric columns only with
-    --eval_metrics) plus one column per audit from the stash_audit.json / trunk_audit.json each fit left -- the worst gradient gap
-    over the fit's audits, marked * when any audited iteration had a code at a format's limit ("saturated")."""
-    import json
-    from .train import parse as train_parse
-    a = train_parse(["--datadir", "."] + (["--task", args.task] if args.task != "completion" else []) + shlex.split(args.train_args))
+    a = train_parse(["--datadir", "."] + (["--task", args.task] if args.task != "completion" else []) + targs)
     expname = a.expname if not (args.task != "completion" and a.expname == "completion") else args.task     # train._plan's rule
     width = max([len(n) for n in names] + [5])
     cols = ([("psnr", "{:.2f} dB", "PSNR unknown"), ("ssim", "{:.4f}", "SSIM unknown")] + ([("lpips", "{:.4f}", "LPIPS unknown")] if a.eval_lpips else [])) if with_metrics else []
-    print(f"{'image':<{width}}" + "".join(f"  {title:>13}" if k == "lpips" else f"  {title:>12}" for k, _, title in cols) + "".join(f"  {title:>12}" for _, title in audits))
+    widths = [13 if k == "lpips" else 12 for k, _, _ in cols] + [12] * len(audits)
+
+    def row(first, cells):
+        return f"{first:<{width}}" + "".join(f"  {c:>{w}}" for c, w in zip(cells, widths))
+    print(row("image", [title for _, _, title in cols] + [f"{au.kind} gap" for au in audits]))
     for n in names:
         root = os.path.join(args.basedir, f"{expname}_top{args.p_topk}", n)
         cells = []
@@ -93,17 +75,15 @@ def _table_with_stash(args, names, with_metrics, audits=(("stash_audit.json", "s
                     u = json.load(f)["unknown"]
                 cells = ["n/a" if (u.get(k) if k == "lpips" else u[k]) is None else fmt.format(u[k]) for k, fmt, _ in cols]
             except (OSError, ValueError, KeyError):
-                cells = ["-"] * len(cols)
-        gaps = []
-        for fname, _ in audits:
+                cells = ["-"] * len(cols)                          # no report: the fit failed or was found in place without one
+        for au in audits:
             try:
-                with open(os.path.join(root, fname)) as f:
+                with open(os.path.join(root, au.file)) as f:
                     reps = json.load(f)[1:]
-                gaps.append("n/a" if not reps else f"{max(r['worst'][1] for r in reps):.3e}" + ("*" if any(r["flags"] for r in reps) else ""))
+                cells.append("n/a" if not reps else f"{max(r['worst'][1] for r in reps):.3e}" + ("*" if any(r["flags"] for r in reps) else ""))
             except (OSError, ValueError, KeyError):
-                gaps.append("-")
-        print(f"{n:<{width}}" + "".join(f"  {c:>13}" if k == "lpips" else f"  {c:>12}" for c, (k, _, _) in zip(cells, cols))
-              + "".join(f"  {g:>12}" for g in gaps))
+                cells.append("-")
+        print(row(n, cells))
     sys.stdout.flush()
 
 

@@ -11,11 +11,15 @@ Flags keep the reference's names and defaults (options/arg_config.py:10-36,55-10
 reference's 512 (the second fused build, libnpp_hip_w512.so); BASELINE.json's configurations are --netwidth 256.
 """
 import argparse
+import collections
+import functools
 import os
 import time
 
 import numpy as np
 import torch
+
+from .audit import at_limits, audit_dumps, refuse as refuse_audit
 
 
 def parse(argv=None):
@@ -182,16 +186,11 @@ def _plan(argv=None):
     if args.graph_iteration:
         from .fit import refuse_graph_iteration
         refuse_graph_iteration(args.precision, args.trunk_precision, args.task, None, SystemExit, flag=True)
-    if args.audit_stash < 0:
-        raise SystemExit("--audit_stash N: N >= 0 (0: never)")
-    if args.audit_stash:
-        from .ops import refuse_stash_audit
-        refuse_stash_audit(args.precision, SystemExit, flag=True, capturing=False)
-    if args.audit_trunk < 0:
-        raise SystemExit("--audit_trunk N: N >= 0 (0: never)")
-    if args.audit_trunk:
-        from .ops import refuse_trunk_audit
-        refuse_trunk_audit(args.trunk_precision, SystemExit, flag=True, capturing=False)
+    for a in AUDITS:
+        if getattr(args, a.flag[2:]) < 0:
+            raise SystemExit(f"{a.flag} N: N >= 0 (0: never)")
+        if getattr(args, a.flag[2:]):
+            refuse_audit(a.kind, SystemExit, flag=True, capturing=False, precision=args.precision, trunk_precision=args.trunk_precision)
     seg_task = args.task == "segmentation"
     from . import weights
     names = ["vgg19"] + ([] if seg_task else ["vgg16"]) + (["alexnet"] if seg_task else [])    # remapping: VGG16 is the style trunk
@@ -253,8 +252,7 @@ def _build(plan, stacked=False):
     lin = None if (args.random_trunks and args.lpips_lin is None and args.vgg16 is None) else weights.lpips_lin("vgg", args.lpips_lin)
     try:
         if args.audit_trunk and d["shifts"] is None:
-            from .ops import refuse_trunk_audit
-            refuse_trunk_audit(args.trunk_precision, SystemExit, flag=True, capturing=False, patch_losses=False)
+            refuse_audit("trunk", SystemExit, flag=True, capturing=False, trunk_precision=args.trunk_precision, patch_losses=False)
         fit = CompletionFit(d["img"], d["mask"], d["angles"], d["periods"], freqs, params, device=args.device, N_rand=args.N_rand,
                             seed=args.seed, lrate=args.lrate, lrate_decay=args.lrate_decay, valid_mask=d["valid_mask"],
                             shifts=d["shifts"], patch_size=d["patch_size"], patch_num=args.patch_num,
@@ -287,8 +285,7 @@ def _build(plan, stacked=False):
     job.writer, job.pending, job.t0, job.name = ThreadPoolExecutor(1), [], time.time(), name
     job.metrics = None                                       # --eval_metrics: the report of the newest test set
     job.lpips = None                                         # --eval_lpips: its LPIPSMetric
-    job.stash_printed = 0                                    # --audit_stash: iteration of the newest [STASH] line
-    job.trunk_printed = 0                                    # --audit_trunk: iteration of the newest [TRUNK] line
+    job.audit_printed = {a.kind: 0 for a in AUDITS}          # --audit_stash / --audit_trunk: iteration of the newest [STASH] / [TRUNK] line
     if args.eval_lpips is not None:
         # (the state dict is the one object weights.load_state_dict gave the fit's own trunks: with --eval_lpips vgg and an fp32 LPIPS
         # trunk in the loop the metric finds that trunk's packed weights; there is no second copy)
@@ -336,20 +333,14 @@ def _finish(job, failed):
         except Exception as e:
             write_error = write_error or e
             print(f"[WARN] writing metrics.json failed: {e}")
-    if failed is None and getattr(job.args, "audit_stash", 0):   # --audit_stash: every report, behind the stash format they speak of
-        try:
-            with open(os.path.join(job.outroot, "stash_audit.json"), "w") as f:
-                f.write(stash_audit_dumps(job.fit.stash_audits, stash_format(job.fit.net.width)) + "\n")
-        except Exception as e:
-            write_error = write_error or e
-            print(f"[WARN] writing stash_audit.json failed: {e}")
-    if failed is None and getattr(job.args, "audit_trunk", 0):   # --audit_trunk: every report, behind the formats they speak of
-        try:
-            with open(os.path.join(job.outroot, "trunk_audit.json"), "w") as f:
-                f.write(trunk_audit_dumps(job.fit.trunk_audits, trunk_format()) + "\n")
-        except Exception as e:
-            write_error = write_error or e
-            print(f"[WARN] writing trunk_audit.json failed: {e}")
+    for a in AUDITS:                                        # --audit_stash / --audit_trunk: every report, behind the format they speak of
+        if failed is None and getattr(job.args, a.flag[2:], 0):
+            try:
+                with open(os.path.join(job.outroot, a.file), "w") as f:
+                    f.write(audit_dumps(f"{a.kind}_format", getattr(job.fit, f"{a.kind}_audits"), a.format(job.fit)) + "\n")
+            except Exception as e:
+                write_error = write_error or e
+                print(f"[WARN] writing {a.file} failed: {e}")
     # first the writers: a queued dump_testset re-creates its directory (os.makedirs(..., exist_ok=True)), so nothing is
     # removed while one may still run
     for p in job.pending:
@@ -538,16 +529,10 @@ def stash_format(width):
             "width": int(width)}
 
 
-def stash_audit_dumps(reports, fmt):
-    """stash_audit.json: [{"stash_format": ...}, report, report, ...] (CompletionFit.stash_audits); json.loads gives the reports back."""
-    import json
-    return json.dumps([{"stash_format": fmt}] + [dict(r) for r in reports], indent=1)
-
-
 def stash_line(rep):
     """The [STASH] line of one audit report."""
     cen, ts = rep["census"], rep["tile_scale"]
-    at_max, nonfinite = (sum(c[k] for c in cen.values()) for k in ("at_max", "nonfinite"))
+    at_max, nonfinite = at_limits(cen.values())
     return (f"[STASH] it {rep['iteration']} ({rep['source']}, {rep['rows']} rows): worst gap {rep['worst'][0]} {rep['worst'][1]:.3e}, "
             f"at_max {at_max}, nonfinite {nonfinite}, tile scale 2^{ts['scale_min'] - 127}..2^{ts['scale_max'] - 127}"
             + ("".join(f" [{f}]" for f in rep["flags"])))
@@ -562,21 +547,22 @@ def trunk_format():
             "compared_with": "exact-fp32 trunks on the same weights (trunk_precision fp32)"}
 
 
-def trunk_audit_dumps(reports, fmt):
-    """trunk_audit.json: [{"trunk_format": ...}, report, report, ...] (CompletionFit.trunk_audits); json.loads gives the reports back."""
-    import json
-    return json.dumps([{"trunk_format": fmt}] + [dict(r) for r in reports], indent=1)
-
-
 def trunk_line(rep):
     """The [TRUNK] line of one audit report: the worst patch-gradient gap, the layer with the largest share of flipped gates over
     all terms, and the values at fp16's limits over all layers."""
     layers = [(t, n, L) for t, T in rep["terms"].items() for n, L in T["layers"].items()]
-    at_max, nonfinite = (sum(L[k] for _, _, L in layers) for k in ("at_max", "nonfinite"))
+    at_max, nonfinite = at_limits(L for _, _, L in layers)
     _, wl, wL = max(layers, key=lambda e: e[2]["gate_flips"] / max(e[2]["elements"], 1))
     return (f"[TRUNK] it {rep['iteration']} ({rep['source']}, {rep['patches']} patches): worst gap {rep['worst'][0]} {rep['worst'][1]:.1e}, "
             f"gate flips {100.0 * wL['gate_flips'] / max(wL['elements'], 1):.2f} % at {wl}, at_max {at_max}, nonfinite {nonfinite}"
             + ("".join(f" [{f}]" for f in rep["flags"])))
+
+
+# the audits of the command line, one row each: kind, flag, file in the result directory, format(fit), line(report)
+stash_audit_dumps, trunk_audit_dumps = functools.partial(audit_dumps, "stash_format"), functools.partial(audit_dumps, "trunk_format")   # (reports, fmt)
+Audit = collections.namedtuple("Audit", "kind flag file format line")
+AUDITS = (Audit("stash", "--audit_stash", "stash_audit.json", lambda fit: stash_format(fit.net.width), stash_line),
+          Audit("trunk", "--audit_trunk", "trunk_audit.json", lambda fit: trunk_format(), trunk_line))
 
 
 def _after_iteration(job, i):
@@ -620,14 +606,11 @@ def _after_iteration(job, i):
             vis = d["img"] * 0.7 + 0.3 * (np.array([0.0, 1.0, 0.0]) * m + d["img"] * (1 - m))    # :396-404
             nio.imsave(os.path.join(tdir, "segment.png"), vis * d["valid_mask"])
             fit.segmentation = r
-    audit = getattr(fit, "last_stash_audit", None)
-    if audit is not None and audit["iteration"] > job.stash_printed:
-        job.stash_printed = audit["iteration"]
-        print(stash_line(audit))
-    audit = getattr(fit, "last_trunk_audit", None)
-    if audit is not None and audit["iteration"] > job.trunk_printed:
-        job.trunk_printed = audit["iteration"]
-        print(trunk_line(audit))
+    for a in AUDITS:
+        rep = getattr(fit, f"last_{a.kind}_audit", None)
+        if rep is not None and rep["iteration"] > job.audit_printed[a.kind]:
+            job.audit_printed[a.kind] = rep["iteration"]
+            print(a.line(rep))
     if i % args.i_print == 0:
         print(f"[TRAIN] Iter: {i} Loss: {float(fit.net.loss_buf[0]):.6f} Patch Loss: {float(fit.last_patch_loss[0]):.6f} "
               f"({(time.time() - t0) / i * 1e3:.2f} ms/iter, skipped {fit.skipped})")
