@@ -1061,6 +1061,48 @@ int npp_cc_number_host(const int32_t* root_hw, int H, int W, int32_t* numbered_h
 int npp_cc_stats_host(const int32_t* numbered_hw, int H, int W, int C, const uint8_t* values_hwc, int nch, int64_t* size_c,
                       int64_t* sums_cn, uint8_t* border_c, int32_t* box_c4);
 
+/* ---- completion task: the image work in front of the periodicity search (frontend.py; csrc/npp_frontend.hip) ----- */
+/* The per-pixel steps of NPP_proposal/feature_searching.py:14-75 and utils/miscs.py:53-96 behind `--front_end gpu`, each defined by
+ * its host twin in cvlite.py / scipy and equal to it bit for bit.  The image and mask kernels are integer arithmetic; the resize
+ * index rules and the normalisation are float64 in the host's operation order without contraction; there are no float atomics and
+ * no entry keeps state in device memory between calls: every result is a PURE FUNCTION OF ITS INPUT, whatever the launch schedule.
+ * (C, h, w) entries put the channel in a grid dimension (C <= 65535): 66 channels are one launch sequence.  h w < 2^31.  Bad
+ * arguments (null pointers included): NPP_ERR_ARG and a message that names the entry, nothing launched.
+ * npp_resize_nearest_u8 / npp_resize_linear_u8: (H, W) uint8 -> (h, w) uint8 (an array of its own) as cv2.resize with INTER_NEAREST
+ *   (source index min(trunc(dst (src / dst_size)), src - 1)) / INTER_LINEAR (11-bit tap table built in the kernel, vertical pass
+ *   (((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2): cvlite.resize_nearest / cvlite.resize_linear_u8.
+ * npp_normalize_u8: per channel of a (C, h, w) fp32 map, min and max in float64, then uint8((a - mn) / rng 255) in that order;
+ *   rng = 1 for a constant channel (all zeros out): cvlite.normalize_to_uint8.
+ * npp_gaussian_blur3_u8: weights [1 2 1]^2, BORDER_REFLECT_101, (v + 8) >> 4, out of place: cvlite.gaussian_blur3_u8.
+ * npp_canny_mark: cvlite.canny_u8 up to the hysteresis in ONE launch -- Sobel with replicated border, |dx| + |dy|, the integer
+ *   tangent test (13573 / 2^15) with OpenCV's strict / non-strict comparisons, zero magnitude outside the map -- d_map_chw (an array
+ *   of its own) = 0, 1 (kept and > low) or 2 (kept and > high).
+ * npp_canny_hysteresis: `rounds` (1..1024) launches that spread the mark 2 to 8-connected pixels marked 1, tile by tile in LDS;
+ *   d_flags[r] (int32, cleared by the entry) = 1 when round r marked a pixel.  Repeat the call until the last flag reads 0: the
+ *   map is then the unique fixed point, whatever the order in which the tiles ran.
+ * npp_canny_finish: 2 -> 255, else 0 (d_out_chw may be d_map_chw).
+ * npp_edge_count: d_out_hw (h, w) fp32 = the number of channels marked 2 at the pixel where d_eroded_hw is non-zero, else 0 (the
+ *   sum over channels of Canny / 255 inside the mask eroded by npp_binary_morph: proposal.act2edge).
+ * npp_edt_sq: d_dsq_hw (H, W) int32 = the exact SQUARED Euclidean distance of every pixel to the nearest zero pixel of the (H, W)
+ *   uint8 mask (the image border is not a zero, as in scipy.ndimage.distance_transform_edt).  H, W <= 32767.  d_tmp_hw: H W words of
+ *   its own, no initial content required.  The mask must hold a zero pixel (the caller checks; without one every distance reads 2^31).
+ * npp_far_points: the greedy walk of utils/miscs.py:53-96 over the pixels in the order LARGEST d^2 FIRST, TIES BY SMALLEST ROW-MAJOR
+ *   INDEX (np.argsort(-d, kind="stable")), as topk (1..16) rounds of a two-stage argmax in a fixed order: a round accepts the first
+ *   pixel after the last accepted one whose squared distance to every accepted pixel is >= n_min (integers only), and a round that
+ *   finds none accepts none.  d_record int32[2 + 2 topk] (cleared by the entry): [0] accepted count, [1] 0, then (index, d^2) pairs.
+ *   d_scratch: NPP_FAR_POINTS_SCRATCH_BYTES bytes, 8-byte aligned, no initial content required. */
+#define NPP_FAR_POINTS_SCRATCH_BYTES 2048
+int npp_resize_nearest_u8(const uint8_t* d_in_hw, int H, int W, uint8_t* d_out_hw, int h, int w, void* stream);
+int npp_resize_linear_u8(const uint8_t* d_in_hw, int H, int W, uint8_t* d_out_hw, int h, int w, void* stream);
+int npp_normalize_u8(const float* d_in_chw, int C, int h, int w, uint8_t* d_out_chw, void* stream);
+int npp_gaussian_blur3_u8(const uint8_t* d_in_chw, int C, int h, int w, uint8_t* d_out_chw, void* stream);
+int npp_canny_mark(const uint8_t* d_img_chw, int C, int h, int w, int low, int high, uint8_t* d_map_chw, void* stream);
+int npp_canny_hysteresis(uint8_t* d_map_chw, int C, int h, int w, int rounds, int32_t* d_flags, void* stream);
+int npp_canny_finish(const uint8_t* d_map_chw, int C, int h, int w, uint8_t* d_out_chw, void* stream);
+int npp_edge_count(const uint8_t* d_map_chw, int C, int h, int w, const uint8_t* d_eroded_hw, float* d_out_hw, void* stream);
+int npp_edt_sq(const uint8_t* d_mask_hw, int H, int W, uint32_t* d_tmp_hw, int32_t* d_dsq_hw, void* stream);
+int npp_far_points(const int32_t* d_dsq_hw, int H, int W, int topk, int n_min, void* d_scratch, int32_t* d_record, void* stream);
+
 /* ---- quality report: SSIM and region-wise PSNR / MAE of an image against a ground truth (metrics.py) ------------------------- */
 /* Both images are (H, W, 3) fp32 in [0, 1], read as they lie; all arithmetic and every output is float64.  No entry keeps state in
  * device memory between launches and none uses atomics: two calls give identical bits.

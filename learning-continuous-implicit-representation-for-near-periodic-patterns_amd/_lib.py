@@ -195,6 +195,16 @@ SYMBOLS = {
     "npp_cc_label_host": (_i32, [_vp, _i32, _i32, _vp]),
     "npp_cc_number_host": (_i32, [_vp, _i32, _i32, _vp, _vp]),
     "npp_cc_stats_host": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "npp_resize_nearest_u8": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "npp_resize_linear_u8": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "npp_normalize_u8": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "npp_gaussian_blur3_u8": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "npp_canny_mark": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "npp_canny_hysteresis": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "npp_canny_finish": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "npp_edge_count": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "npp_edt_sq": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "npp_far_points": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "npp_ssim_map": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "npp_region_sums_blocks": (_i32, [_i32, _i32]),
     "npp_region_sums": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),

@@ -1536,6 +1536,114 @@ def binary_morph(mask_u8, iterations, dilate):
     return out
 
 
+# ---- completion task: the image work in front of the periodicity search (include/npp_hip.h npp_resize_* .. npp_far_points;
+# frontend.py is the public face).  Device tensors in, device tensors out; scratch is allocated per call.
+FAR_POINTS_SCRATCH_BYTES, FAR_POINTS_MAX_TOPK, EDT_MAX_DIM = 2048, 16, 32767
+
+
+def _req_hw(t, dtype, name):
+    _req(t, dtype, name)
+    if t.dim() != 2 or t.numel() == 0:
+        raise ValueError(f"{name}: expected a non-empty (H, W)")
+    return t.shape
+
+
+def _req_chw(t, dtype, name):
+    _req(t, dtype, name)
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"{name}: expected a non-empty (C, h, w)")
+    return t.shape
+
+
+def _resize_u8(entry, img_u8, dsize):
+    H, W = _req_hw(img_u8, torch.uint8, "img_u8")
+    w, h = int(dsize[0]), int(dsize[1])
+    if h < 1 or w < 1:
+        raise ValueError(f"dsize: expected (w, h) >= 1, got {tuple(dsize)}")
+    out = torch.empty((h, w), dtype=torch.uint8, device=img_u8.device)
+    check(getattr(lib(), entry)(_p(img_u8), H, W, _p(out), h, w, _stream()), entry)
+    return out
+
+
+def resize_nearest_u8(img_u8, dsize):
+    """(H,W) uint8 -> (h,w) uint8, dsize = (w, h): cv2.resize INTER_NEAREST (== cvlite.resize_nearest, bit for bit)."""
+    return _resize_u8("npp_resize_nearest_u8", img_u8, dsize)
+
+
+def resize_linear_u8(img_u8, dsize):
+    """(H,W) uint8 -> (h,w) uint8, dsize = (w, h): cv2.resize INTER_LINEAR on uint8 (== cvlite.resize_linear_u8, bit for bit)."""
+    return _resize_u8("npp_resize_linear_u8", img_u8, dsize)
+
+
+def normalize_u8(act):
+    """(C,h,w) fp32 -> (C,h,w) uint8: per channel uint8((a - min) / (max - min) * 255) in float64, zeros for a constant channel
+    (== cvlite.normalize_to_uint8(channel_idx=(1, 2)))."""
+    C_, h, w = _req_chw(act, torch.float32, "act")
+    out = torch.empty((C_, h, w), dtype=torch.uint8, device=act.device)
+    check(lib().npp_normalize_u8(_p(act), C_, h, w, _p(out), _stream()), "npp_normalize_u8")
+    return out
+
+
+def gaussian_blur3_u8(img_u8):
+    """(C,h,w) uint8 -> (C,h,w) uint8: cv2.GaussianBlur((3, 3), 0) per channel (== cvlite.gaussian_blur3_u8)."""
+    C_, h, w = _req_chw(img_u8, torch.uint8, "img_u8")
+    out = torch.empty_like(img_u8)
+    check(lib().npp_gaussian_blur3_u8(_p(img_u8), C_, h, w, _p(out), _stream()), "npp_gaussian_blur3_u8")
+    return out
+
+
+def canny_mark(img_u8, low, high):
+    """(C,h,w) uint8 -> (C,h,w) uint8 in {0, 1 weak, 2 strong}: cvlite.canny_u8 up to the hysteresis, thresholds already floored."""
+    C_, h, w = _req_chw(img_u8, torch.uint8, "img_u8")
+    out = torch.empty_like(img_u8)
+    check(lib().npp_canny_mark(_p(img_u8), C_, h, w, int(low), int(high), _p(out), _stream()), "npp_canny_mark")
+    return out
+
+
+def canny_hysteresis(marks, rounds=8):
+    """`rounds` hysteresis rounds on a canny_mark map, in place -> (rounds,) int32 device flags, flag r = round r marked a pixel."""
+    C_, h, w = _req_chw(marks, torch.uint8, "marks")
+    flags = torch.empty(int(rounds), dtype=torch.int32, device=marks.device)
+    check(lib().npp_canny_hysteresis(_p(marks), C_, h, w, int(rounds), _p(flags), _stream()), "npp_canny_hysteresis")
+    return flags
+
+
+def canny_finish(marks):
+    """Marks (C,h,w) -> uint8 {0, 255}: 255 where the mark is 2."""
+    C_, h, w = _req_chw(marks, torch.uint8, "marks")
+    out = torch.empty_like(marks)
+    check(lib().npp_canny_finish(_p(marks), C_, h, w, _p(out), _stream()), "npp_canny_finish")
+    return out
+
+
+def edge_count(marks, eroded_u8):
+    """Marks (C,h,w) after the hysteresis, eroded mask (h,w) uint8 -> (h,w) fp32: channels marked 2 per pixel inside the mask."""
+    C_, h, w = _req_chw(marks, torch.uint8, "marks")
+    _req(eroded_u8, torch.uint8, "eroded_u8", (h, w))
+    out = torch.empty((h, w), dtype=torch.float32, device=marks.device)
+    check(lib().npp_edge_count(_p(marks), C_, h, w, _p(eroded_u8), _p(out), _stream()), "npp_edge_count")
+    return out
+
+
+def edt_sq(mask_u8):
+    """(H,W) uint8 -> (H,W) int32: exact squared Euclidean distance to the nearest zero pixel (the caller has checked there is one)."""
+    H, W = _req_hw(mask_u8, torch.uint8, "mask_u8")
+    tmp = torch.empty((H, W), dtype=torch.int32, device=mask_u8.device)
+    out = torch.empty((H, W), dtype=torch.int32, device=mask_u8.device)
+    check(lib().npp_edt_sq(_p(mask_u8), H, W, _p(tmp), _p(out), _stream()), "npp_edt_sq")
+    return out
+
+
+def far_points(dsq, topk, n_min):
+    """Squared distances (H,W) int32 -> (2 + 2 topk,) int32 device record [count, 0, (index, d^2) ...]: the greedy far-point walk,
+    largest d^2 first, ties by smallest row-major index, accepted pixels >= n_min (squared) apart."""
+    H, W = _req_hw(dsq, torch.int32, "dsq")
+    scratch = torch.empty(FAR_POINTS_SCRATCH_BYTES // 8, dtype=torch.int64, device=dsq.device)
+    rec = torch.empty(2 + 2 * int(topk), dtype=torch.int32, device=dsq.device)
+    check(lib().npp_far_points(_p(dsq), H, W, int(topk), int(n_min), _p(scratch), _p(rec), _stream()), "npp_far_points")
+    return rec
+
+
 # ---- segmentation task: 4-connected components (include/npp_hip.h npp_cc_*; regions.py is the public face) ----------------------
 # Device tensors in, device tensors out; the *_host forms take and return NumPy arrays and never touch a GPU.  Scratch is allocated
 # per call and needs no initial content.

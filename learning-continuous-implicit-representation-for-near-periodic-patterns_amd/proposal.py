@@ -108,12 +108,19 @@ class AlexConv1:
     def __call__(self, im_u8):
         """im (H,W,3) uint8 -> (64, Hp/4, Wp/4) fp32, Hp/Wp = H/W padded with zeros to multiples of 32 on the right / bottom
         BEFORE ToTensor + Normalize (feature_searching.py:20-24, utils/ops.py:47-53)."""
-        im = np.asarray(im_u8)[..., :3]
-        H, W = im.shape[:2]
-        Hp, Wp = -(-H // 32) * 32, -(-W // 32) * 32
-        pad = np.zeros((Hp, Wp, 3), np.uint8)
-        pad[:H, :W] = im
-        x = torch.from_numpy(pad).to(self.device).permute(2, 0, 1).float().div(255.0)
+        if isinstance(im_u8, torch.Tensor):                                  # (front_end="gpu": the image is already on the device)
+            im = im_u8[..., :3]
+            H, W = im.shape[:2]
+            pad = torch.zeros((-(-H // 32) * 32, -(-W // 32) * 32, 3), dtype=torch.uint8, device=self.device)
+            pad[:H, :W] = im
+        else:
+            im = np.asarray(im_u8)[..., :3]
+            H, W = im.shape[:2]
+            Hp, Wp = -(-H // 32) * 32, -(-W // 32) * 32
+            pad = np.zeros((Hp, Wp, 3), np.uint8)
+            pad[:H, :W] = im
+            pad = torch.from_numpy(pad)
+        x = pad.to(self.device).permute(2, 0, 1).float().div(255.0)
         mean = torch.tensor(_IMAGENET_MEAN, device=self.device).view(3, 1, 1)
         std = torch.tensor(_IMAGENET_STD, device=self.device).view(3, 1, 1)
         x = ((x - mean) / std)[None]
@@ -123,17 +130,45 @@ class AlexConv1:
         return y.reshape(ho, wo, 64).permute(2, 0, 1).contiguous()
 
 
-def im2act(im_u8, mask, conv1=None, gray_only=False, device="cuda"):
+FRONT_ENDS = ("host", "gpu")
+
+
+def _front_end(front_end, who):
+    """front_end="host": the image work in NumPy (cvlite.py), as ever; "gpu": its device twins (frontend.py), bit-equal."""
+    if front_end not in FRONT_ENDS:
+        raise ValueError(f"{who}: unknown front_end {front_end!r} (expected one of {FRONT_ENDS})")
+    return front_end == "gpu"
+
+
+def _u8_on(a, dev, name):
+    """An (..., ) uint8 image as a contiguous device tensor: uploaded once, or taken as it is when it already lives there."""
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    if t.dtype != torch.uint8:
+        raise TypeError(f"{name}: front_end='gpu' takes uint8, got {t.dtype}")
+    return t.to(dev).contiguous()
+
+
+def im2act(im_u8, mask, conv1=None, gray_only=False, device="cuda", front_end="host"):
     """feature_searching.py:14-50: (activation (C+2 | 2, h, w) * mask, mask (1, h, w)) at a quarter of the image size.
-    Channels: conv1 activations (unless gray_only), the gray image resized image -> 2x(h, w) -> (h, w), the mask."""
-    im = np.asarray(im_u8)[..., :3]
+    Channels: conv1 activations (unless gray_only), the gray image resized image -> 2x(h, w) -> (h, w), the mask.
+    front_end="gpu": image and mask (uint8, NumPy or device tensors) are uploaded once; gray, both resizes and the mask stay there."""
+    gpu = _front_end(front_end, "im2act")
     dev = ops.select_device(device) if conv1 is None else conv1.device
-    h, w = im.shape[0] // 4, im.shape[1] // 4
-    m = torch.from_numpy(np.ascontiguousarray(cvlite.resize_nearest(np.asarray(mask), (w, h))).astype(np.float32)).to(dev)[None]
-    g = cvlite.rgb_to_gray_u8(im)
-    g = cvlite.resize_linear_u8(g, (w * 2, h * 2))
-    g = cvlite.resize_linear_u8(g, (w, h))
-    g = torch.from_numpy(g.astype(np.float32)).to(dev)[None]
+    if gpu:
+        from . import frontend
+        im = _u8_on(im_u8, dev, "im_u8")[..., :3].contiguous()
+        h, w = im.shape[0] // 4, im.shape[1] // 4
+        m = frontend.resize_nearest(_u8_on(mask, dev, "mask"), (w, h)).float()[None]
+        g = frontend.resize_linear_u8(ops.rgb_to_gray_u8(im), (w * 2, h * 2))
+        g = frontend.resize_linear_u8(g, (w, h)).float()[None]
+    else:
+        im = np.asarray(im_u8)[..., :3]
+        h, w = im.shape[0] // 4, im.shape[1] // 4
+        m = torch.from_numpy(np.ascontiguousarray(cvlite.resize_nearest(np.asarray(mask), (w, h))).astype(np.float32)).to(dev)[None]
+        g = cvlite.rgb_to_gray_u8(im)
+        g = cvlite.resize_linear_u8(g, (w * 2, h * 2))
+        g = cvlite.resize_linear_u8(g, (w, h))
+        g = torch.from_numpy(g.astype(np.float32)).to(dev)[None]
     if gray_only:
         act = torch.cat([g, m], 0)
     else:
@@ -143,9 +178,13 @@ def im2act(im_u8, mask, conv1=None, gray_only=False, device="cuda"):
     return act * m, m
 
 
-def act2edge(activation, mask):
+def act2edge(activation, mask, front_end="host"):
     """feature_searching.py:53-69: per channel, normalise to uint8, Canny on the blurred channel inside the mask eroded 4 times
-    (utils/miscs.py:22-33); the edge maps are summed (/255).  -> (2, h, w): [edge count, mask]."""
+    (utils/miscs.py:22-33); the edge maps are summed (/255).  -> (2, h, w): [edge count, mask].
+    front_end="gpu": all channels in one launch sequence on the activation's device (frontend.edge_count), no copy to the host."""
+    if _front_end(front_end, "act2edge"):
+        from . import frontend
+        return torch.cat([frontend.edge_count(activation, mask[0])[None], mask[0].float()[None]])
     a = cvlite.normalize_to_uint8(activation.detach().cpu().numpy(), channel_idx=(1, 2))
     m = mask[0].detach().cpu().numpy()
     edge = np.zeros((1,) + a.shape[1:])
@@ -155,13 +194,14 @@ def act2edge(activation, mask):
 
 
 def search_periodicity_by_feat(img_u8, mask, repeat_range=(2, 32, 5), edge_searching=False, gray_only=False, threshold=10,
-                               conv1=None, device="cuda"):
+                               conv1=None, device="cuda", front_end="host"):
     """feature_searching.py:158-204: feature map -> (optional) edge masking -> brute-force displacement search per
-    repeat-range group -> ([angles], [periods], [shifts]) scaled back to image pixels."""
-    act, m = im2act(img_u8, mask, conv1=conv1, gray_only=gray_only, device=device)
+    repeat-range group -> ([angles], [periods], [shifts]) scaled back to image pixels.  front_end: see im2act / act2edge."""
+    _front_end(front_end, "search_periodicity_by_feat")
+    act, m = im2act(img_u8, mask, conv1=conv1, gray_only=gray_only, device=device, front_end=front_end)
     if edge_searching:
-        edge = act2edge(act[:-1], m).to(act.device)
+        edge = act2edge(act[:-1], m, front_end=front_end).to(act.device)
         act = act * edge[[0]]
-    ratio = float(np.round(np.asarray(img_u8).shape[0] / act.shape[1]))
+    ratio = float(np.round(np.shape(img_u8)[0] / act.shape[1]))
     cands = feature_search(act, m[0], repeat_range=repeat_range, edge_searching=edge_searching, scale=ratio)
     return [c[0] for c in cands], [c[1] for c in cands], [c[2] for c in cands]

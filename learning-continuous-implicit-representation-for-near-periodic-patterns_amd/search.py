@@ -10,7 +10,9 @@ unknown_mask.png, valid_mask.png):
 Flags keep the reference's names (options/arg_config.py:105-145).  Two of them are `store_false` switches there, so the
 reference's DEFAULT run is gray_only = True, edge_searching = True -- no AlexNet involved; passing `--gray_only` turns the
 AlexNet-conv1 features ON (then --alexnet <torchvision alexnet state_dict> is needed, the checkpoint the reference downloads is
-not in its tree).  Under torch.distributed the candidate fits are sharded over the ranks (ProposalRanker.rank)."""
+not in its tree).  `--front_end gpu` runs the image work before the fits (resizes, Canny edge count, pseudo mask) as the HIP kernels of
+frontend.py instead of NumPy / SciPy: bit-equal, with the far-point tie rule fixed.  Under torch.distributed the
+candidate fits are sharded over the ranks (ProposalRanker.rank)."""
 import argparse
 import json
 import os
@@ -50,6 +52,10 @@ def parse(argv=None):
     ap.add_argument("--loss_type", default="robust_loss_adaptive", choices=["robust_loss_adaptive", "l2", "robust_loss"],
                     help="options/arg_config.py:34 (models/mse_calculator.py:19-23): the pixel loss of the candidate fits")
     ap.add_argument("--precision", default=None, choices=["fp32", "bf16"], help="arithmetic of the candidate fits (default fp32)")
+    ap.add_argument("--front_end", default="host", choices=["host", "gpu"],
+                    help="where the image work in front of the candidate fits runs (resizes, Canny edge count, pseudo mask): host = NumPy / "
+                         "SciPy as ever; gpu = the bit-equal HIP kernels of npp_amd.frontend, whose far-point tie rule is fixed (largest "
+                         "distance first, ties by smallest row-major index) instead of following the host's sort")
     ap.add_argument("--device", default="cuda:0")
     return ap.parse_args(argv)
 
@@ -101,14 +107,29 @@ def prepare_image(masked_img, mask, valid_mask, args, conv1=None, trunks=None):
     """The per-image front half of search_image: displacement search -> candidates, pseudo mask -> ranker.  -> (candidates, ranker)."""
     from . import proposal
     from .light import ProposalRanker
+    front_end = getattr(args, "front_end", "host")
     m2 = np.asarray(mask, np.float64).reshape(masked_img.shape[:2])
     v2 = np.asarray(valid_mask, np.float64).reshape(masked_img.shape[:2])
+    if front_end == "gpu":
+        # image and masks cross once, as they were read; the casts, products and everything per pixel after them run on the device
+        from . import frontend, ops
+        dev = ops.select_device(args.device)
+        img_d = torch.from_numpy(np.ascontiguousarray(masked_img)).to(dev).mul(255).to(torch.uint8)
+        m_d, v_d = torch.from_numpy(m2).to(dev), torch.from_numpy(v2).to(dev)
+        img_u8, mask_u8 = img_d, (v_d * m_d).to(torch.uint8)
+    else:
+        img_u8, mask_u8 = np.uint8(np.asarray(masked_img) * 255), np.uint8(v2 * m2)
+    kw = {} if front_end == "host" else {"front_end": front_end}
     angles, periods, shifts = proposal.search_periodicity_by_feat(
-        np.uint8(np.asarray(masked_img) * 255), np.uint8(v2 * m2), repeat_range=tuple(args.search_range),
-        edge_searching=args.edge_searching, gray_only=args.gray_only, conv1=conv1, device=args.device)
+        img_u8, mask_u8, repeat_range=tuple(args.search_range),
+        edge_searching=args.edge_searching, gray_only=args.gray_only, conv1=conv1, device=args.device, **kw)
     if not angles:
         raise RuntimeError("periodicity search: no displacement pair passed the angle test in any repeat-range group")
-    _, i_train, i_val = pseudo_mask_split(m2, v2)
+    if front_end == "gpu":
+        _, i_train, i_val = frontend.pseudo_mask_split(m_d, v_d)
+        i_train, i_val = i_train.cpu().numpy(), i_val.cpu().numpy()
+    else:
+        _, i_train, i_val = pseudo_mask_split(m2, v2)
     t = trunks or {}
     args.carry_effective = _carry(args)
     ranker = ProposalRanker(masked_img, i_train, i_val, device=args.device, N_iters=args.N_iters, N_rand=args.N_rand, W=args.netwidth,
@@ -169,6 +190,8 @@ def _write(args, out, imgs, res):
     # single-rank default here does the same; --independent_candidates / more than one rank start every candidate from the initial
     # latents.  Recorded so that rankings are compared like with like.
     odgt.update(carry_adaptive_latents=bool(getattr(args, "carry_effective", _carry(args))))
+    if getattr(args, "front_end", "host") != "host":                                # (default files are unchanged)
+        odgt.update(front_end=args.front_end)
     with open(os.path.join(out, "config.odgt"), "w") as f:
         json.dump(odgt, f)
         f.write("\n")
