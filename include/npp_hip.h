@@ -545,6 +545,19 @@ int npp_conv3x3_pf(const void* d_x, int N_total, int n_run, int H, int W, int Ci
                 const void* d_pack, const float* d_bias, int mode, const void* d_mask, void* d_y,
                 float* d_tap, int Ctap, const float* tap_scale, const void* d_next_pack, int64_t next_pack_bytes,
                    void* stream);
+/* Which kernel form the launch of these arguments takes, decided on the host alone (no GPU, no stream): the struct the launcher
+ * itself launches from, under the current npp_tune("conv_wink" / "conv_win" / "conv_wstat") values and the once-read
+ * NPP_CONV_TILE.  fold: 0 = npp_conv3x3 / npp_conv3x3_pf, 1 = npp_conv3x3_pool (mode 0, even H and W), 2 = npp_conv3x3_dgrad_pool
+ * (mode 2).  Argument errors are the launcher's (bad mode, n_run, channels, geometry -> NPP_ERR_ARG).  out[NPP_CONV_PLAN_N]:
+ *   FAMILY  0 = conv3x3_kernel (tile), 1 = conv3x3_win_kernel, 2 = conv3x3_wink_kernel
+ *   CT, PT  32-channel and 32-position tiles of one workgroup (win: 2, 8; wink: 2, 4 NPT)
+ *   S       waves (tile) or wave groups (wink: 2) the contraction is split over; win: 1
+ *   NPT     wink only: position tiles per wave (1 or 2), else 0
+ *   WSTAT   1: weight-stationary block numbering (tile family only; GRID_X then counts 8 x ceil(groups / 8) x position blocks)
+ *   GRID_X, GRID_Y, LDS (dynamic LDS bytes of the launch) */
+enum { NPP_CONV_PLAN_FAMILY = 0, NPP_CONV_PLAN_CT, NPP_CONV_PLAN_PT, NPP_CONV_PLAN_S, NPP_CONV_PLAN_NPT, NPP_CONV_PLAN_WSTAT,
+       NPP_CONV_PLAN_GRID_X, NPP_CONV_PLAN_GRID_Y, NPP_CONV_PLAN_LDS, NPP_CONV_PLAN_N };
+int npp_conv3x3_plan(int N_total, int n_run, int H, int W, int Cin, int Cout, int mode, int fold, int32_t out[]);
 
 /* nn.MaxPool2d(2,2) on flat tensors, and its backward fused with the ReLU gate of the pooled
  * layer: dz = (route(dy) + addend) * [x > 0]; the gradient goes to the first maximum of each

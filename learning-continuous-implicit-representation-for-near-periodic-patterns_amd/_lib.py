@@ -283,6 +283,7 @@ SYMBOLS = {
                            C.POINTER(C.c_float), _vp]),
     "npp_conv3x3_pf": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32,
                            C.POINTER(C.c_float), _vp, _i64, _vp]),
+    "npp_conv3x3_plan": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32)]),
     "npp_conv3x3_pool": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(C.c_float), _vp,
                          _i64, _vp]),
     "npp_conv_pair_fwd_ok": (_i32, [_i32, _i32, _i32, _i32, _i32]),

@@ -1280,6 +1280,143 @@ extern "C" int npp_trunk_patch_in_loss_stack(const float* d_pred, int64_t Bp, in
   return check_launch(who);
 }
 
+// ---- the form choice of one npp_conv3x3* launch, on the host alone ---------------------------------------------------------------
+// Everything conv3x3_impl decides between its argument checks and its launch: which kernel family, which tile, the wink kernel's
+// sizes, the weight-stationary numbering, the grid and the dynamic LDS.  conv3x3_impl launches FROM this struct and
+// npp_conv3x3_plan() returns it, so a test that asks which form a shape takes is told what the launch does.
+enum ConvFamily : int { kPlanTile = 0, kPlanWin = 1, kPlanWink = 2 };
+enum ConvFold : int { kFoldNone = 0, kFoldFwdPool = 1, kFoldDgradPool = 2 };
+constexpr int kPlanWinkLdsMax = 160 * 1024;
+struct ConvPlan {
+  int family;                  // ConvFamily
+  int mode;                    // ConvMode of the kernel (the folds are modes of their own)
+  int ct, pt, s;               // tile family: conv3x3_kernel<ct, pt, s>; win: 2, 8, 1; wink: 2, 4 npt, 2 (position tiles per workgroup, wave groups)
+  int npt, wu;                 // wink only: position tiles per wave, window units per chunk in LDS
+  int wstat, wstat_npos, wstat_ncg;
+  unsigned grid_x, grid_y;
+  int lds;                     // dynamic LDS bytes of the launch
+  int pos_tiles, pool_tiles, pool_cbn;
+  uint32_t pack_bytes;
+};
+static int conv3x3_plan(int N_total, int n_run, int H, int W, int Cin, int Cout, int mode, int fold, ConvPlan& p) {
+  int rc = conv_geom_check(N_total, H, W, "npp_conv3x3");
+  if (rc) return rc;
+  if (mode < 0 || mode > 2 || n_run < 1 || n_run > N_total) {
+    set_error("npp_conv3x3: bad argument (mode=%d n_run=%d N=%d)", mode, n_run, N_total);
+    return NPP_ERR_ARG;
+  }
+  if (Cin % 16 || Cout % 16 || Cin < 16 || Cout < 16 || Cin > 512 || Cout > 512) {
+    set_error("npp_conv3x3: Cin=%d / Cout=%d must be multiples of 16 in [16, 512] (pad the image to 16 channels)", Cin, Cout);
+    return NPP_ERR_ARG;
+  }
+  p = ConvPlan{};
+  const int Wp = W + 2, S = (H + 2) * Wp, CI = Cin / 16;
+  const int64_t range = n_run == N_total ? conv_npos_round(N_total, H, W)
+                                         : ((int64_t)n_run * S + kPosRound - 1) / kPosRound * kPosRound;
+  p.pos_tiles = (int)(range / 32);
+  const int cot_n = (Cout + 31) / 32;
+  p.pack_bytes = (uint32_t)((int64_t)cot_n * CI * 9 * 1024);
+  if (fold == kFoldFwdPool) {                      // forward + pool: two-row position tiles over the n_run images' interiors
+    p.pool_cbn = (W + 15) / 16;
+    p.pool_tiles = n_run * (H / 2) * p.pool_cbn;
+    p.pos_tiles = (p.pool_tiles + 1) / 2 * 2;
+    mode = kConvFwdPool;
+  } else if (fold) {
+    mode = kConvDgradPool;
+  }
+  p.mode = mode;
+  // Tile choice: the largest output tile per workgroup (fewest operand bytes per MFMA) that still yields about one
+  // workgroup per CU, with the contraction split over S waves (CI % S == 0).  NPP_CONV_TILE="ct,pt,s" forces one
+  // (diagnostics: tools/conv_probe.py).
+  // Measured on MI355X (tools/conv_probe.py, 12 x 96^2 VGG shapes): 2x2 tiles with S = 4 win wherever the channel steps
+  // split four ways (c2_2 21 -> 18 us, c3_x 20 -> 14.5, c4_x 42 -> 25, c5_x 38 -> 15 with 1x1 S = 4); position-rich layers
+  // (>= 1024 workgroups without a split) are better off unsplit; 2x4 tiles never won at these sizes.
+  struct Cand { int ct, pt, s; int64_t min_wgs; };
+  static const Cand cands[] = {{2, 2, 1, 1024}, {2, 2, 4, 200}, {2, 1, 4, 200}, {1, 1, 4, 100}, {1, 1, 8, 1}, {2, 1, 1, 1}, {1, 1, 1, 1}};
+  auto feasible = [&](const Cand& c) { return cot_n % c.ct == 0 && CI % c.s == 0 && p.pos_tiles % c.pt == 0; };
+  auto wgs = [&](const Cand& c) { return (int64_t)(p.pos_tiles / c.pt) * (cot_n / c.ct); };
+  Cand pick = {1, 1, 1, 1};
+  static const char* force = getenv("NPP_CONV_TILE");
+  bool found = false;
+  if (force && strlen(force) == 5 && force[1] == ',' && force[3] == ',') {
+    for (const Cand& c : cands)
+      if (c.ct == force[0] - '0' && c.pt == force[2] - '0' && c.s == force[4] - '0' && feasible(c)) { pick = c; found = true; }
+  }
+  const bool forced = found;
+  if (!found && CI == 1) {                      // the image layer: 9 k-steps, nothing to split
+    const Cand c = {2, 1, 1, 1};
+    if (feasible(c)) { pick = c; found = true; }
+  }
+  for (const Cand& c : cands) {
+    if (found) break;
+    // (two-row tiles of the pool fold waste columns on narrow maps -- 12 of 16 on VGG16's conv4_3 -- which must not push the
+    //  launch to a smaller tile than the plain layer beside it runs with: 192 workgroups of 2 x 1 tiles beat 384 of 1 x 1)
+    const int64_t need = mode == kConvFwdPool ? c.min_wgs * 9 / 10 : c.min_wgs;
+    if (feasible(c) && wgs(c) >= need) { pick = c; found = true; }
+  }
+  // window form with the contraction split over wave groups (conv3x3_wink_kernel): channel-rich layers (>= 8 channel steps) whose
+  // positions give about one 8-wave workgroup per CU; NPP_CONV_WINK=0: never (A/B comparator), 2: wherever feasible (probe)
+  const int wink_mode = __atomic_load_n(&g_tune.conv_wink, __ATOMIC_RELAXED);
+  if (wink_mode && !forced && !fold && cot_n % 2 == 0 && Wp <= kWinkMaxWp && CI % 2 == 0 && (CI >= 8 || wink_mode == 2) &&
+      (mode == kConvFwd || mode == kConvDgradMask || mode == kConvDgradLin)) {
+    const int64_t wgs2 = (int64_t)(p.pos_tiles / 8) * (cot_n / 2), wgs1 = (int64_t)(p.pos_tiles / 4) * (cot_n / 2);
+    const int npt = (p.pos_tiles % 8 == 0 && wgs2 >= 200) ? 2 : ((p.pos_tiles % 4 == 0 && (wgs1 >= 200 || wink_mode == 2)) ? 1 : 0);
+    if (npt) {
+      const int WPk = 128 * npt, wu = (WPk + 2 * (Wp + 1) + 7) / 8 * 8;
+      const int stage = 2 * 9 * 1024 + 2 * wu * 16;
+      const int red = 4 * 2 * (2 * npt) * 4096;
+      const int smem = 2 * 2 * stage > red ? 2 * 2 * stage : red;
+      if (smem <= kPlanWinkLdsMax) {
+        p.family = kPlanWink; p.ct = 2; p.pt = 4 * npt; p.s = 2; p.npt = npt; p.wu = wu; p.lds = smem;
+        p.grid_x = (unsigned)(p.pos_tiles / (4 * npt)); p.grid_y = (unsigned)(cot_n / 2);
+        return NPP_OK;
+      }
+    }
+  }
+  // window-staged form (conv3x3_win_kernel): few input-channel steps, many positions, 64-channel output blocks
+  const int win_mode = __atomic_load_n(&g_tune.conv_win, __ATOMIC_RELAXED);     // 0: never (A/B comparator)
+  const int64_t win_wgs = (int64_t)(p.pos_tiles / 8) * (cot_n / 2);
+  if (win_mode && !forced && !fold && CI <= 8 && cot_n % 2 == 0 && p.pos_tiles % 8 == 0 && 2 * (Wp + 1) + kWinPos <= kWinMaxUnits &&
+      ((win_wgs >= 200 && mode == kConvFwd && CI <= 4) || win_mode == 2)) {       // measured: only these layers gain (conv1_1, conv1_2, conv2_1 forward)
+    p.family = kPlanWin; p.ct = 2; p.pt = 8; p.s = 1; p.lds = win_lds_bytes<2>();
+    p.grid_x = (unsigned)(p.pos_tiles / 8); p.grid_y = (unsigned)(cot_n / 2);
+    return NPP_OK;
+  }
+  p.family = kPlanTile; p.ct = pick.ct; p.pt = pick.pt; p.s = pick.s;
+  p.lds = pick.s > 1 ? pick.s * pick.ct * pick.pt * 16 * 64 * (int)sizeof(float) : 0;      // the split forms' reduction buffers
+  p.grid_x = (unsigned)(p.pos_tiles / pick.pt); p.grid_y = (unsigned)(cot_n / pick.ct);
+  // weight-stationary numbering where the pack outweighs the activations the launch reads and there are channel groups for all XCDs
+  const int wstat_mode = __atomic_load_n(&g_tune.conv_wstat, __ATOMIC_RELAXED);     // 0: never (A/B comparator)
+  const int64_t act_bytes = (int64_t)(Cin / 8) * range * 16;
+  if (wstat_mode && (int)p.grid_y >= 8 && (int64_t)p.pack_bytes > 2 * act_bytes) {
+    p.wstat = 1; p.wstat_npos = (int)p.grid_x; p.wstat_ncg = (int)p.grid_y;
+    p.grid_x = (unsigned)(8 * (((int)p.grid_y + 7) / 8) * (int)p.grid_x); p.grid_y = 1;
+  }
+  return NPP_OK;
+}
+
+// The plan of the launch npp_conv3x3 / _pf (fold 0), npp_conv3x3_pool (fold 1, mode 0) or npp_conv3x3_dgrad_pool (fold 2, mode 2)
+// would make of these arguments under the current npp_tune values; no GPU is touched.  out: NPP_CONV_PLAN_* of include/npp_hip.h.
+extern "C" int npp_conv3x3_plan(int N_total, int n_run, int H, int W, int Cin, int Cout, int mode, int fold, int32_t out[]) {
+  if (!out || fold < kFoldNone || fold > kFoldDgradPool) { set_error("npp_conv3x3_plan: bad argument (fold=%d)", fold); return NPP_ERR_ARG; }
+  if ((fold == kFoldFwdPool && (mode != kConvFwd || (H & 1) || (W & 1))) || (fold == kFoldDgradPool && mode != kConvDgradLin)) {
+    set_error("npp_conv3x3_plan: fold %d needs mode %d%s (mode=%d H=%d W=%d)", fold, fold == kFoldFwdPool ? kConvFwd : kConvDgradLin,
+              fold == kFoldFwdPool ? " and even H, W" : "", mode, H, W);
+    return NPP_ERR_ARG;
+  }
+  if (fold == kFoldDgradPool) {
+    int rc = conv_geom_check(N_total, 2 * H, 2 * W, "npp_conv3x3_dgrad_pool");
+    if (rc) return rc;
+  }
+  ConvPlan p;
+  int rc = conv3x3_plan(N_total, n_run, H, W, Cin, Cout, mode, fold, p);
+  if (rc) return rc;
+  out[NPP_CONV_PLAN_FAMILY] = p.family; out[NPP_CONV_PLAN_CT] = p.ct; out[NPP_CONV_PLAN_PT] = p.pt; out[NPP_CONV_PLAN_S] = p.s;
+  out[NPP_CONV_PLAN_NPT] = p.npt; out[NPP_CONV_PLAN_WSTAT] = p.wstat; out[NPP_CONV_PLAN_GRID_X] = (int32_t)p.grid_x;
+  out[NPP_CONV_PLAN_GRID_Y] = (int32_t)p.grid_y; out[NPP_CONV_PLAN_LDS] = p.lds;
+  return NPP_OK;
+}
+
 template <int CT, int PT, int S>
 static int conv_launch_mode(const ConvArgs& a, int mode, dim3 grid, hipStream_t s) {
   const char* who = "npp_conv3x3";
@@ -1345,14 +1482,13 @@ static int conv3x3_impl(const void* d_x, int N_total, int n_run, int H, int W, i
                         const PoolFold* fold) {
   int rc = conv_geom_check(N_total, H, W, "npp_conv3x3");
   if (rc) return rc;
-  if (!d_x || !d_pack || (!d_y && !d_tap) || mode < 0 || mode > 2 || n_run < 1 || n_run > N_total) {
+  if (!d_x || !d_pack || (!d_y && !d_tap)) {
     set_error("npp_conv3x3: bad argument (mode=%d n_run=%d N=%d)", mode, n_run, N_total);
     return NPP_ERR_ARG;
   }
-  if (Cin % 16 || Cout % 16 || Cin < 16 || Cout < 16 || Cin > 512 || Cout > 512) {
-    set_error("npp_conv3x3: Cin=%d / Cout=%d must be multiples of 16 in [16, 512] (pad the image to 16 channels)", Cin, Cout);
-    return NPP_ERR_ARG;
-  }
+  ConvPlan plan;
+  rc = conv3x3_plan(N_total, n_run, H, W, Cin, Cout, mode, fold ? (fold->ypool ? kFoldFwdPool : kFoldDgradPool) : kFoldNone, plan);
+  if (rc) return rc;
   if ((mode == kConvFwd && !d_bias) || (mode == kConvDgradMask && !d_mask)) { set_error("npp_conv3x3: mode %d needs bias / mask", mode); return NPP_ERR_ARG; }
   if (d_tap && (Ctap < 1 || Ctap > Cout || (tap_scale && Ctap > 4))) { set_error("npp_conv3x3: bad Ctap=%d", Ctap); return NPP_ERR_ARG; }
   ConvArgs a{};
@@ -1362,108 +1498,51 @@ static int conv3x3_impl(const void* d_x, int N_total, int n_run, int H, int W, i
   for (int i = 0; i < 4; ++i) a.tap_scale[i] = (tap_scale && i < Ctap) ? tap_scale[i] : 1.0f;
   a.nposp = conv_nposp(N_total, H, W);
   a.npos_valid = (int64_t)N_total * a.S;
-  const int64_t range = n_run == N_total ? conv_npos_round(N_total, H, W)
-                                         : ((int64_t)n_run * a.S + kPosRound - 1) / kPosRound * kPosRound;
-  a.pos_tiles = (int)(range / 32);
+  a.pos_tiles = plan.pos_tiles;
   a.x_bytes = (uint32_t)((int64_t)(Cin / 8) * a.nposp * 16);
-  const int cot_n = (Cout + 31) / 32;
-  a.pack_bytes = (uint32_t)((int64_t)cot_n * a.CI * 9 * 1024);
+  a.pack_bytes = plan.pack_bytes;
   a.pf = (const char*)d_next_pack;
   a.pf_bytes = d_next_pack ? next_pack_bytes : 0;
   NPP_DIAG_FILL(a);
   if (fold && fold->ypool) {                       // forward + pool: two-row position tiles over the n_run images' interiors
     a.pool_dz = fold->ypool;
     a.pool_nposp = conv_nposp(N_total, H / 2, W / 2);
-    a.pool_cbn = (W + 15) / 16;
-    a.pool_tiles = n_run * (H / 2) * a.pool_cbn;
-    a.pos_tiles = (a.pool_tiles + 1) / 2 * 2;
-    mode = kConvFwdPool;
+    a.pool_cbn = plan.pool_cbn;
+    a.pool_tiles = plan.pool_tiles;
   } else if (fold) {
     a.pool_x = fold->x; a.pool_add = fold->add; a.pool_dz = fold->dz;
     a.pool_nposp = conv_nposp(N_total, 2 * H, 2 * W);
     a.y = nullptr;
-    mode = kConvDgradPool;
   }
+  mode = plan.mode;
   const hipStream_t s = (hipStream_t)stream;
   const char* who = "npp_conv3x3";
-  // Tile choice: the largest output tile per workgroup (fewest operand bytes per MFMA) that still yields about one
-  // workgroup per CU, with the contraction split over S waves (CI % S == 0).  NPP_CONV_TILE="ct,pt,s" forces one
-  // (diagnostics: tools/conv_probe.py).
-  // Measured on MI355X (tools/conv_probe.py, 12 x 96^2 VGG shapes): 2x2 tiles with S = 4 win wherever the channel steps
-  // split four ways (c2_2 21 -> 18 us, c3_x 20 -> 14.5, c4_x 42 -> 25, c5_x 38 -> 15 with 1x1 S = 4); position-rich layers
-  // (>= 1024 workgroups without a split) are better off unsplit; 2x4 tiles never won at these sizes.
-  struct Cand { int ct, pt, s; int64_t min_wgs; };
-  static const Cand cands[] = {{2, 2, 1, 1024}, {2, 2, 4, 200}, {2, 1, 4, 200}, {1, 1, 4, 100}, {1, 1, 8, 1}, {2, 1, 1, 1}, {1, 1, 1, 1}};
-  auto feasible = [&](const Cand& c) { return cot_n % c.ct == 0 && a.CI % c.s == 0 && a.pos_tiles % c.pt == 0; };
-  auto wgs = [&](const Cand& c) { return (int64_t)(a.pos_tiles / c.pt) * (cot_n / c.ct); };
-  Cand pick = {1, 1, 1, 1};
-  static const char* force = getenv("NPP_CONV_TILE");
-  bool found = false;
-  if (force && strlen(force) == 5 && force[1] == ',' && force[3] == ',') {
-    for (const Cand& c : cands)
-      if (c.ct == force[0] - '0' && c.pt == force[2] - '0' && c.s == force[4] - '0' && feasible(c)) { pick = c; found = true; }
-  }
-  const bool forced = found;
-  if (!found && a.CI == 1) {                    // the image layer: 9 k-steps, nothing to split
-    const Cand c = {2, 1, 1, 1};
-    if (feasible(c)) { pick = c; found = true; }
-  }
-  for (const Cand& c : cands) {
-    if (found) break;
-    // (two-row tiles of the pool fold waste columns on narrow maps -- 12 of 16 on VGG16's conv4_3 -- which must not push the
-    //  launch to a smaller tile than the plain layer beside it runs with: 192 workgroups of 2 x 1 tiles beat 384 of 1 x 1)
-    const int64_t need = mode == kConvFwdPool ? c.min_wgs * 9 / 10 : c.min_wgs;
-    if (feasible(c) && wgs(c) >= need) { pick = c; found = true; }
-  }
-  // window form with the contraction split over wave groups (conv3x3_wink_kernel): channel-rich layers (>= 8 channel steps) whose
-  // positions give about one 8-wave workgroup per CU; NPP_CONV_WINK=0: never (A/B comparator), 2: wherever feasible (probe)
-  const int wink_mode = __atomic_load_n(&g_tune.conv_wink, __ATOMIC_RELAXED);
-  if (wink_mode && !forced && !fold && cot_n % 2 == 0 && a.Wp <= kWinkMaxWp && a.CI % 2 == 0 && (a.CI >= 8 || wink_mode == 2) &&
-      (mode == kConvFwd || mode == kConvDgradMask || mode == kConvDgradLin)) {
-    const int64_t wgs2 = (int64_t)(a.pos_tiles / 8) * (cot_n / 2), wgs1 = (int64_t)(a.pos_tiles / 4) * (cot_n / 2);
-    const int npt = (a.pos_tiles % 8 == 0 && wgs2 >= 200) ? 2 : ((a.pos_tiles % 4 == 0 && (wgs1 >= 200 || wink_mode == 2)) ? 1 : 0);
-    if (npt) {
-      const int WPk = 128 * npt, wu = (WPk + 2 * (a.Wp + 1) + 7) / 8 * 8;
-      const int stage = 2 * 9 * 1024 + 2 * wu * 16;
-      const int red = 4 * 2 * (2 * npt) * 4096;
-      const int smem = 2 * 2 * stage > red ? 2 * 2 * stage : red;
-      const dim3 kgrid((unsigned)(a.pos_tiles / (4 * npt)), (unsigned)(cot_n / 2));
-      constexpr int kWinkLdsMax = 160 * 1024;        // the limit set: the most a launch of these kernels may ask for (smem grows with Wp)
-      if (smem <= kWinkLdsMax) {
-        const dim3 kblock(512);
-        if (npt == 2) {
-          if (mode == kConvFwd) return launch_lds<conv3x3_wink_kernel<2, 2, 2, kConvFwd>>(who, kgrid, kblock, smem, kWinkLdsMax, s, a, wu);
-          if (mode == kConvDgradMask) return launch_lds<conv3x3_wink_kernel<2, 2, 2, kConvDgradMask>>(who, kgrid, kblock, smem, kWinkLdsMax, s, a, wu);
-          return launch_lds<conv3x3_wink_kernel<2, 2, 2, kConvDgradLin>>(who, kgrid, kblock, smem, kWinkLdsMax, s, a, wu);
-        }
-        if (mode == kConvFwd) return launch_lds<conv3x3_wink_kernel<2, 1, 2, kConvFwd>>(who, kgrid, kblock, smem, kWinkLdsMax, s, a, wu);
-        if (mode == kConvDgradMask) return launch_lds<conv3x3_wink_kernel<2, 1, 2, kConvDgradMask>>(who, kgrid, kblock, smem, kWinkLdsMax, s, a, wu);
-        return launch_lds<conv3x3_wink_kernel<2, 1, 2, kConvDgradLin>>(who, kgrid, kblock, smem, kWinkLdsMax, s, a, wu);
-      }
+  const dim3 grid(plan.grid_x, plan.grid_y);
+  if (plan.family == kPlanWink) {
+    constexpr int kWinkLdsMax = kPlanWinkLdsMax;     // the limit set: the most a launch of these kernels may ask for (smem grows with Wp)
+    const dim3 kblock(512);
+    const int smem = plan.lds, wu = plan.wu;
+    if (plan.npt == 2) {
+      if (mode == kConvFwd) return launch_lds<conv3x3_wink_kernel<2, 2, 2, kConvFwd>>(who, grid, kblock, smem, kWinkLdsMax, s, a, wu);
+      if (mode == kConvDgradMask) return launch_lds<conv3x3_wink_kernel<2, 2, 2, kConvDgradMask>>(who, grid, kblock, smem, kWinkLdsMax, s, a, wu);
+      return launch_lds<conv3x3_wink_kernel<2, 2, 2, kConvDgradLin>>(who, grid, kblock, smem, kWinkLdsMax, s, a, wu);
     }
+    if (mode == kConvFwd) return launch_lds<conv3x3_wink_kernel<2, 1, 2, kConvFwd>>(who, grid, kblock, smem, kWinkLdsMax, s, a, wu);
+    if (mode == kConvDgradMask) return launch_lds<conv3x3_wink_kernel<2, 1, 2, kConvDgradMask>>(who, grid, kblock, smem, kWinkLdsMax, s, a, wu);
+    return launch_lds<conv3x3_wink_kernel<2, 1, 2, kConvDgradLin>>(who, grid, kblock, smem, kWinkLdsMax, s, a, wu);
   }
-  // window-staged form (conv3x3_win_kernel): few input-channel steps, many positions, 64-channel output blocks
-  const int win_mode = __atomic_load_n(&g_tune.conv_win, __ATOMIC_RELAXED);     // 0: never (A/B comparator)
-  const int64_t win_wgs = (int64_t)(a.pos_tiles / 8) * (cot_n / 2);
-  if (win_mode && !forced && !fold && a.CI <= 8 && cot_n % 2 == 0 && a.pos_tiles % 8 == 0 && 2 * (a.Wp + 1) + kWinPos <= kWinMaxUnits &&
-      ((win_wgs >= 200 && mode == kConvFwd && a.CI <= 4) || win_mode == 2)) {       // measured: only these layers gain (conv1_1, conv1_2, conv2_1 forward)
-    const dim3 wgrid((unsigned)(a.pos_tiles / 8), (unsigned)(cot_n / 2));
+  if (plan.family == kPlanWin) {
     constexpr int smem = win_lds_bytes<2>();
     const dim3 wblock(256);
-    if (mode == kConvFwd) return launch_lds<conv3x3_win_kernel<2, kConvFwd>>(who, wgrid, wblock, smem, smem, s, a);
-    if (mode == kConvDgradMask) return launch_lds<conv3x3_win_kernel<2, kConvDgradMask>>(who, wgrid, wblock, smem, smem, s, a);
-    return launch_lds<conv3x3_win_kernel<2, kConvDgradLin>>(who, wgrid, wblock, smem, smem, s, a);
+    if (mode == kConvFwd) return launch_lds<conv3x3_win_kernel<2, kConvFwd>>(who, grid, wblock, smem, smem, s, a);
+    if (mode == kConvDgradMask) return launch_lds<conv3x3_win_kernel<2, kConvDgradMask>>(who, grid, wblock, smem, smem, s, a);
+    return launch_lds<conv3x3_win_kernel<2, kConvDgradLin>>(who, grid, wblock, smem, smem, s, a);
   }
-  dim3 grid((unsigned)(a.pos_tiles / pick.pt), (unsigned)(cot_n / pick.ct));
-  // weight-stationary numbering where the pack outweighs the activations the launch reads and there are channel groups for all XCDs
-  const int wstat_mode = __atomic_load_n(&g_tune.conv_wstat, __ATOMIC_RELAXED);     // 0: never (A/B comparator)
-  const int64_t act_bytes = (int64_t)(Cin / 8) * range * 16;
-  if (wstat_mode && (int)grid.y >= 8 && (int64_t)a.pack_bytes > 2 * act_bytes) {
-    a.wstat = 1; a.wstat_npos = (int)grid.x; a.wstat_ncg = (int)grid.y;
+  if (plan.wstat) {
+    a.wstat = 1; a.wstat_npos = plan.wstat_npos; a.wstat_ncg = plan.wstat_ncg;
     a.pf = nullptr; a.pf_bytes = 0;                       // (the next pack is partitioned the same way: nothing to request into EVERY L2)
-    grid = dim3((unsigned)(8 * (((int)grid.y + 7) / 8) * (int)grid.x), 1);
   }
-  const int ct = pick.ct, pt = pick.pt, ws = pick.s;          // one of cands[]
+  const int ct = plan.ct, pt = plan.pt, ws = plan.s;          // one of the plan's candidates
   if (ct == 2 && pt == 2 && ws == 4) return conv_launch_mode<2, 2, 4>(a, mode, grid, s);
   if (ct == 2 && pt == 1 && ws == 4) return conv_launch_mode<2, 1, 4>(a, mode, grid, s);
   if (ct == 1 && pt == 1 && ws == 8) return conv_launch_mode<1, 1, 8>(a, mode, grid, s);

@@ -888,6 +888,20 @@ def conv3x3(x, N_total, n_run, H, W, cin, cout, pack, bias, mode, mask, y, tap=N
                             ctap, ts, _stream()), "npp_conv3x3")
 
 
+CONV_PLAN_FIELDS = ("family", "ct", "pt", "s", "npt", "wstat", "grid_x", "grid_y", "lds")
+CONV_PLAN_FAMILIES = ("tile", "win", "wink")
+
+
+def conv3x3_plan(N_total, n_run, H, W, cin, cout, mode, fold=0):
+    """The kernel form the launch of these arguments takes under the current tune() values (npp_conv3x3_plan: host only, no GPU) as
+    a dict of CONV_PLAN_FIELDS, family by name.  fold: 0 conv3x3, 1 conv3x3_pool (mode 0), 2 conv3x3_dgrad_pool (mode 2)."""
+    out = (C.c_int32 * len(CONV_PLAN_FIELDS))()
+    check(lib().npp_conv3x3_plan(N_total, n_run, H, W, cin, cout, mode, fold, out), "npp_conv3x3_plan")
+    p = dict(zip(CONV_PLAN_FIELDS, (int(v) for v in out)))
+    p["family"] = CONV_PLAN_FAMILIES[p["family"]]
+    return p
+
+
 def conv3x3_pool(x, N_total, n_run, H, W, cin, cout, pack, bias, y, ypool, tap=None, ctap=0, tap_scale=None, next_pack=None):
     """Forward layer + the 2 x 2 max-pool that follows it in one launch (y: the layer's output, ypool: the pooled tensor)."""
     ts = None if tap_scale is None else (C.c_float * len(tap_scale))(*[float(v) for v in tap_scale])
