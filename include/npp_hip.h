@@ -179,6 +179,29 @@ int npp_mlp_fwd_grid(const npp_grid* grid, const npp_embed_cfg* cfg, int width, 
 /* npp_mlp_fwd32 (exact fp32 chain) over a canvas grid: d_out (n, 3). */
 int npp_mlp_fwd32_grid(const npp_grid* grid, const npp_embed_cfg* cfg, int width, const void* d_w32, const float* d_params,
                        float* d_out, int out_act, void* stream);
+/* The _view forms are the _grid forms under a projective map: canvas pixel (i, j) sits at
+ *     d = (m6 i + m7 j) + m8,  y = ((m0 i + m1 j) + m2) / d,  x = ((m3 i + m4 j) + m5) / d
+ * in fp32, every product and sum rounded separately (no fma contraction) and an IEEE quotient; i and j converted exactly.  The same
+ * launch contract: pixels [start, start + n) in row-major order, exactly n rows stored, n == 0 a no-op, indices below 2^24.  A pixel
+ * is IN VIEW iff d > 0 and y and x are finite; a pixel not in view stores (0, 0, 0) and computes on the position (0, 0), so no
+ * non-finite position enters the chain.  d_inside (n bytes, may be null): 0 not in view, 1 in view, 3 in view and inside the fit's
+ * image rectangle, -0.5 <= y < cfg->H - 0.5 and -0.5 <= x < cfg->W - 0.5.  NPP_ERR_ARG (with a message) for a non-finite matrix
+ * entry, width < 1, negative start or n, or an index that reaches 2^24.  The affine map [[1/sy, 0, y0], [0, 1/sx, x0], [0, 0, 1]]
+ * with power-of-two scales is the grid launch at (y0, x0, sy, sx) bit for bit. */
+typedef struct {
+  int64_t start, n;      /* first canvas pixel (row-major) and number of pixels of this launch */
+  int32_t width;         /* canvas width in pixels */
+  float m[9];            /* row-major 3x3 map: canvas (row, col, 1) -> fit-frame (y, x) over d */
+} npp_view;
+/* npp_mlp_fwd_grid under a view: d_out (n, 3), d_inside (n) or null. */
+int npp_mlp_fwd_view(const npp_view* view, const npp_embed_cfg* cfg, int width, const void* d_wf, const float* d_params,
+                     float* d_out, uint8_t* d_inside, int out_act, void* stream);
+/* npp_mlp_fwd32_grid under a view: d_out (n, 3), d_inside (n) or null. */
+int npp_mlp_fwd32_view(const npp_view* view, const npp_embed_cfg* cfg, int width, const void* d_w32, const float* d_params,
+                       float* d_out, uint8_t* d_inside, int out_act, void* stream);
+/* The positions and inside bytes of such a launch by plain C++ on the host (the same rule, compiled without contraction): out_yx
+ * (n, 2) [y, x] ((0, 0) for a pixel not in view), inside (n) or null; H, W: the fit's image size (cfg->H, cfg->W). */
+int npp_view_coords_host(const npp_view* view, int H, int W, float* out_yx, uint8_t* inside);
 /* npp_mlp_fwd_act (inference) on fp32 positions: coords (Bp, 2) -> d_pred (Bp, 3), Bp a multiple of NPP_ROW_TILE. */
 int npp_mlp_fwd_coordf(const float* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_wf,
                        const float* d_params, float* d_pred, int out_act, void* stream);
@@ -1115,6 +1138,23 @@ int npp_canny_finish(const uint8_t* d_map_chw, int C, int h, int w, uint8_t* d_o
 int npp_edge_count(const uint8_t* d_map_chw, int C, int h, int w, const uint8_t* d_eroded_hw, float* d_out_hw, void* stream);
 int npp_edt_sq(const uint8_t* d_mask_hw, int H, int W, uint32_t* d_tmp_hw, int32_t* d_dsq_hw, void* stream);
 int npp_far_points(const int32_t* d_dsq_hw, int H, int W, int topk, int n_min, void* d_scratch, int32_t* d_record, void* stream);
+
+/* ---- perspective views: warp a uint8 image or mask under a 3 x 3 map (view.py; csrc/npp_view.hip) ------------------------------ */
+/* d_src (Hs, Ws, C) uint8 with C in 1..4 -> d_out (Ho, Wo, C) and, unless null, d_inside (Ho, Wo).  m: the row-major map of npp_view
+ * as nine doubles; canvas pixel (i, j) reads the source at
+ *     d = (m6 i + m7 j) + m8,  y = ((m0 i + m1 j) + m2) / d,  x = ((m3 i + m4 j) + m5) / d
+ * in FLOAT64, every product and sum rounded separately (no fma contraction), so NumPy, the host twin and the kernel agree bit for bit.
+ * mode 0, nearest: taps iy = floor(y + 0.5), ix = floor(x + 0.5); in the source iff d > 0, y and x finite, 0 <= iy < Hs, 0 <= ix < Ws.
+ * mode 1, bilinear: in the source iff d > 0, finite, 0 <= y <= Hs - 1 and 0 <= x <= Ws - 1; y0 = floor(y), y1 = min(y0 + 1, Hs - 1),
+ *   fy = y - y0, likewise in x; v = ((1 - fy) ((1 - fx) a00 + fx a01)) + (fy ((1 - fx) a10 + fx a11)) in float64 in that order, and
+ *   the result is floor(v + 0.5) clamped to [0, 255].
+ * A pixel outside the source: value 0 and inside 0; otherwise inside 255.  Ho Wo and Hs Ws < 2^31.  Bad arguments (null pointers,
+ * a non-finite matrix entry, a mode other than 0 or 1): NPP_ERR_ARG and a message, nothing launched.  The _host form is the same
+ * definition by plain C++ on host arrays. */
+int npp_warp_image_u8(const uint8_t* d_src, int Hs, int Ws, int C, int Ho, int Wo, const double m[9], int mode, uint8_t* d_out,
+                      uint8_t* d_inside, void* stream);
+int npp_warp_image_u8_host(const uint8_t* src, int Hs, int Ws, int C, int Ho, int Wo, const double m[9], int mode, uint8_t* out,
+                           uint8_t* inside);
 
 /* ---- quality report: SSIM and region-wise PSNR / MAE of an image against a ground truth (metrics.py) ------------------------- */
 /* Both images are (H, W, 3) fp32 in [0, 1], read as they lie; all arithmetic and every output is float64.  No entry keeps state in

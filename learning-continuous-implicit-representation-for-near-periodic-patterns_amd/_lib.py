@@ -92,6 +92,12 @@ class Grid(C.Structure):
                 ("sy", C.c_float), ("sx", C.c_float)]
 
 
+class View(C.Structure):
+    """npp_view (include/npp_hip.h): canvas pixels [start, start + n) of a canvas `width` pixels wide; pixel (i, j) is evaluated at
+    ((m0 i + m1 j) + m2, (m3 i + m4 j) + m5) / ((m6 i + m7 j) + m8) of the fit's pixel frame."""
+    _fields_ = [("start", C.c_int64), ("n", C.c_int64), ("width", C.c_int32), ("m", C.c_float * 9)]
+
+
 class DevImage(C.Structure):
     """npp_dev_image (include/npp_hip.h): the per-image constants of the rng_mode="device" launches."""
     _fields_ = [("sat", C.c_void_p), ("pool_val", C.c_void_p), ("pool_train", C.c_void_p), ("n_pool_val", C.c_int64),
@@ -102,6 +108,7 @@ class DevImage(C.Structure):
 _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 _cfgp = C.POINTER(EmbedCfg)
 _gridp = C.POINTER(Grid)
+_viewp = C.POINTER(View)
 
 # every symbol include/npp_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -130,6 +137,9 @@ SYMBOLS = {
     "npp_mlp_fwd_act": (_i32, [_vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "npp_mlp_fwd_grid": (_i32, [_gridp, _cfgp, _i32, _vp, _vp, _vp, _i32, _vp]),
     "npp_mlp_fwd32_grid": (_i32, [_gridp, _cfgp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "npp_mlp_fwd_view": (_i32, [_viewp, _cfgp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "npp_mlp_fwd32_view": (_i32, [_viewp, _cfgp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "npp_view_coords_host": (_i32, [_viewp, _i32, _i32, _vp, _vp]),
     "npp_mlp_fwd_coordf": (_i32, [_vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _i32, _vp]),
     "npp_mlp_fwd32_coordf": (_i32, [_vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _i32, _vp]),
     "npp_warp_fwd_coordf": (_i32, [_vp, _i64, _cfgp, _vp, _vp]),
@@ -205,6 +215,8 @@ SYMBOLS = {
     "npp_edge_count": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "npp_edt_sq": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "npp_far_points": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "npp_warp_image_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _i32, _vp, _vp, _vp]),
+    "npp_warp_image_u8_host": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _i32, _vp, _vp]),
     "npp_ssim_map": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "npp_region_sums_blocks": (_i32, [_i32, _i32]),
     "npp_region_sums": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),

@@ -65,6 +65,25 @@ int check_grid(const npp_grid* g, const char* who) {
   return NPP_OK;
 }
 
+// Arguments of a view launch (include/npp_hip.h npp_view): the grid launch's checks with a finite matrix in place of its origin and scale
+int check_view(const npp_view* v, const char* who) {
+  if (!v) { set_error("%s: null view", who); return NPP_ERR_ARG; }
+  for (int k = 0; k < 9; ++k)
+    if (!isfinite(v->m[k])) { set_error("%s: matrix entry m[%d] = %g is not finite", who, k, v->m[k]); return NPP_ERR_ARG; }
+  if (v->width < 1) { set_error("%s: canvas width %d must be >= 1", who, v->width); return NPP_ERR_ARG; }
+  if (v->start < 0 || v->n < 0) { set_error("%s: start=%lld / n=%lld must be >= 0", who, (long long)v->start, (long long)v->n); return NPP_ERR_ARG; }
+  constexpr int64_t kExact = 1 << 24;                        // canvas indices above this are not exact in fp32
+  if (v->width > kExact) { set_error("%s: canvas width %d: column indices would reach 2^24", who, v->width); return NPP_ERR_ARG; }
+  if (v->n == 0) return NPP_OK;
+  if (v->start > INT64_MAX - v->n || (v->start + v->n - 1) / v->width >= kExact) {
+    set_error("%s: canvas pixels [%lld, %lld + %lld) at width %d: row indices would reach 2^24", who, (long long)v->start,
+              (long long)v->start, (long long)v->n, v->width);
+    return NPP_ERR_ARG;
+  }
+  if ((v->n + NPP_ROW_TILE - 1) / NPP_ROW_TILE > 0x7fffffffLL) { set_error("%s: n=%lld too large for one launch", who, (long long)v->n); return NPP_ERR_ARG; }
+  return NPP_OK;
+}
+
 #ifndef NPP_EMB_ROWS
 #define NPP_EMB_ROWS 32
 #endif

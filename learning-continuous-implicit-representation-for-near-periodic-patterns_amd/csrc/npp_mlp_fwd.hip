@@ -127,6 +127,7 @@ struct FwdArgs {
   // holds g.n rows)
   const float* coordsf;
   npp_grid g;
+  ViewArgs view;     // CM == kCoordView (npp_mlp_fwd_view): the projective map, the inside bytes (pred then holds view.v.n rows)
 };
 
 struct EmbTabs {
@@ -680,7 +681,8 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[NTW][kNB], char* out, int
 // ACT: the output nonlinearity is read from A_.out_act (npp_mlp_fwd_act: tanh / raw); false = the sigmoid, compiled in -- a template
 // parameter for the same reason as STACK (the run-time test cost the default launch 0.9 us in a same-box A/B)
 // CM: coordinate mode (npp_common.h CoordMode) of the render paths -- fp32 positions (npp_mlp_fwd_coordf) or the implicit canvas
-// grid (npp_mlp_fwd_grid); both read the nonlinearity from A_.out_act like ACT.  kCoordI32 is every other launch, unchanged.
+// grid (npp_mlp_fwd_grid) or that canvas under a projective map (npp_mlp_fwd_view); all read the nonlinearity from A_.out_act like
+// ACT.  kCoordI32 is every other launch, unchanged.
 template <int TRAIN, bool MULTI, bool EMB_IN = false, bool STACK = false, bool ACT = false, int CM = kCoordI32>
 __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdArgs A_, EmbedDev e_arg, NetDesc d) {
   static_assert(CM == kCoordI32 || (TRAIN == 0 && !EMB_IN && !STACK), "the render coordinate modes are inference-only");
@@ -756,7 +758,8 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
       sX[L.tid] = (float)c.y;
     } else {
       float y, x;
-      load_coord<CM>(A_.coordsf, A_.g, row0 + L.tid, y, x);
+      if (CM == kCoordView) view_row(A_.view, row0 + L.tid, y, x);       // (0, 0) for a pixel not in view
+      else load_coord<CM>(A_.coordsf, A_.g, row0 + L.tid, y, x);
       sY[L.tid] = y;
       sX[L.tid] = x;
     }
@@ -973,7 +976,15 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
       for (int w = 0; w < kNT / 2; ++w) z += sRGB[(w * kRowTile + row) * 3 + c];   // P's neuron tiles, in order
       float o = 1.0f / (1.0f + __expf(-z));                         // helpers.py:56 sigmoid
       if ((EMB_IN || ACT || CM != kCoordI32) && A_.out_act != 1) o = A_.out_act == 2 ? tanhf(z) : z;   // helpers.py:57-58 tanh (--normalize_type 2) / raw network output
-      if (CM != kCoordGrid || row0 + row < A_.g.n) s_pred[(row0 + row) * 3 + c] = o;   // a grid launch stores exactly g.n rows
+      if (CM == kCoordView) {
+        // the inside byte again from the map (nothing is carried through the chain); a pixel not in view stores zeros
+        if (row0 + row < A_.view.v.n) {
+          float y, x;
+          const uint8_t in = view_row(A_.view, row0 + row, y, x);
+          s_pred[(row0 + row) * 3 + c] = in ? o : 0.0f;
+          if (c == 0 && A_.view.inside) A_.view.inside[row0 + row] = in;
+        }
+      } else if (CM != kCoordGrid || row0 + row < A_.g.n) s_pred[(row0 + row) * 3 + c] = o;   // a grid launch stores exactly g.n rows
     }
   }
 #pragma unroll
@@ -994,15 +1005,15 @@ using namespace npp;
 
 // Every launched instantiation of mlp_fwd_kernel, as one selection over (kernel form, stash form T, K > 1).  The entry point names
 // the form; T: 0 no stash (inference), 1 the 16-bit training stash, 2 the 8-bit one (npp_tune "stash8").  The stacked form always
-// trains and the render forms never do, so only those T exist for them: 3 forms x 3 T + stacked x 2 T + 2 render forms, x 2 for K.
-enum FwdForm { kFwdPlain, kFwdEmbIn, kFwdStack, kFwdAct, kFwdCoordF, kFwdGrid };
+// trains and the render forms never do, so only those T exist for them: 3 forms x 3 T + stacked x 2 T + 3 render forms, x 2 for K.
+enum FwdForm { kFwdPlain, kFwdEmbIn, kFwdStack, kFwdAct, kFwdCoordF, kFwdGrid, kFwdView };
 struct FwdLaunch {
   const FwdArgs& A; const EmbedDev& e; const NetDesc& d;
   dim3 grid; hipStream_t stream; const char* who;
   template <int T, FwdForm F>
   int go() const {
     constexpr bool EMB_IN = F == kFwdEmbIn, STACK = F == kFwdStack, ACT = F == kFwdAct;      // ACT: the output nonlinearity is read from the arguments
-    constexpr int CM = F == kFwdCoordF ? kCoordF32 : F == kFwdGrid ? kCoordGrid : kCoordI32;
+    constexpr int CM = F == kFwdCoordF ? kCoordF32 : F == kFwdGrid ? kCoordGrid : F == kFwdView ? kCoordView : kCoordI32;
     const dim3 block(kThreads);
     return d.K > 1 ? launch_lds<mlp_fwd_kernel<T, true, EMB_IN, STACK, ACT, CM>>(who, grid, block, kSmemFwd, kSmemFwd, stream, A, e, d)
                    : launch_lds<mlp_fwd_kernel<T, false, EMB_IN, STACK, ACT, CM>>(who, grid, block, kSmemFwd, kSmemFwd, stream, A, e, d);
@@ -1018,7 +1029,7 @@ static int fwd_launch(FwdForm f, const FwdArgs& A, const EmbedDev& e, const NetD
   if (f == kFwdEmbIn) return T == 2 ? L.go<2, kFwdEmbIn>() : T == 1 ? L.go<1, kFwdEmbIn>() : L.go<0, kFwdEmbIn>();
   if (f == kFwdAct) return T == 2 ? L.go<2, kFwdAct>() : T == 1 ? L.go<1, kFwdAct>() : L.go<0, kFwdAct>();
   if (f == kFwdPlain) return T == 2 ? L.go<2, kFwdPlain>() : T == 1 ? L.go<1, kFwdPlain>() : L.go<0, kFwdPlain>();
-  return f == kFwdCoordF ? L.go<0, kFwdCoordF>() : L.go<0, kFwdGrid>();
+  return f == kFwdCoordF ? L.go<0, kFwdCoordF>() : f == kFwdGrid ? L.go<0, kFwdGrid>() : L.go<0, kFwdView>();
 }
 
 static int fwd_check(int64_t Bp, int width, const void* in, const void* d_wf, const float* d_params, const float* d_pred,
@@ -1074,6 +1085,7 @@ extern "C" int npp_mlp_fwd_emb(const float* d_emb, int64_t ld, int64_t Bp, int K
 // ---- render paths: fp32 positions / the implicit canvas grid (include/npp_hip.h "continuous coordinates") -----------------------
 namespace npp {
 int check_grid(const npp_grid* g, const char* who);
+int check_view(const npp_view* v, const char* who);
 }
 
 extern "C" int npp_mlp_fwd_coordf(const float* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_wf,
@@ -1104,6 +1116,23 @@ extern "C" int npp_mlp_fwd_grid(const npp_grid* grid, const npp_embed_cfg* cfg, 
   A.Bp = n_wg * kRowTile; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_out; A.out_act = out_act;
   A.g = *grid;
   return fwd_launch(kFwdGrid, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, who);
+}
+
+extern "C" int npp_mlp_fwd_view(const npp_view* view, const npp_embed_cfg* cfg, int width, const void* d_wf, const float* d_params,
+                                float* d_out, uint8_t* d_inside, int out_act, void* stream) {
+  const char* who = "npp_mlp_fwd_view";
+  int rc = check_view(view, who);
+  if (rc) return rc;
+  if ((rc = check_embed_cfg(cfg, who))) return rc;
+  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
+  if (view->n == 0) return NPP_OK;
+  if (!d_wf || !d_params || !d_out) { set_error("%s: null pointer", who); return NPP_ERR_ARG; }
+  if (out_act < 0 || out_act > 2) { set_error("%s: out_act=%d", who, out_act); return NPP_ERR_ARG; }
+  const int64_t n_wg = (view->n + kRowTile - 1) / kRowTile;
+  FwdArgs A{};
+  A.Bp = n_wg * kRowTile; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_out; A.out_act = out_act;
+  A.view = ViewArgs{*view, d_inside, cfg->H, cfg->W};
+  return fwd_launch(kFwdView, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, who);
 }
 
 // ---- stacked form: M images per launch (npp_common.h "stacked launches") ----------------------------------------------------

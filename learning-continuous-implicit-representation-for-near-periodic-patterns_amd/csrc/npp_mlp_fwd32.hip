@@ -26,6 +26,7 @@ namespace npp {
 EmbedDev make_embed_dev(const npp_embed_cfg& c);
 int check_embed_cfg(const npp_embed_cfg* c, const char* who);
 int check_grid(const npp_grid* g, const char* who);
+int check_view(const npp_view* v, const char* who);
 
 constexpr int kT32 = 32 * kNT;                     // threads: 2 neuron tiles per wave (4 waves at W = 256, 8 at W = 512)
 constexpr int kRegion32 = kW * kRowTile * 4;       // 64 KiB: 256 features x 64 rows fp32
@@ -44,6 +45,7 @@ struct Fwd32Args {
   const float* coordsf;
   npp_grid g;
   float* stash;              // STASH: (stash32_rows(K), Bp) fp32, feature-major
+  ViewArgs view;             // CM == kCoordView (npp_mlp_fwd32_view): the projective map, the inside bytes (pred then holds view.v.n rows)
 };
 
 // B operands generated from the 22 warped coordinates of one proposal (sV[i][row], fp32): k-step q < 220 contracts
@@ -82,7 +84,8 @@ __device__ __forceinline__ void stash32_tiles(const f32x16 (&acc)[NTW][kNB], flo
     }
 }
 
-// CM: coordinate mode (npp_common.h CoordMode) -- int32 pixel indices, fp32 positions or the implicit canvas grid
+// CM: coordinate mode (npp_common.h CoordMode) -- int32 pixel indices, fp32 positions, the implicit canvas grid or that canvas
+// under a projective map
 // STASH: also write the training stash (A_.stash)
 template <bool MULTI, int CM = kCoordI32, bool STASH = false>
 __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedDev e_arg, NetDesc d, Desc32 d32) {
@@ -126,7 +129,8 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
       sX[tid] = (float)c.y;
     } else {
       float y, x;
-      load_coord<CM>(A_.coordsf, A_.g, row0 + tid, y, x);
+      if (CM == kCoordView) view_row(A_.view, row0 + tid, y, x);         // (0, 0) for a pixel not in view
+      else load_coord<CM>(A_.coordsf, A_.g, row0 + tid, y, x);
       sY[tid] = y;
       sX[tid] = x;
     }
@@ -280,7 +284,15 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
 #pragma unroll
     for (int w = 0; w < kNT / 2; ++w) z += sRGB[(w * kRowTile + row) * 3 + c];
     const float o = A_.out_act == 1 ? 1.0f / (1.0f + expf(-z)) : (A_.out_act == 2 ? tanhf(z) : z);
-    if (CM != kCoordGrid || row0 + row < A_.g.n) A_.pred[(row0 + row) * 3 + c] = o;
+    if (CM == kCoordView) {
+      // the inside byte again from the map (nothing is carried through the chain); a pixel not in view stores zeros
+      if (row0 + row < A_.view.v.n) {
+        float y, x;
+        const uint8_t in = view_row(A_.view, row0 + row, y, x);
+        A_.pred[(row0 + row) * 3 + c] = in ? o : 0.0f;
+        if (c == 0 && A_.view.inside) A_.view.inside[row0 + row] = in;
+      }
+    } else if (CM != kCoordGrid || row0 + row < A_.g.n) A_.pred[(row0 + row) * 3 + c] = o;
   }
 }
 
@@ -368,6 +380,21 @@ extern "C" int npp_mlp_fwd32_grid(const npp_grid* grid, const npp_embed_cfg* cfg
   const int64_t n_wg = (grid->n + kRowTile - 1) / kRowTile;
   Fwd32Args A{nullptr, n_wg * kRowTile, (const float*)d_w32, d_params, d_out, out_act, nullptr, *grid};
   return fwd32_launch<kCoordGrid>(A, cfg, n_wg, stream, who);
+}
+
+extern "C" int npp_mlp_fwd32_view(const npp_view* view, const npp_embed_cfg* cfg, int width, const void* d_w32, const float* d_params,
+                                  float* d_out, uint8_t* d_inside, int out_act, void* stream) {
+  const char* who = "npp_mlp_fwd32_view";
+  int rc = check_view(view, who);
+  if (rc) return rc;
+  if ((rc = check_embed_cfg(cfg, who))) return rc;
+  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
+  if (view->n == 0) return NPP_OK;
+  if (!d_w32 || !d_params || !d_out || out_act < 0 || out_act > 2) { set_error("%s: bad argument", who); return NPP_ERR_ARG; }
+  const int64_t n_wg = (view->n + kRowTile - 1) / kRowTile;
+  Fwd32Args A{nullptr, n_wg * kRowTile, (const float*)d_w32, d_params, d_out, out_act, nullptr, npp_grid{}, nullptr,
+              ViewArgs{*view, d_inside, cfg->H, cfg->W}};
+  return fwd32_launch<kCoordView>(A, cfg, n_wg, stream, who);
 }
 
 // The forward of the exact-fp32 fit: npp_mlp_fwd32 plus the stash (d_stash: sizes[1] of npp_train_workspace32)

@@ -1,0 +1,127 @@
+// npp_view.hip -- perspective views (view.py, DESIGN.md "Perspective views"): the uint8 image / mask warp under a 3 x 3 map with its
+// coverage mask, and the host twins of the view rule.  The warp's positions and bilinear blend are float64 in the operation order
+// include/npp_hip.h writes down, every product and sum rounded separately: one function body serves the kernel (spelt __d*_rn) and
+// the host twin (plain operators; the file is built with -ffp-contract=off and the pragma holds it without the flag), so NumPy, the
+// host and the device agree bit for bit.  One thread per canvas pixel, all channels; no atomics, no state between calls.
+#include "npp_common.h"
+
+namespace npp {
+
+#ifdef __HIP_DEVICE_COMPILE__
+#define NPP_WARP_OP(name, intr, op) __host__ __device__ __forceinline__ double name(double a, double b) { return intr(a, b); }
+#else
+#define NPP_WARP_OP(name, intr, op) \
+  __host__ __device__ __forceinline__ double name(double a, double b) { _Pragma("clang fp contract(off)") return a op b; }
+#endif
+NPP_WARP_OP(warp_mul, __dmul_rn, *)
+NPP_WARP_OP(warp_add, __dadd_rn, +)
+NPP_WARP_OP(warp_sub, __dsub_rn, -)
+NPP_WARP_OP(warp_div, __ddiv_rn, /)
+#undef NPP_WARP_OP
+
+struct WarpMap { double m[9]; };
+
+// Canvas pixel (i, j): C bytes of out and one of inside (nullable)
+__host__ __device__ __forceinline__ void warp_pixel(const uint8_t* __restrict__ src, int Hs, int Ws, int C, const WarpMap& M, int mode,
+                                                    int i, int j, uint8_t* __restrict__ out, uint8_t* __restrict__ inside) {
+  const double fi = (double)i, fj = (double)j;
+  const double d = warp_add(warp_add(warp_mul(M.m[6], fi), warp_mul(M.m[7], fj)), M.m[8]);
+  const double y = warp_div(warp_add(warp_add(warp_mul(M.m[0], fi), warp_mul(M.m[1], fj)), M.m[2]), d);
+  const double x = warp_div(warp_add(warp_add(warp_mul(M.m[3], fi), warp_mul(M.m[4], fj)), M.m[5]), d);
+  bool in = d > 0.0 && __builtin_isfinite(y) && __builtin_isfinite(x);
+  if (mode == 0) {
+    // the comparisons are on the floored doubles: no integer conversion of a position out of range
+    const double ry = floor(warp_add(y, 0.5)), rx = floor(warp_add(x, 0.5));
+    in = in && ry >= 0.0 && ry < (double)Hs && rx >= 0.0 && rx < (double)Ws;
+    const uint8_t* s = src + ((int64_t)(in ? (int)ry : 0) * Ws + (in ? (int)rx : 0)) * C;
+    for (int c = 0; c < C; ++c) out[c] = in ? s[c] : 0;
+  } else {
+    in = in && y >= 0.0 && y <= (double)(Hs - 1) && x >= 0.0 && x <= (double)(Ws - 1);
+    const double y0f = in ? floor(y) : 0.0, x0f = in ? floor(x) : 0.0;
+    const int y0 = (int)y0f, x0 = (int)x0f;
+    const int y1 = y0 + 1 < Hs ? y0 + 1 : Hs - 1, x1 = x0 + 1 < Ws ? x0 + 1 : Ws - 1;
+    const double fy = in ? warp_sub(y, y0f) : 0.0, fx = in ? warp_sub(x, x0f) : 0.0;
+    const double gy = warp_sub(1.0, fy), gx = warp_sub(1.0, fx);
+    const uint8_t* r0 = src + (int64_t)y0 * Ws * C;
+    const uint8_t* r1 = src + (int64_t)y1 * Ws * C;
+    for (int c = 0; c < C; ++c) {
+      const int64_t c0 = (int64_t)x0 * C + c, c1 = (int64_t)x1 * C + c;
+      const double a00 = (double)r0[c0], a01 = (double)r0[c1], a10 = (double)r1[c0], a11 = (double)r1[c1];
+      const double top = warp_add(warp_mul(gx, a00), warp_mul(fx, a01)), bot = warp_add(warp_mul(gx, a10), warp_mul(fx, a11));
+      double v = floor(warp_add(warp_add(warp_mul(gy, top), warp_mul(fy, bot)), 0.5));
+      v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
+      out[c] = in ? (uint8_t)(int)v : 0;
+    }
+  }
+  if (inside) *inside = in ? 255 : 0;
+}
+
+__global__ __launch_bounds__(256) void warp_image_kernel(const uint8_t* __restrict__ src, int Hs, int Ws, int C, int Ho, int Wo, WarpMap M,
+                                                         int mode, uint8_t* __restrict__ out, uint8_t* __restrict__ inside) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (int64_t)Ho * Wo) return;
+  const int i = (int)(p / Wo), j = (int)(p - (int64_t)i * Wo);
+  warp_pixel(src, Hs, Ws, C, M, mode, i, j, out + p * C, inside ? inside + p : nullptr);
+}
+
+static int warp_check(const char* who, const void* src, int Hs, int Ws, int C, int Ho, int Wo, const double* m, int mode, const void* out) {
+  if (!src || !out || src == out || !m) { set_error("%s: null pointer (the output needs an array of its own)", who); return NPP_ERR_ARG; }
+  if (Hs < 1 || Ws < 1 || Ho < 1 || Wo < 1 || (int64_t)Hs * Ws >= ((int64_t)1 << 31) || (int64_t)Ho * Wo >= ((int64_t)1 << 31)) {
+    set_error("%s: bad shape (source %d x %d, canvas %d x %d: all >= 1 and fewer than 2^31 pixels)", who, Hs, Ws, Ho, Wo);
+    return NPP_ERR_ARG;
+  }
+  if (C < 1 || C > 4) { set_error("%s: C=%d channels (1..4)", who, C); return NPP_ERR_ARG; }
+  if (mode != 0 && mode != 1) { set_error("%s: mode=%d (0 nearest, 1 bilinear)", who, mode); return NPP_ERR_ARG; }
+  for (int k = 0; k < 9; ++k)
+    if (!isfinite(m[k])) { set_error("%s: matrix entry m[%d] = %g is not finite", who, k, m[k]); return NPP_ERR_ARG; }
+  return NPP_OK;
+}
+
+int check_view(const npp_view* v, const char* who);
+
+}  // namespace npp
+
+using namespace npp;
+
+extern "C" int npp_warp_image_u8(const uint8_t* d_src, int Hs, int Ws, int C, int Ho, int Wo, const double m[9], int mode, uint8_t* d_out,
+                                 uint8_t* d_inside, void* stream) {
+  const int rc = warp_check("npp_warp_image_u8", d_src, Hs, Ws, C, Ho, Wo, m, mode, d_out);
+  if (rc) return rc;
+  WarpMap M;
+  for (int k = 0; k < 9; ++k) M.m[k] = m[k];
+  hipLaunchKernelGGL(warp_image_kernel, dim3((unsigned)(((int64_t)Ho * Wo + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_src, Hs, Ws,
+                     C, Ho, Wo, M, mode, d_out, d_inside);
+  return check_launch("npp_warp_image_u8");
+}
+
+extern "C" int npp_warp_image_u8_host(const uint8_t* src, int Hs, int Ws, int C, int Ho, int Wo, const double m[9], int mode, uint8_t* out,
+                                      uint8_t* inside) {
+  const int rc = warp_check("npp_warp_image_u8_host", src, Hs, Ws, C, Ho, Wo, m, mode, out);
+  if (rc) return rc;
+  WarpMap M;
+  for (int k = 0; k < 9; ++k) M.m[k] = m[k];
+  for (int i = 0; i < Ho; ++i)
+    for (int j = 0; j < Wo; ++j) {
+      const int64_t p = (int64_t)i * Wo + j;
+      warp_pixel(src, Hs, Ws, C, M, mode, i, j, out + p * C, inside ? inside + p : nullptr);
+    }
+  return NPP_OK;
+}
+
+// The positions and inside bytes of a view launch (npp_mlp_fwd_view / npp_mlp_fwd32_view) on the host: view_coord of npp_common.h
+extern "C" int npp_view_coords_host(const npp_view* view, int H, int W, float* out_yx, uint8_t* inside) {
+  const char* who = "npp_view_coords_host";
+  const int rc = check_view(view, who);
+  if (rc) return rc;
+  if (H < 1 || W < 1) { set_error("%s: image size %d x %d must be >= 1", who, H, W); return NPP_ERR_ARG; }
+  if (view->n == 0) return NPP_OK;
+  if (!out_yx) { set_error("%s: null pointer", who); return NPP_ERR_ARG; }
+  for (int64_t r = 0; r < view->n; ++r) {
+    float y, x;
+    const uint8_t in = view_coord(*view, H, W, view->start + r, y, x);
+    out_yx[2 * r] = y;
+    out_yx[2 * r + 1] = x;
+    if (inside) inside[r] = in;
+  }
+  return NPP_OK;
+}

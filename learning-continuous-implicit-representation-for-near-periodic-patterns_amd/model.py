@@ -254,6 +254,33 @@ class NPPNet:
                    width=self.width)
         return out.view(Hc, Wc, 3)
 
+    def render_view(self, size, M, precision="bf16", chunk_rows=1 << 22, return_inside=False):
+        """render_grid under a projective map (view.py): pixel (i, j) of the size = (H', W') canvas is the network at
+        ((m0 i + m1 j) + m2, (m3 i + m4 j) + m5) / ((m6 i + m7 j) + m8) of the fit's frame, M the row-major 3 x 3 map, converted to
+        float32 once -> (H', W', 3) float32 on the device, and with return_inside also (H', W') uint8: 0 the pixel is not in view
+        (behind the map's horizon or at a non-finite position; it renders zero), 1 in view, 3 in view and inside the fit's image
+        rectangle.  Chunked view launches, no coordinate buffer.  The affine map [[1/sy, 0, y0], [0, 1/sx, x0], [0, 0, 1]] with
+        power-of-two scales is render_grid bit for bit.  A non-finite or singular M raises ValueError before any launch."""
+        from . import view
+        fn = _render_fn(precision)
+        Hc, Wc = (int(s) for s in size)
+        if Hc < 1 or Wc < 1:
+            raise ValueError(f"size {tuple(size)}: both sides must be >= 1")
+        if int(chunk_rows) < 1:
+            raise ValueError(f"chunk_rows {chunk_rows} must be >= 1")
+        m32 = view.check_matrix(M).astype(np.float32)
+        total = Hc * Wc
+        out = torch.empty((total, 3), dtype=torch.float32, device=self.device)
+        inside = torch.empty(total, dtype=torch.uint8, device=self.device) if return_inside else None
+        w = self._w32_pack() if precision == "fp32" else self._wf_pack()
+        launch = getattr(ops, fn + "_view")
+        for s0 in range(0, total, int(chunk_rows)):
+            n = min(int(chunk_rows), total - s0)
+            launch(ops.view_arg(s0, n, Wc, m32), self.cfg, w, self.params, out=out[s0:s0 + n],
+                   inside=None if inside is None else inside[s0:s0 + n], out_act=self.out_act, width=self.width)
+        out = out.view(Hc, Wc, 3)
+        return (out, inside.view(Hc, Wc)) if return_inside else out
+
     # ---- model file (modelfile.py) ---------------------------------------------------------
     def embedder_config(self):
         """(angles_deg (K, 2), periods (K, 2), freqs (10,), freq_offsets (5,), res (H, W)) as the embedder was built with."""

@@ -408,6 +408,92 @@ def mlp_fwd32_grid(grid, cfg, w32, params, out=None, out_act=1, width=NPP_WIDTH)
     return out
 
 
+def view_arg(start, n, canvas_width, M):
+    """npp_view: canvas pixels [start, start + n) of a canvas `canvas_width` wide under the row-major 3 x 3 map M (nine numbers,
+    stored as float32): pixel (i, j) at ((m0 i + m1 j) + m2, (m3 i + m4 j) + m5) / ((m6 i + m7 j) + m8)."""
+    from ._lib import View
+    m = np.asarray(M, dtype=np.float32).reshape(-1)
+    if m.size != 9:
+        raise ValueError(f"M: expected a 3 x 3 matrix, got {np.shape(M)}")
+    return View(int(start), int(n), int(canvas_width), (C.c_float * 9)(*[float(v) for v in m]))
+
+
+def _view_inside(inside, n):
+    if inside is not None:
+        _req(inside, torch.uint8, "inside")
+        if inside.dim() != 1 or inside.shape[0] < n:
+            raise ValueError(f"inside: expected at least ({n},), got {tuple(inside.shape)}")
+    return inside
+
+
+def mlp_fwd_view(view, cfg, wf, params, out=None, inside=None, out_act=1, width=NPP_WIDTH):
+    """Fused bf16 render of view.n canvas pixels (view: view_arg(...)) -> out[:view.n] (n, 3); inside (uint8, optional) receives
+    the bytes 0 not in view (the row is zero) / 1 in view / 3 also inside the fit's image rectangle."""
+    out = _grid_out(out, view.n, params.device)
+    check(lib(width).npp_mlp_fwd_view(C.byref(view), C.byref(cfg), width, _p(wf), _p(params), _p(out), _p(_view_inside(inside, view.n)),
+                                      int(out_act), _stream()), "npp_mlp_fwd_view", width)
+    return out
+
+
+def mlp_fwd32_view(view, cfg, w32, params, out=None, inside=None, out_act=1, width=NPP_WIDTH):
+    """Exact-fp32 render of view.n canvas pixels -> out[:view.n] (n, 3); inside as in mlp_fwd_view."""
+    out = _grid_out(out, view.n, params.device)
+    check(lib(width).npp_mlp_fwd32_view(C.byref(view), C.byref(cfg), width, _p(w32), _p(params), _p(out), _p(_view_inside(inside, view.n)),
+                                        int(out_act), _stream()), "npp_mlp_fwd32_view", width)
+    return out
+
+
+def view_coords_host(view, res):
+    """npp_view_coords_host: the fp32 positions (n, 2) [y, x] and inside bytes (n,) a view launch forms, by plain C++ on the host;
+    res = (H, W) of the fit."""
+    yx = np.zeros((view.n, 2), np.float32)
+    inside = np.zeros(view.n, np.uint8)
+    check(lib().npp_view_coords_host(C.byref(view), int(res[0]), int(res[1]), C.c_void_p(yx.ctypes.data), C.c_void_p(inside.ctypes.data)),
+          "npp_view_coords_host")
+    return yx, inside
+
+
+def _warp_args(M, size, mode):
+    m = np.asarray(M, dtype=np.float64).reshape(-1)
+    if m.size != 9:
+        raise ValueError(f"M: expected a 3 x 3 matrix, got {np.shape(M)}")
+    if mode not in ("nearest", "bilinear"):
+        raise ValueError(f"mode {mode!r}: 'nearest' or 'bilinear'")
+    Ho, Wo = (int(s) for s in size)
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"size {tuple(size)}: both sides must be >= 1")
+    return (C.c_double * 9)(*[float(v) for v in m]), Ho, Wo, int(mode == "bilinear")
+
+
+def warp_image_u8(img_u8, M, size, mode="bilinear"):
+    """(Hs, Ws) or (Hs, Ws, C <= 4) uint8 on the device -> the size = (Ho, Wo) canvas under the map M (canvas pixel -> source
+    position, float64) and its (Ho, Wo) coverage mask (255 inside the source): include/npp_hip.h npp_warp_image_u8."""
+    _req(img_u8, torch.uint8, "img_u8")
+    if img_u8.dim() not in (2, 3) or img_u8.numel() == 0:
+        raise ValueError("img_u8: expected a non-empty (H, W) or (H, W, C)")
+    m, Ho, Wo, md = _warp_args(M, size, mode)
+    Cn = 1 if img_u8.dim() == 2 else img_u8.shape[2]
+    out = torch.empty((Ho, Wo) + tuple(img_u8.shape[2:]), dtype=torch.uint8, device=img_u8.device)
+    inside = torch.empty((Ho, Wo), dtype=torch.uint8, device=img_u8.device)
+    check(lib().npp_warp_image_u8(_p(img_u8), img_u8.shape[0], img_u8.shape[1], Cn, Ho, Wo, m, md, _p(out), _p(inside), _stream()),
+          "npp_warp_image_u8")
+    return out, inside
+
+
+def warp_image_u8_host(img_u8, M, size, mode="bilinear"):
+    """warp_image_u8 on a NumPy array, by the library's host twin."""
+    img = np.ascontiguousarray(img_u8, np.uint8)
+    if img.ndim not in (2, 3) or img.size == 0:
+        raise ValueError("img_u8: expected a non-empty (H, W) or (H, W, C)")
+    m, Ho, Wo, md = _warp_args(M, size, mode)
+    Cn = 1 if img.ndim == 2 else img.shape[2]
+    out = np.empty((Ho, Wo) + img.shape[2:], np.uint8)
+    inside = np.empty((Ho, Wo), np.uint8)
+    check(lib().npp_warp_image_u8_host(C.c_void_p(img.ctypes.data), img.shape[0], img.shape[1], Cn, Ho, Wo, m, md,
+                                       C.c_void_p(out.ctypes.data), C.c_void_p(inside.ctypes.data)), "npp_warp_image_u8_host")
+    return out, inside
+
+
 def mlp_wgrad(dzT, actT, Bp, K, ksplit, gslabs, width=NPP_WIDTH):
     _req(gslabs, torch.float32, "gslabs")
     check(lib(width).npp_mlp_wgrad(_p(dzT), _p(actT), Bp, K, width, ksplit, _p(gslabs), _stream()), "npp_mlp_wgrad", width)
