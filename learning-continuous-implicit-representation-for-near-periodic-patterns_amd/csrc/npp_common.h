@@ -113,78 +113,6 @@ __device__ __forceinline__ float warp_value(const EmbedDev& e, int p, int i, flo
   }
 }
 
-// ---- coordinate intake of the render paths (include/npp_hip.h "continuous coordinates") -------------------------------
-// Coordinate modes of the forward kernels: how row r's (y, x) enters.  A template parameter: the int32 form compiles as before.
-enum CoordMode { kCoordI32 = 0, kCoordF32 = 1, kCoordGrid = 2, kCoordView = 3 };
-
-// What a view launch adds to the forward kernels' argument structs (their LAST member; the other modes never read it)
-struct ViewArgs {
-  npp_view v;
-  uint8_t* inside;        // nullable: v.n bytes
-  int32_t H, W;           // the fit's image size (the rectangle of inside byte 3)
-};
-
-// One separately rounded fp32 operation: the _rn intrinsics on the device, the plain operator on the host (every source is compiled
-// with -ffp-contract=off, and the pragma holds it without the flag)
-#ifdef __HIP_DEVICE_COMPILE__
-#define NPP_VIEW_OP(name, intr, op) __host__ __device__ __forceinline__ float name(float a, float b) { return intr(a, b); }
-#else
-#define NPP_VIEW_OP(name, intr, op) \
-  __host__ __device__ __forceinline__ float name(float a, float b) { _Pragma("clang fp contract(off)") return a op b; }
-#endif
-NPP_VIEW_OP(view_mul, __fmul_rn, *)
-NPP_VIEW_OP(view_add, __fadd_rn, +)
-NPP_VIEW_OP(view_div, __fdiv_rn, /)
-#undef NPP_VIEW_OP
-
-// Canvas pixel p (row-major) of a view (include/npp_hip.h npp_view): d = (m6 i + m7 j) + m8, y = ((m0 i + m1 j) + m2) / d,
-// x = ((m3 i + m4 j) + m5) / d; i, j < 2^24 (checked at launch).  Returns the inside byte: 0 not in view (d <= 0 or a non-finite
-// position; y = x = 0 then, so nothing non-finite enters the chain), 1 in view, 3 also inside [-0.5, H - 0.5) x [-0.5, W - 0.5).
-__host__ __device__ __forceinline__ uint8_t view_coord(const npp_view& v, int H, int W, int64_t p, float& y, float& x) {
-  const int64_t i = p / v.width;
-  const float fi = (float)i, fj = (float)(int32_t)(p - i * v.width);
-  const float d = view_add(view_add(view_mul(v.m[6], fi), view_mul(v.m[7], fj)), v.m[8]);
-  y = view_div(view_add(view_add(view_mul(v.m[0], fi), view_mul(v.m[1], fj)), v.m[2]), d);
-  x = view_div(view_add(view_add(view_mul(v.m[3], fi), view_mul(v.m[4], fj)), v.m[5]), d);
-  if (!(d > 0.0f && __builtin_isfinite(y) && __builtin_isfinite(x))) {
-    y = x = 0.0f;
-    return 0;
-  }
-  return y >= -0.5f && y < (float)H - 0.5f && x >= -0.5f && x < (float)W - 0.5f ? 3 : 1;
-}
-
-// Row r of a view launch: canvas pixel start + min(r, n - 1), as in a grid launch
-__device__ __forceinline__ uint8_t view_row(const ViewArgs& a, int64_t r, float& y, float& x) {
-  return view_coord(a.v, a.H, a.W, a.v.start + (r < a.v.n ? r : a.v.n - 1), y, x);
-}
-
-// Row r of a grid launch: canvas pixel start + min(r, n - 1) in row-major order (the surplus rows of the last 64-row tile
-// compute on the last pixel and are not stored), at y = y0 + i / sy, x = x0 + j / sx -- an IEEE quotient, then a separate add;
-// i, j < 2^24 (checked at launch), so their fp32 conversion is exact.
-__device__ __forceinline__ void grid_coord(const npp_grid& g, int64_t r, float& y, float& x) {
-  const int64_t p = g.start + (r < g.n ? r : g.n - 1);
-  const int64_t i = p / g.width;
-  const int32_t j = (int32_t)(p - i * g.width);
-  y = __fadd_rn(g.y0, __fdiv_rn((float)i, g.sy));
-  x = __fadd_rn(g.x0, __fdiv_rn((float)j, g.sx));
-}
-
-// (y, x) of row r in coordinate mode CM: int32 pixel indices, fp32 positions ((N, 2) [y, x]) or the implicit grid
-template <int CM>
-__device__ __forceinline__ void load_coord(const void* coords, const npp_grid& g, int64_t r, float& y, float& x) {
-  if (CM == kCoordGrid) {
-    grid_coord(g, r, y, x);
-  } else if (CM == kCoordF32) {
-    const float2 c = ((const float2*)coords)[r];
-    y = c.x;
-    x = c.y;
-  } else {
-    const int2 c = ((const int2*)coords)[r];
-    y = (float)c.x;
-    x = (float)c.y;
-  }
-}
-
 // Both functions of one argument from ONE reduction (bitwise the values sincos_pi2(x, false) / (x, true) return): the
 // precise embedder needs sin(f v) and cos(f v) of every (frequency, coordinate) pair.
 __device__ __forceinline__ void sincos_pi2_both(float x, float& sn, float& cs) {

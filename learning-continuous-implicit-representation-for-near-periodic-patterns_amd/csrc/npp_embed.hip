@@ -3,7 +3,7 @@
 // (models/embedder.py:140-148, :51-56; NPP_completion/train.py:93-105).
 //
 // Algorithmic bytes per pixel: 8 B coords in + 4*K*462 B out (fp32) or 2*K*462 B (bf16).
-#include "npp_common.h"
+#include "npp_coord.h"
 #include <math.h>
 
 namespace npp {
@@ -43,7 +43,23 @@ int check_embed_cfg(const npp_embed_cfg* c, const char* who) {
   return NPP_OK;
 }
 
-// Arguments of a grid launch (include/npp_hip.h "continuous coordinates"); NPP_OK also for n == 0 (the caller returns early)
+// The canvas of a grid / view launch: pixels [start, start + n) of a canvas `width` wide; NPP_OK also for n == 0 (the caller returns early)
+int check_canvas(int64_t start, int64_t n, int32_t width, const char* who) {
+  if (width < 1) { set_error("%s: canvas width %d must be >= 1", who, width); return NPP_ERR_ARG; }
+  if (start < 0 || n < 0) { set_error("%s: start=%lld / n=%lld must be >= 0", who, (long long)start, (long long)n); return NPP_ERR_ARG; }
+  constexpr int64_t kExact = 1 << 24;                        // canvas indices above this are not exact in fp32
+  if (width > kExact) { set_error("%s: canvas width %d: column indices would reach 2^24", who, width); return NPP_ERR_ARG; }
+  if (n == 0) return NPP_OK;
+  if (start > INT64_MAX - n || (start + n - 1) / width >= kExact) {
+    set_error("%s: canvas pixels [%lld, %lld + %lld) at width %d: row indices would reach 2^24", who, (long long)start,
+              (long long)start, (long long)n, width);
+    return NPP_ERR_ARG;
+  }
+  if ((n + NPP_ROW_TILE - 1) / NPP_ROW_TILE > 0x7fffffffLL) { set_error("%s: n=%lld too large for one launch", who, (long long)n); return NPP_ERR_ARG; }
+  return NPP_OK;
+}
+
+// Arguments of a grid launch (include/npp_hip.h "continuous coordinates"): a finite origin and a finite positive scale, then the canvas
 int check_grid(const npp_grid* g, const char* who) {
   if (!g) { set_error("%s: null grid", who); return NPP_ERR_ARG; }
   if (!(isfinite(g->sy) && g->sy > 0.0f && isfinite(g->sx) && g->sx > 0.0f)) {
@@ -51,37 +67,15 @@ int check_grid(const npp_grid* g, const char* who) {
     return NPP_ERR_ARG;
   }
   if (!(isfinite(g->y0) && isfinite(g->x0))) { set_error("%s: origin (%g, %g) must be finite", who, g->y0, g->x0); return NPP_ERR_ARG; }
-  if (g->width < 1) { set_error("%s: canvas width %d must be >= 1", who, g->width); return NPP_ERR_ARG; }
-  if (g->start < 0 || g->n < 0) { set_error("%s: start=%lld / n=%lld must be >= 0", who, (long long)g->start, (long long)g->n); return NPP_ERR_ARG; }
-  constexpr int64_t kExact = 1 << 24;                        // canvas indices above this are not exact in fp32
-  if (g->width > kExact) { set_error("%s: canvas width %d: column indices would reach 2^24", who, g->width); return NPP_ERR_ARG; }
-  if (g->n == 0) return NPP_OK;
-  if (g->start > INT64_MAX - g->n || (g->start + g->n - 1) / g->width >= kExact) {
-    set_error("%s: canvas pixels [%lld, %lld + %lld) at width %d: row indices would reach 2^24", who, (long long)g->start,
-              (long long)g->start, (long long)g->n, g->width);
-    return NPP_ERR_ARG;
-  }
-  if ((g->n + NPP_ROW_TILE - 1) / NPP_ROW_TILE > 0x7fffffffLL) { set_error("%s: n=%lld too large for one launch", who, (long long)g->n); return NPP_ERR_ARG; }
-  return NPP_OK;
+  return check_canvas(g->start, g->n, g->width, who);
 }
 
-// Arguments of a view launch (include/npp_hip.h npp_view): the grid launch's checks with a finite matrix in place of its origin and scale
+// Arguments of a view launch (include/npp_hip.h npp_view): a finite matrix, then the canvas
 int check_view(const npp_view* v, const char* who) {
   if (!v) { set_error("%s: null view", who); return NPP_ERR_ARG; }
   for (int k = 0; k < 9; ++k)
     if (!isfinite(v->m[k])) { set_error("%s: matrix entry m[%d] = %g is not finite", who, k, v->m[k]); return NPP_ERR_ARG; }
-  if (v->width < 1) { set_error("%s: canvas width %d must be >= 1", who, v->width); return NPP_ERR_ARG; }
-  if (v->start < 0 || v->n < 0) { set_error("%s: start=%lld / n=%lld must be >= 0", who, (long long)v->start, (long long)v->n); return NPP_ERR_ARG; }
-  constexpr int64_t kExact = 1 << 24;                        // canvas indices above this are not exact in fp32
-  if (v->width > kExact) { set_error("%s: canvas width %d: column indices would reach 2^24", who, v->width); return NPP_ERR_ARG; }
-  if (v->n == 0) return NPP_OK;
-  if (v->start > INT64_MAX - v->n || (v->start + v->n - 1) / v->width >= kExact) {
-    set_error("%s: canvas pixels [%lld, %lld + %lld) at width %d: row indices would reach 2^24", who, (long long)v->start,
-              (long long)v->start, (long long)v->n, v->width);
-    return NPP_ERR_ARG;
-  }
-  if ((v->n + NPP_ROW_TILE - 1) / NPP_ROW_TILE > 0x7fffffffLL) { set_error("%s: n=%lld too large for one launch", who, (long long)v->n); return NPP_ERR_ARG; }
-  return NPP_OK;
+  return check_canvas(v->start, v->n, v->width, who);
 }
 
 #ifndef NPP_EMB_ROWS
@@ -105,8 +99,8 @@ struct ColEnt { float f; int code; };            // code = v index | identity <<
 // wave-uniform (wave w takes jobs w, w+4, ...) so the constant tables are read through
 // scalar loads.  Phase 2: every thread produces column PAIRS (462 is even) so stores are
 // 8 B (fp32) / 4 B (bf16) and fully coalesced.
-// FCOORD: the coordinates are fp32 positions (npp_embed_fwd_coordf) instead of int32 pixel indices.
-template <bool PRECISE, bool BF16OUT, bool FCOORD = false>
+// CM: kCoordI32 (int32 pixel indices) or kCoordF32 (fp32 positions, npp_embed_fwd_coordf).
+template <bool PRECISE, bool BF16OUT, int CM = kCoordI32>
 __global__ __launch_bounds__(kEmbThreads) void embed_kernel(const void* __restrict__ coords,
                                                             int64_t N, EmbedDev e,
                                                             void* __restrict__ out) {
@@ -135,14 +129,8 @@ __global__ __launch_bounds__(kEmbThreads) void embed_kernel(const void* __restri
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int64_t r = row0 + lane;
-    float y, x;                                   // (row=y, col=x): first member is y
-    if (FCOORD) {
-      const float2 c = (r < N && lane < kEmbRows) ? ((const float2*)coords)[r] : make_float2(0.0f, 0.0f);
-      y = c.x; x = c.y;
-    } else {
-      const int2 c = (r < N && lane < kEmbRows) ? ((const int2*)coords)[r] : make_int2(0, 0);
-      y = (float)c.x; x = (float)c.y;
-    }
+    float y = 0.0f, x = 0.0f;                     // (row=y, col=x): first member is y
+    if (r < N && lane < kEmbRows) row_coord<CM>((const int32_t*)coords, CoordSrc{(const float*)coords}, r, y, x);
     for (int job = wave; job < K * 22; job += 4)
       if (lane < kEmbRows) sv[lane * kSvStride + job] = warp_value<PRECISE>(e, job / 22, job % 22, y, x);
   }
@@ -246,13 +234,13 @@ __global__ __launch_bounds__(kEmbThreads) void embed_kernel(const void* __restri
   }
 }
 
-template <bool FCOORD = false>
+template <int CM = kCoordI32>
 __global__ void warp_kernel(const void* __restrict__ coords, int64_t N, EmbedDev e,
                             float* __restrict__ out) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= N) return;
   float y, x;
-  load_coord<FCOORD ? kCoordF32 : kCoordI32>(coords, npp_grid{}, r, y, x);
+  row_coord<CM>((const int32_t*)coords, CoordSrc{(const float*)coords}, r, y, x);
   for (int p = 0; p < e.K; ++p)
     for (int i = 0; i < 22; ++i) out[r * (e.K * 22) + p * 22 + i] = warp_value<true>(e, p, i, y, x);
 }
@@ -261,7 +249,7 @@ __global__ void warp_kernel(const void* __restrict__ coords, int64_t N, EmbedDev
 
 using namespace npp;
 
-template <bool FCOORD>
+template <int CM>
 static int embed_launch(const void* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, void* d_out, int out_dtype, int precise,
                         void* stream, const char* who) {
   int rc = check_embed_cfg(cfg, who);
@@ -273,42 +261,42 @@ static int embed_launch(const void* d_coords_yx, int64_t N, const npp_embed_cfg*
   const dim3 grid((unsigned)((N + kEmbRows - 1) / kEmbRows)), block(kEmbThreads);
   hipStream_t s = (hipStream_t)stream;
   if (precise) {
-    if (out_dtype) hipLaunchKernelGGL((embed_kernel<true, true, FCOORD>), grid, block, 0, s, d_coords_yx, N, e, d_out);
-    else hipLaunchKernelGGL((embed_kernel<true, false, FCOORD>), grid, block, 0, s, d_coords_yx, N, e, d_out);
+    if (out_dtype) hipLaunchKernelGGL((embed_kernel<true, true, CM>), grid, block, 0, s, d_coords_yx, N, e, d_out);
+    else hipLaunchKernelGGL((embed_kernel<true, false, CM>), grid, block, 0, s, d_coords_yx, N, e, d_out);
   } else {
-    if (out_dtype) hipLaunchKernelGGL((embed_kernel<false, true, FCOORD>), grid, block, 0, s, d_coords_yx, N, e, d_out);
-    else hipLaunchKernelGGL((embed_kernel<false, false, FCOORD>), grid, block, 0, s, d_coords_yx, N, e, d_out);
+    if (out_dtype) hipLaunchKernelGGL((embed_kernel<false, true, CM>), grid, block, 0, s, d_coords_yx, N, e, d_out);
+    else hipLaunchKernelGGL((embed_kernel<false, false, CM>), grid, block, 0, s, d_coords_yx, N, e, d_out);
   }
   return check_launch(who);
 }
 
-template <bool FCOORD>
+template <int CM>
 static int warp_launch(const void* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, float* d_out, void* stream, const char* who) {
   int rc = check_embed_cfg(cfg, who);
   if (rc) return rc;
   if (N < 0 || (N > 0 && (!d_coords_yx || !d_out))) { set_error("%s: bad N/pointers", who); return NPP_ERR_ARG; }
   if (N == 0) return NPP_OK;
   const EmbedDev e = make_embed_dev(*cfg);
-  hipLaunchKernelGGL(warp_kernel<FCOORD>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(warp_kernel<CM>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      d_coords_yx, N, e, d_out);
   return check_launch(who);
 }
 
 extern "C" int npp_embed_fwd(const int32_t* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, void* d_out,
                              int out_dtype, int precise, void* stream) {
-  return embed_launch<false>(d_coords_yx, N, cfg, d_out, out_dtype, precise, stream, "npp_embed_fwd");
+  return embed_launch<kCoordI32>(d_coords_yx, N, cfg, d_out, out_dtype, precise, stream, "npp_embed_fwd");
 }
 
 extern "C" int npp_embed_fwd_coordf(const float* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, void* d_out,
                                     int out_dtype, int precise, void* stream) {
-  return embed_launch<true>(d_coords_yx, N, cfg, d_out, out_dtype, precise, stream, "npp_embed_fwd_coordf");
+  return embed_launch<kCoordF32>(d_coords_yx, N, cfg, d_out, out_dtype, precise, stream, "npp_embed_fwd_coordf");
 }
 
 extern "C" int npp_warp_fwd(const int32_t* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, float* d_out,
                             void* stream) {
-  return warp_launch<false>(d_coords_yx, N, cfg, d_out, stream, "npp_warp_fwd");
+  return warp_launch<kCoordI32>(d_coords_yx, N, cfg, d_out, stream, "npp_warp_fwd");
 }
 
 extern "C" int npp_warp_fwd_coordf(const float* d_coords_yx, int64_t N, const npp_embed_cfg* cfg, float* d_out, void* stream) {
-  return warp_launch<true>(d_coords_yx, N, cfg, d_out, stream, "npp_warp_fwd_coordf");
+  return warp_launch<kCoordF32>(d_coords_yx, N, cfg, d_out, stream, "npp_warp_fwd_coordf");
 }

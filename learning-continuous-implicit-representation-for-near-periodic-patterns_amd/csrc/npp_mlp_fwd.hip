@@ -26,13 +26,10 @@
 //
 // Algorithmic work: 2 * ((K+1)*462*256 + 11*256^2 + 384) FLOP per row;
 // the zero padding of 462 -> 480 slots per proposal is not counted.
-#include "npp_common.h"
+#include "npp_coord.h"
 #include <cstring>
 
 namespace npp {
-
-EmbedDev make_embed_dev(const npp_embed_cfg& c);
-int check_embed_cfg(const npp_embed_cfg* c, const char* who);
 
 // Waves per 64-row workgroup: 4 (each owns 2 of the 8 neuron tiles; <= 256 VGPRs, 2 waves per SIMD with two workgroups
 // per CU) or 8 (1 tile each; <= 128 VGPRs, 4 waves per SIMD: more independent instruction streams to cover the LDS
@@ -93,10 +90,7 @@ constexpr int kNChunks = (kKSEmb + kChunkKS - 1) / kChunkKS;   // 4 (8,8,8,6)
 constexpr int kVRows = 22 + 8;                                 // rows 22..29 repeat rows 0..7 (see gen_emb_pair)
 constexpr int kSmemV = kVRows * kRowTile * 4;                  // warped coords of one proposal
 constexpr int kSmemE = (sizeof(EmbedDev) + 15) / 16 * 16;
-// Branch-free embedding generation is driven by two small LDS tables built once per workgroup:
-//  WarpEnt[K][22]: per warped coordinate cos/sin(theta), period, 1/period, phase, or the
-//                linear form for the two normalised raw coordinates.
-struct WarpEnt { float cs, sn, per, inv_per, phase, lin; };   // lin: value = t - 1 (normalised raw coordinate)
+// the warp table that drives the branch-free embedding generation (npp_coord.h WarpEnt[K][22])
 constexpr int kSmemWarp = NPP_MAX_K * 22 * (int)sizeof(WarpEnt);                // 3520
 // the 4-wave rgb partial sums reuse region R0 after a barrier (everything else is dead by then)
 constexpr int kSmemFwd = 2 * kRegionBytes + kSmemV + 2 * kRowTile * 4 + kSmemE + kSmemWarp;
@@ -123,11 +117,7 @@ struct FwdArgs {
   Stack S;
   const EmbedDev* estack;
   int64_t wf_stride16, params_stride, act_stride;     // 16-byte units / floats / bytes per image
-  // render paths (CM != kCoordI32, inference only): fp32 positions instead of coords, or the implicit canvas grid (pred then
-  // holds g.n rows)
-  const float* coordsf;
-  npp_grid g;
-  ViewArgs view;     // CM == kCoordView (npp_mlp_fwd_view): the projective map, the inside bytes (pred then holds view.v.n rows)
+  CoordSrc src;      // render paths (CM != kCoordI32, inference only)
 };
 
 struct EmbTabs {
@@ -680,7 +670,7 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[NTW][kNB], char* out, int
 // pressure in a kernel that already spills 40 of them.
 // ACT: the output nonlinearity is read from A_.out_act (npp_mlp_fwd_act: tanh / raw); false = the sigmoid, compiled in -- a template
 // parameter for the same reason as STACK (the run-time test cost the default launch 0.9 us in a same-box A/B)
-// CM: coordinate mode (npp_common.h CoordMode) of the render paths -- fp32 positions (npp_mlp_fwd_coordf) or the implicit canvas
+// CM: coordinate mode (npp_coord.h CoordMode) of the render paths -- fp32 positions (npp_mlp_fwd_coordf) or the implicit canvas
 // grid (npp_mlp_fwd_grid) or that canvas under a projective map (npp_mlp_fwd_view); all read the nonlinearity from A_.out_act like
 // ACT.  kCoordI32 is every other launch, unchanged.
 template <int TRAIN, bool MULTI, bool EMB_IN = false, bool STACK = false, bool ACT = false, int CM = kCoordI32>
@@ -724,20 +714,7 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
     for (int i = 0; i < (int)(sizeof(EmbedDev) / 4); ++i) dst[i] = src[i];
   }
   wg_barrier();
-  for (int wi = threadIdx.x; wi < ed.K * 22; wi += kThreads) {
-    const int p = wi / 22, i = wi - p * 22, ori = i >= 11, ii = ori ? i - 11 : i;
-    WarpEnt w{0.0f, 0.0f, 1.0f, 1.0f, 0.0f, 0.0f};
-    if (ii == 0) {                                          // (x / res[1] - 0.5) * 2, (y / res[0] - 0.5) * 2
-      w.lin = 1.0f;
-      if (ori) w.cs = 2.0f * ed.inv_h; else w.sn = 2.0f * ed.inv_w;
-    } else {
-      const int o = (ii - 1) >> 1;
-      w.cs = ed.cs[p][ori]; w.sn = ed.sn[p][ori];
-      w.per = ed.per[p][ori][o]; w.inv_per = 1.0f / w.per;
-      w.phase = ((ii - 1) & 1) ? 0.25f : 0.0f;
-    }
-    tWarp[wi] = w;
-  }
+  build_warp_table(ed, tWarp, kThreads);
   const EmbTabs e{ed.freq_rev, tWarp, A_.emb, A_.emb_ld};
   Lane L;
   L.tid = threadIdx.x;
@@ -752,17 +729,10 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
   const int nt0 = kNTW * L.wave;         // this wave's neuron tiles in 256-wide layers
 
   if (!EMB_IN && L.tid < kRowTile) {
-    if (CM == kCoordI32) {
-      const int2 c = ((const int2*)s_coords)[row0 + L.tid];
-      sY[L.tid] = (float)c.x;              // (row=y, col=x)
-      sX[L.tid] = (float)c.y;
-    } else {
-      float y, x;
-      if (CM == kCoordView) view_row(A_.view, row0 + L.tid, y, x);       // (0, 0) for a pixel not in view
-      else load_coord<CM>(A_.coordsf, A_.g, row0 + L.tid, y, x);
-      sY[L.tid] = y;
-      sX[L.tid] = x;
-    }
+    float y, x;
+    row_coord<CM>(s_coords, A_.src, row0 + L.tid, y, x);       // (0, 0) for a pixel not in view
+    sY[L.tid] = y;
+    sX[L.tid] = x;
   }
   wg_barrier();
 
@@ -976,15 +946,7 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
       for (int w = 0; w < kNT / 2; ++w) z += sRGB[(w * kRowTile + row) * 3 + c];   // P's neuron tiles, in order
       float o = 1.0f / (1.0f + __expf(-z));                         // helpers.py:56 sigmoid
       if ((EMB_IN || ACT || CM != kCoordI32) && A_.out_act != 1) o = A_.out_act == 2 ? tanhf(z) : z;   // helpers.py:57-58 tanh (--normalize_type 2) / raw network output
-      if (CM == kCoordView) {
-        // the inside byte again from the map (nothing is carried through the chain); a pixel not in view stores zeros
-        if (row0 + row < A_.view.v.n) {
-          float y, x;
-          const uint8_t in = view_row(A_.view, row0 + row, y, x);
-          s_pred[(row0 + row) * 3 + c] = in ? o : 0.0f;
-          if (c == 0 && A_.view.inside) A_.view.inside[row0 + row] = in;
-        }
-      } else if (CM != kCoordGrid || row0 + row < A_.g.n) s_pred[(row0 + row) * 3 + c] = o;   // a grid launch stores exactly g.n rows
+      store_rgb<CM>(A_.src, s_pred, row0 + row, c, o);
     }
   }
 #pragma unroll
@@ -1032,48 +994,43 @@ static int fwd_launch(FwdForm f, const FwdArgs& A, const EmbedDev& e, const NetD
   return f == kFwdCoordF ? L.go<0, kFwdCoordF>() : f == kFwdGrid ? L.go<0, kFwdGrid>() : L.go<0, kFwdView>();
 }
 
-static int fwd_check(int64_t Bp, int width, const void* in, const void* d_wf, const float* d_params, const float* d_pred,
-                     const char* who) {
-  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
-  if (Bp <= 0 || Bp % kRowTile) { set_error("%s: Bp=%lld must be a positive multiple of %d", who, (long long)Bp, kRowTile); return NPP_ERR_ARG; }
-  if (!in || !d_wf || !d_params || !d_pred) { set_error("%s: null pointer", who); return NPP_ERR_ARG; }
-  if (Bp / kRowTile > 0x7fffffffLL) { set_error("%s: Bp too large", who); return NPP_ERR_ARG; }
-  return NPP_OK;
+// The body of the entry points that launch on a coordinate tensor (d_actT: the training stash, null for a render)
+static int fwd_rows(const char* who, FwdForm f, const void* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width,
+                    const void* d_wf, const float* d_params, float* d_pred, void* d_actT, int out_act, void* stream) {
+  const int rc = fwd_entry_check(who, cfg, width, Bp, false, d_coords_yx, d_wf, d_params, d_pred, out_act);
+  if (rc) return rc;
+  FwdArgs A{};
+  A.Bp = Bp; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_pred; A.actF = (char*)d_actT; A.out_act = out_act;
+  if (f == kFwdCoordF) A.src.coordsf = (const float*)d_coords_yx; else A.coords = (const int32_t*)d_coords_yx;
+  return fwd_launch(f, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, who);
 }
 
-extern "C" int npp_mlp_fwd(const int32_t* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width,
-                           const void* d_wf, const float* d_params, float* d_pred, void* d_actT, void* stream) {
-  int rc = check_embed_cfg(cfg, "npp_mlp_fwd");
-  if (rc) return rc;
-  if ((rc = fwd_check(Bp, width, d_coords_yx, d_wf, d_params, d_pred, "npp_mlp_fwd"))) return rc;
+// ... and of those that launch on the n pixels of a canvas, behind their checks
+static int fwd_canvas(const char* who, FwdForm f, int64_t n, const CoordSrc& src, const npp_embed_cfg* cfg, const void* d_wf,
+                      const float* d_params, float* d_out, int out_act, void* stream) {
   FwdArgs A{};
-  A.coords = d_coords_yx; A.Bp = Bp; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_pred;
-  A.actF = (char*)d_actT; A.out_act = 1;
-  return fwd_launch(kFwdPlain, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, "npp_mlp_fwd");
+  A.Bp = (n + kRowTile - 1) / kRowTile * kRowTile; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_out; A.out_act = out_act;
+  A.src = src;
+  return fwd_launch(f, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, who);
 }
 
 // npp_mlp_fwd with the output nonlinearity of render() as an argument (models/helpers.py:55-60): 1 sigmoid (--normalize_type 1, what
 // npp_mlp_fwd applies), 2 tanh (--normalize_type 2: images in [-1, 1], loaders.py:56), 0 the raw network output
 extern "C" int npp_mlp_fwd_act(const int32_t* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_wf,
                                const float* d_params, float* d_pred, void* d_actT, int out_act, void* stream) {
-  int rc = check_embed_cfg(cfg, "npp_mlp_fwd_act");
-  if (rc) return rc;
-  if ((rc = fwd_check(Bp, width, d_coords_yx, d_wf, d_params, d_pred, "npp_mlp_fwd_act"))) return rc;
-  if (out_act < 0 || out_act > 2) { set_error("npp_mlp_fwd_act: out_act=%d", out_act); return NPP_ERR_ARG; }
-  FwdArgs A{};
-  A.coords = d_coords_yx; A.Bp = Bp; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_pred;
-  A.actF = (char*)d_actT; A.out_act = out_act;
-  return fwd_launch(kFwdPlain, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, "npp_mlp_fwd_act");
+  return fwd_rows("npp_mlp_fwd_act", kFwdPlain, d_coords_yx, Bp, cfg, width, d_wf, d_params, d_pred, d_actT, out_act, stream);
+}
+
+extern "C" int npp_mlp_fwd(const int32_t* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width,
+                           const void* d_wf, const float* d_params, float* d_pred, void* d_actT, void* stream) {
+  return fwd_rows("npp_mlp_fwd", kFwdPlain, d_coords_yx, Bp, cfg, width, d_wf, d_params, d_pred, d_actT, 1, stream);
 }
 
 extern "C" int npp_mlp_fwd_emb(const float* d_emb, int64_t ld, int64_t Bp, int K, int width, const void* d_wf,
                                const float* d_params, float* d_out, void* d_actT, int out_act, void* stream) {
-  int rc = fwd_check(Bp, width, d_emb, d_wf, d_params, d_out, "npp_mlp_fwd_emb");
+  int rc = fwd_args_check("npp_mlp_fwd_emb", width, Bp, false, d_emb, d_wf, d_params, d_out, out_act);
   if (rc) return rc;
-  if (K < 1 || K > NPP_MAX_K || ld < (int64_t)K * kE || out_act < 0 || out_act > 2) {
-    set_error("npp_mlp_fwd_emb: bad K=%d / ld=%lld / out_act=%d", K, (long long)ld, out_act);
-    return NPP_ERR_ARG;
-  }
+  if (K < 1 || K > NPP_MAX_K || ld < (int64_t)K * kE) { set_error("npp_mlp_fwd_emb: bad K=%d / ld=%lld", K, (long long)ld); return NPP_ERR_ARG; }
   FwdArgs A{};
   A.Bp = Bp; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_out; A.actF = (char*)d_actT;
   A.emb = d_emb; A.emb_ld = ld; A.out_act = out_act;
@@ -1082,57 +1039,30 @@ extern "C" int npp_mlp_fwd_emb(const float* d_emb, int64_t ld, int64_t Bp, int K
   return fwd_launch(kFwdEmbIn, A, e, make_desc(K), stream, "npp_mlp_fwd_emb");
 }
 
-// ---- render paths: fp32 positions / the implicit canvas grid (include/npp_hip.h "continuous coordinates") -----------------------
-namespace npp {
-int check_grid(const npp_grid* g, const char* who);
-int check_view(const npp_view* v, const char* who);
-}
-
+// ---- render paths: fp32 positions / the implicit canvas grid / a view of it (include/npp_hip.h "continuous coordinates") ---------
 extern "C" int npp_mlp_fwd_coordf(const float* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_wf,
                                   const float* d_params, float* d_pred, int out_act, void* stream) {
-  const char* who = "npp_mlp_fwd_coordf";
-  int rc = check_embed_cfg(cfg, who);
-  if (rc) return rc;
-  if ((rc = fwd_check(Bp, width, d_coords_yx, d_wf, d_params, d_pred, who))) return rc;
-  if (out_act < 0 || out_act > 2) { set_error("%s: out_act=%d", who, out_act); return NPP_ERR_ARG; }
-  FwdArgs A{};
-  A.Bp = Bp; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_pred; A.out_act = out_act;
-  A.coordsf = d_coords_yx;
-  return fwd_launch(kFwdCoordF, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, who);
+  return fwd_rows("npp_mlp_fwd_coordf", kFwdCoordF, d_coords_yx, Bp, cfg, width, d_wf, d_params, d_pred, nullptr, out_act, stream);
 }
 
 extern "C" int npp_mlp_fwd_grid(const npp_grid* grid, const npp_embed_cfg* cfg, int width, const void* d_wf, const float* d_params,
                                 float* d_out, int out_act, void* stream) {
   const char* who = "npp_mlp_fwd_grid";
   int rc = check_grid(grid, who);
-  if (rc) return rc;
-  if ((rc = check_embed_cfg(cfg, who))) return rc;
-  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
-  if (grid->n == 0) return NPP_OK;
-  if (!d_wf || !d_params || !d_out) { set_error("%s: null pointer", who); return NPP_ERR_ARG; }
-  if (out_act < 0 || out_act > 2) { set_error("%s: out_act=%d", who, out_act); return NPP_ERR_ARG; }
-  const int64_t n_wg = (grid->n + kRowTile - 1) / kRowTile;
-  FwdArgs A{};
-  A.Bp = n_wg * kRowTile; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_out; A.out_act = out_act;
-  A.g = *grid;
-  return fwd_launch(kFwdGrid, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, who);
+  if (rc || (rc = fwd_entry_check(who, cfg, width, grid->n, true, nullptr, d_wf, d_params, d_out, out_act)) || grid->n == 0) return rc;
+  CoordSrc src{};
+  src.g = *grid;
+  return fwd_canvas(who, kFwdGrid, grid->n, src, cfg, d_wf, d_params, d_out, out_act, stream);
 }
 
 extern "C" int npp_mlp_fwd_view(const npp_view* view, const npp_embed_cfg* cfg, int width, const void* d_wf, const float* d_params,
                                 float* d_out, uint8_t* d_inside, int out_act, void* stream) {
   const char* who = "npp_mlp_fwd_view";
   int rc = check_view(view, who);
-  if (rc) return rc;
-  if ((rc = check_embed_cfg(cfg, who))) return rc;
-  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
-  if (view->n == 0) return NPP_OK;
-  if (!d_wf || !d_params || !d_out) { set_error("%s: null pointer", who); return NPP_ERR_ARG; }
-  if (out_act < 0 || out_act > 2) { set_error("%s: out_act=%d", who, out_act); return NPP_ERR_ARG; }
-  const int64_t n_wg = (view->n + kRowTile - 1) / kRowTile;
-  FwdArgs A{};
-  A.Bp = n_wg * kRowTile; A.wf = (const bf16x8*)d_wf; A.params = d_params; A.pred = d_out; A.out_act = out_act;
-  A.view = ViewArgs{*view, d_inside, cfg->H, cfg->W};
-  return fwd_launch(kFwdView, A, make_embed_dev(*cfg), make_desc(cfg->K), stream, who);
+  if (rc || (rc = fwd_entry_check(who, cfg, width, view->n, true, nullptr, d_wf, d_params, d_out, out_act)) || view->n == 0) return rc;
+  CoordSrc src{};
+  src.view.v = *view; src.view.inside = d_inside; src.view.H = cfg->H; src.view.W = cfg->W;
+  return fwd_canvas(who, kFwdView, view->n, src, cfg, d_wf, d_params, d_out, out_act, stream);
 }
 
 // ---- stacked form: M images per launch (npp_common.h "stacked launches") ----------------------------------------------------
@@ -1150,7 +1080,7 @@ extern "C" int npp_embed_dev_build(const npp_embed_cfg* cfg, void* host_out) {
 extern "C" int npp_mlp_fwd_stack(const int32_t* d_coords_yx, int64_t Bp, const void* d_embed_dev, int M, int K, int width,
                                  const void* d_wf, int64_t wf_stride_bytes, const float* d_params, int64_t params_stride,
                                  float* d_pred, void* d_actT, int64_t act_stride_bytes, const void* d_iter, void* stream) {
-  int rc = fwd_check(Bp, width, d_coords_yx, d_wf, d_params, d_pred, "npp_mlp_fwd_stack");
+  int rc = fwd_args_check("npp_mlp_fwd_stack", width, Bp, false, d_coords_yx, d_wf, d_params, d_pred, 1);
   if (rc) return rc;
   if (M < 1 || M > NPP_MAX_STACK || K < 1 || K > NPP_MAX_K || !d_embed_dev || wf_stride_bytes % 16 || act_stride_bytes % 16 ||
       wf_stride_bytes < 16 * make_desc(K).wf_total16 || params_stride < make_desc(K).total_params) {

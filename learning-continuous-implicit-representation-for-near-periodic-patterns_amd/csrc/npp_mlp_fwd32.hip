@@ -20,19 +20,14 @@
 //
 // Algorithmic work: 2 * ((K+1)*462*256 + 11*256^2 + 384) FLOP per row.
 #include "npp_chain32.h"
+#include "npp_coord.h"
 
 namespace npp {
 
-EmbedDev make_embed_dev(const npp_embed_cfg& c);
-int check_embed_cfg(const npp_embed_cfg* c, const char* who);
-int check_grid(const npp_grid* g, const char* who);
-int check_view(const npp_view* v, const char* who);
-
 constexpr int kT32 = 32 * kNT;                     // threads: 2 neuron tiles per wave (4 waves at W = 256, 8 at W = 512)
 constexpr int kRegion32 = kW * kRowTile * 4;       // 64 KiB: 256 features x 64 rows fp32
-struct WarpEnt32 { float cs, sn, per, inv_per, phase, lin; };
 constexpr int kSmem32 = kRegion32 + 22 * kRowTile * 4 + 2 * kRowTile * 4 + ((sizeof(EmbedDev) + 15) / 16) * 16 +
-                        NPP_MAX_K * 22 * (int)sizeof(WarpEnt32);
+                        NPP_MAX_K * 22 * (int)sizeof(WarpEnt);
 
 struct Fwd32Args {
   const int32_t* coords;
@@ -41,11 +36,8 @@ struct Fwd32Args {
   const float* params;
   float* pred;
   int32_t out_act;
-  // render paths (CM != kCoordI32): fp32 positions instead of coords, or the implicit canvas grid (pred then holds g.n rows)
-  const float* coordsf;
-  npp_grid g;
   float* stash;              // STASH: (stash32_rows(K), Bp) fp32, feature-major
-  ViewArgs view;             // CM == kCoordView (npp_mlp_fwd32_view): the projective map, the inside bytes (pred then holds view.v.n rows)
+  CoordSrc src;              // render paths (CM != kCoordI32, inference only)
 };
 
 // B operands generated from the 22 warped coordinates of one proposal (sV[i][row], fp32): k-step q < 220 contracts
@@ -84,7 +76,7 @@ __device__ __forceinline__ void stash32_tiles(const f32x16 (&acc)[NTW][kNB], flo
     }
 }
 
-// CM: coordinate mode (npp_common.h CoordMode) -- int32 pixel indices, fp32 positions, the implicit canvas grid or that canvas
+// CM: coordinate mode (npp_coord.h CoordMode) -- int32 pixel indices, fp32 positions, the implicit canvas grid or that canvas
 // under a projective map
 // STASH: also write the training stash (A_.stash)
 template <bool MULTI, int CM = kCoordI32, bool STASH = false>
@@ -95,7 +87,7 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
   float* sY = sV + 22 * kRowTile;
   float* sX = sY + kRowTile;
   EmbedDev& ed = *(EmbedDev*)(sX + kRowTile);
-  WarpEnt32* tWarp = (WarpEnt32*)((char*)&ed + ((sizeof(EmbedDev) + 15) / 16) * 16);
+  WarpEnt* tWarp = (WarpEnt*)((char*)&ed + ((sizeof(EmbedDev) + 15) / 16) * 16);
   if (threadIdx.x == 0) {
     const uint32_t* src = (const uint32_t*)&e_arg;
     uint32_t* dst = (uint32_t*)&ed;
@@ -103,9 +95,11 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
     for (int i = 0; i < (int)(sizeof(EmbedDev) / 4); ++i) dst[i] = src[i];
   }
   wg_barrier();
+  // build_warp_table(ed, tWarp, kT32), written out: as a call the compiler forms the same table with seven more instructions, and the
+  // grid launches of this kernel then measured 0.4 - 0.5 % slower than before at W = 256, twice (profiles/render_intake_refactor.txt)
   for (int wi = threadIdx.x; wi < ed.K * 22; wi += kT32) {
     const int p = wi / 22, i = wi - p * 22, ori = i >= 11, ii = ori ? i - 11 : i;
-    WarpEnt32 w{0.0f, 0.0f, 1.0f, 1.0f, 0.0f, 0.0f};
+    WarpEnt w{0.0f, 0.0f, 1.0f, 1.0f, 0.0f, 0.0f};
     if (ii == 0) {
       w.lin = 1.0f;
       if (ori) w.cs = 2.0f * ed.inv_h; else w.sn = 2.0f * ed.inv_w;
@@ -123,17 +117,10 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
   const float* P = A_.params;
   const int nt0 = 2 * wave;
   if (tid < kRowTile) {
-    if (CM == kCoordI32) {
-      const int2 c = ((const int2*)A_.coords)[row0 + tid];
-      sY[tid] = (float)c.x;
-      sX[tid] = (float)c.y;
-    } else {
-      float y, x;
-      if (CM == kCoordView) view_row(A_.view, row0 + tid, y, x);         // (0, 0) for a pixel not in view
-      else load_coord<CM>(A_.coordsf, A_.g, row0 + tid, y, x);
-      sY[tid] = y;
-      sX[tid] = x;
-    }
+    float y, x;
+    row_coord<CM>(A_.coords, A_.src, row0 + tid, y, x);         // (0, 0) for a pixel not in view
+    sY[tid] = y;
+    sX[tid] = x;
   }
   wg_barrier();
 
@@ -141,7 +128,7 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
   auto gen_warp = [&](int p) {
     const float y = sY[lane], x = sX[lane];
     for (int i = wave; i < 22; i += kT32 / 64) {
-      const WarpEnt32 w = tWarp[p * 22 + i];
+      const WarpEnt w = tWarp[p * 22 + i];
       const float t = __fadd_rn(__fmul_rn(y, w.cs), __fmul_rn(x, w.sn));
       const float qf = floorf(t * w.inv_per);
       float r = fmaf(-qf, w.per, t);
@@ -284,15 +271,7 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
 #pragma unroll
     for (int w = 0; w < kNT / 2; ++w) z += sRGB[(w * kRowTile + row) * 3 + c];
     const float o = A_.out_act == 1 ? 1.0f / (1.0f + expf(-z)) : (A_.out_act == 2 ? tanhf(z) : z);
-    if (CM == kCoordView) {
-      // the inside byte again from the map (nothing is carried through the chain); a pixel not in view stores zeros
-      if (row0 + row < A_.view.v.n) {
-        float y, x;
-        const uint8_t in = view_row(A_.view, row0 + row, y, x);
-        A_.pred[(row0 + row) * 3 + c] = in ? o : 0.0f;
-        if (c == 0 && A_.view.inside) A_.view.inside[row0 + row] = in;
-      }
-    } else if (CM != kCoordGrid || row0 + row < A_.g.n) A_.pred[(row0 + row) * 3 + c] = o;
+    store_rgb<CM>(A_.src, A_.pred, row0 + row, c, o);
   }
 }
 
@@ -335,77 +314,71 @@ extern "C" int npp_pack_weights32(const float* d_params, void* d_w32, int K, int
 }
 
 template <int CM, bool STASH = false>
-static int fwd32_launch(const Fwd32Args& A, const npp_embed_cfg* cfg, int64_t n_wg, void* stream, const char* who) {
+static int fwd32_launch(const Fwd32Args& A, const npp_embed_cfg* cfg, void* stream, const char* who) {
   const EmbedDev e = make_embed_dev(*cfg);
   const NetDesc d = make_desc(cfg->K);
   const Desc32 d32 = make_desc32(cfg->K);
-  const dim3 grid((unsigned)n_wg), block(kT32);
+  const dim3 grid((unsigned)(A.Bp / kRowTile)), block(kT32);
   const hipStream_t s = (hipStream_t)stream;
   return cfg->K > 1 ? launch_lds<mlp_fwd32_kernel<true, CM, STASH>>(who, grid, block, kSmem32, kSmem32, s, A, e, d, d32)
                     : launch_lds<mlp_fwd32_kernel<false, CM, STASH>>(who, grid, block, kSmem32, kSmem32, s, A, e, d, d32);
 }
 
+// The arguments every launch of the chain shares; n rows are computed in whole 64-row tiles
+static Fwd32Args fwd32_args(int64_t n, const void* d_w32, const float* d_params, float* d_out, int out_act) {
+  Fwd32Args A{};
+  A.Bp = (n + kRowTile - 1) / kRowTile * kRowTile; A.w32 = (const float*)d_w32; A.params = d_params; A.pred = d_out; A.out_act = out_act;
+  return A;
+}
+
 extern "C" int npp_mlp_fwd32(const int32_t* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_w32,
                              const float* d_params, float* d_out, int out_act, void* stream) {
-  int rc = check_embed_cfg(cfg, "npp_mlp_fwd32");
+  const char* who = "npp_mlp_fwd32";
+  const int rc = fwd_entry_check(who, cfg, width, Bp, false, d_coords_yx, d_w32, d_params, d_out, out_act);
   if (rc) return rc;
-  if (width != NPP_WIDTH) { set_error("npp_mlp_fwd32: width %d unsupported (build is %d)", width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
-  if (Bp <= 0 || Bp % kRowTile || Bp / kRowTile > 0x7fffffffLL) { set_error("npp_mlp_fwd32: Bp=%lld must be a positive multiple of %d", (long long)Bp, kRowTile); return NPP_ERR_ARG; }
-  if (!d_coords_yx || !d_w32 || !d_params || !d_out || out_act < 0 || out_act > 2) { set_error("npp_mlp_fwd32: bad argument"); return NPP_ERR_ARG; }
-  Fwd32Args A{d_coords_yx, Bp, (const float*)d_w32, d_params, d_out, out_act};
-  return fwd32_launch<kCoordI32>(A, cfg, Bp / kRowTile, stream, "npp_mlp_fwd32");
+  Fwd32Args A = fwd32_args(Bp, d_w32, d_params, d_out, out_act);
+  A.coords = d_coords_yx;
+  return fwd32_launch<kCoordI32>(A, cfg, stream, who);
 }
 
 extern "C" int npp_mlp_fwd32_coordf(const float* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_w32,
                                     const float* d_params, float* d_out, int out_act, void* stream) {
   const char* who = "npp_mlp_fwd32_coordf";
-  int rc = check_embed_cfg(cfg, who);
+  const int rc = fwd_entry_check(who, cfg, width, Bp, false, d_coords_yx, d_w32, d_params, d_out, out_act);
   if (rc) return rc;
-  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
-  if (Bp <= 0 || Bp % kRowTile || Bp / kRowTile > 0x7fffffffLL) { set_error("%s: Bp=%lld must be a positive multiple of %d", who, (long long)Bp, kRowTile); return NPP_ERR_ARG; }
-  if (!d_coords_yx || !d_w32 || !d_params || !d_out || out_act < 0 || out_act > 2) { set_error("%s: bad argument", who); return NPP_ERR_ARG; }
-  Fwd32Args A{nullptr, Bp, (const float*)d_w32, d_params, d_out, out_act, d_coords_yx, npp_grid{}};
-  return fwd32_launch<kCoordF32>(A, cfg, Bp / kRowTile, stream, who);
+  Fwd32Args A = fwd32_args(Bp, d_w32, d_params, d_out, out_act);
+  A.src.coordsf = d_coords_yx;
+  return fwd32_launch<kCoordF32>(A, cfg, stream, who);
 }
 
 extern "C" int npp_mlp_fwd32_grid(const npp_grid* grid, const npp_embed_cfg* cfg, int width, const void* d_w32, const float* d_params,
                                   float* d_out, int out_act, void* stream) {
   const char* who = "npp_mlp_fwd32_grid";
   int rc = check_grid(grid, who);
-  if (rc) return rc;
-  if ((rc = check_embed_cfg(cfg, who))) return rc;
-  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
-  if (grid->n == 0) return NPP_OK;
-  if (!d_w32 || !d_params || !d_out || out_act < 0 || out_act > 2) { set_error("%s: bad argument", who); return NPP_ERR_ARG; }
-  const int64_t n_wg = (grid->n + kRowTile - 1) / kRowTile;
-  Fwd32Args A{nullptr, n_wg * kRowTile, (const float*)d_w32, d_params, d_out, out_act, nullptr, *grid};
-  return fwd32_launch<kCoordGrid>(A, cfg, n_wg, stream, who);
+  if (rc || (rc = fwd_entry_check(who, cfg, width, grid->n, true, nullptr, d_w32, d_params, d_out, out_act)) || grid->n == 0) return rc;
+  Fwd32Args A = fwd32_args(grid->n, d_w32, d_params, d_out, out_act);
+  A.src.g = *grid;
+  return fwd32_launch<kCoordGrid>(A, cfg, stream, who);
 }
 
 extern "C" int npp_mlp_fwd32_view(const npp_view* view, const npp_embed_cfg* cfg, int width, const void* d_w32, const float* d_params,
                                   float* d_out, uint8_t* d_inside, int out_act, void* stream) {
   const char* who = "npp_mlp_fwd32_view";
   int rc = check_view(view, who);
-  if (rc) return rc;
-  if ((rc = check_embed_cfg(cfg, who))) return rc;
-  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
-  if (view->n == 0) return NPP_OK;
-  if (!d_w32 || !d_params || !d_out || out_act < 0 || out_act > 2) { set_error("%s: bad argument", who); return NPP_ERR_ARG; }
-  const int64_t n_wg = (view->n + kRowTile - 1) / kRowTile;
-  Fwd32Args A{nullptr, n_wg * kRowTile, (const float*)d_w32, d_params, d_out, out_act, nullptr, npp_grid{}, nullptr,
-              ViewArgs{*view, d_inside, cfg->H, cfg->W}};
-  return fwd32_launch<kCoordView>(A, cfg, n_wg, stream, who);
+  if (rc || (rc = fwd_entry_check(who, cfg, width, view->n, true, nullptr, d_w32, d_params, d_out, out_act)) || view->n == 0) return rc;
+  Fwd32Args A = fwd32_args(view->n, d_w32, d_params, d_out, out_act);
+  A.src.view.v = *view; A.src.view.inside = d_inside; A.src.view.H = cfg->H; A.src.view.W = cfg->W;
+  return fwd32_launch<kCoordView>(A, cfg, stream, who);
 }
 
 // The forward of the exact-fp32 fit: npp_mlp_fwd32 plus the stash (d_stash: sizes[1] of npp_train_workspace32)
 extern "C" int npp_mlp_fwd32_train(const int32_t* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_w32,
                                    const float* d_params, float* d_pred, void* d_stash, int out_act, void* stream) {
   const char* who = "npp_mlp_fwd32_train";
-  int rc = check_embed_cfg(cfg, who);
+  const int rc = fwd_entry_check(who, cfg, width, Bp, false, d_coords_yx, d_w32, d_params, d_pred, out_act);
   if (rc) return rc;
-  if (width != NPP_WIDTH) { set_error("%s: width %d unsupported (build is %d)", who, width, NPP_WIDTH); return NPP_ERR_UNSUPPORTED; }
-  if (Bp <= 0 || Bp % kRowTile || Bp / kRowTile > 0x7fffffffLL) { set_error("%s: Bp=%lld must be a positive multiple of %d", who, (long long)Bp, kRowTile); return NPP_ERR_ARG; }
-  if (!d_coords_yx || !d_w32 || !d_params || !d_pred || !d_stash || out_act < 0 || out_act > 2) { set_error("%s: bad argument", who); return NPP_ERR_ARG; }
-  Fwd32Args A{d_coords_yx, Bp, (const float*)d_w32, d_params, d_pred, out_act, nullptr, npp_grid{}, (float*)d_stash};
-  return fwd32_launch<kCoordI32, true>(A, cfg, Bp / kRowTile, stream, who);
+  if (!d_stash) { set_error("%s: null stash", who); return NPP_ERR_ARG; }
+  Fwd32Args A = fwd32_args(Bp, d_w32, d_params, d_pred, out_act);
+  A.coords = d_coords_yx; A.stash = (float*)d_stash;
+  return fwd32_launch<kCoordI32, true>(A, cfg, stream, who);
 }

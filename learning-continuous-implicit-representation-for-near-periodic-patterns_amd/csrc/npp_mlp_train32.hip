@@ -16,11 +16,9 @@
 // of that part of the slab -- zeros included, so a slab without rows holds zeros.  No float atomics anywhere: two runs give the same
 // bits, and npp_adam_step_net / npp_grad_reduce add the slabs in slab order.
 #include "npp_chain32.h"
+#include "npp_coord.h"
 
 namespace npp {
-
-EmbedDev make_embed_dev(const npp_embed_cfg& c);
-int check_embed_cfg(const npp_embed_cfg* c, const char* who);
 
 constexpr int kTB32 = 32 * kNT;                    // threads of the backward chain: 2 feature tiles per wave
 constexpr int kRegionB32 = kW * kRowTile * 4;

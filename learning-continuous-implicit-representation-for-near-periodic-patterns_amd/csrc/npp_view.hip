@@ -3,7 +3,7 @@
 // include/npp_hip.h writes down, every product and sum rounded separately: one function body serves the kernel (spelt __d*_rn) and
 // the host twin (plain operators; the file is built with -ffp-contract=off and the pragma holds it without the flag), so NumPy, the
 // host and the device agree bit for bit.  One thread per canvas pixel, all channels; no atomics, no state between calls.
-#include "npp_common.h"
+#include "npp_coord.h"
 
 namespace npp {
 
@@ -77,8 +77,6 @@ static int warp_check(const char* who, const void* src, int Hs, int Ws, int C, i
   return NPP_OK;
 }
 
-int check_view(const npp_view* v, const char* who);
-
 }  // namespace npp
 
 using namespace npp;
@@ -108,7 +106,7 @@ extern "C" int npp_warp_image_u8_host(const uint8_t* src, int Hs, int Ws, int C,
   return NPP_OK;
 }
 
-// The positions and inside bytes of a view launch (npp_mlp_fwd_view / npp_mlp_fwd32_view) on the host: view_coord of npp_common.h
+// The positions and inside bytes of a view launch (npp_mlp_fwd_view / npp_mlp_fwd32_view) on the host: view_coord of npp_coord.h
 extern "C" int npp_view_coords_host(const npp_view* view, int H, int W, float* out_yx, uint8_t* inside) {
   const char* who = "npp_view_coords_host";
   const int rc = check_view(view, who);

@@ -13,12 +13,6 @@ from ._lib import EmbedCfg, param_layout, NPP_E, NPP_WIDTH
 LATENT_ALPHA_INIT = 2.3841858e-07   # logit(0.5) in fp32 (robust_loss_pytorch/util.py:75-83)
 
 
-def _render_fn(precision):
-    if precision not in ("bf16", "fp32"):
-        raise ValueError(f"precision {precision!r}: 'bf16' (fused chain) or 'fp32' (exact chain)")
-    return "mlp_fwd" if precision == "bf16" else "mlp_fwd32"
-
-
 def _pair(v):
     """One number or a pair -> (float, float)."""
     a = np.asarray(v, dtype=np.float64).reshape(-1)
@@ -27,6 +21,13 @@ def _pair(v):
     if a.size != 2:
         raise ValueError(f"expected one number or a pair, got {v!r}")
     return float(a[0]), float(a[1])
+
+
+def _pixel_coords(coords):
+    """render() / render_fp32() take pixel indices; positions go through render_at()."""
+    if not (isinstance(coords, torch.Tensor) and coords.dtype == torch.int32):
+        raise TypeError(f"coords: expected an int32 tensor, got {getattr(coords, 'dtype', type(coords))}")
+    return coords
 
 
 def canvas_coords(size, origin=(0.0, 0.0), scale=(1.0, 1.0), start=0, n=None):
@@ -183,26 +184,48 @@ class NPPNet:
             ws["n_rows"] = n_rows
 
     # ---- the path ---------------------------------------------------------------------
+    def _render(self, src, precision, total=None, chunk_rows=None, inside=None, empty_ok=False):
+        """The one render path (ops.render on the pack of `precision`).  src an (n, 2) int32 / float32 tensor: padded to whole 64-row
+        tiles -> (n, 3).  src a function (start, n) -> ops.grid_arg / ops.view_arg with total canvas pixels: launches of at most
+        chunk_rows pixels -> (total, 3) (and their inside bytes into `inside`)."""
+        if precision not in ("bf16", "fp32"):
+            raise ValueError(f"precision {precision!r}: 'bf16' (fused chain) or 'fp32' (exact chain)")
+        if total is None and empty_ok and src.shape[0] == 0:
+            return torch.empty((0, 3), dtype=torch.float32, device=self.device)
+        pack = self._w32_pack() if precision == "fp32" else self._wf_pack()
+        kw = dict(precision=precision, out_act=self.out_act, width=self.width)
+        if total is None:
+            n = src.shape[0]
+            bp = ops.pad_rows(n)
+            if bp != n:
+                src = torch.cat([src, src.new_zeros((bp - n, 2))], 0)
+            return ops.render(src.contiguous(), self.cfg, pack, self.params, **kw)[:n]
+        out = torch.empty((total, 3), dtype=torch.float32, device=self.device)
+        for s0 in range(0, total, chunk_rows):
+            n = min(chunk_rows, total - s0)
+            ops.render(src(s0, n), self.cfg, pack, self.params, out=out[s0:s0 + n],
+                       inside=None if inside is None else inside[s0:s0 + n], **kw)
+        return out
+
+    @staticmethod
+    def _canvas(size, chunk_rows):
+        Hc, Wc = (int(s) for s in size)
+        if Hc < 1 or Wc < 1:
+            raise ValueError(f"size {tuple(size)}: both sides must be >= 1")
+        if int(chunk_rows) < 1:
+            raise ValueError(f"chunk_rows {chunk_rows} must be >= 1")
+        return Hc, Wc, int(chunk_rows)
+
     def render(self, coords):
         """render(None, emb[coords], args, **render_kwargs) of the reference (helpers.py:41-62)
         for arbitrary pixel coordinates; no gradient state is kept (train.py:277-309)."""
-        n = coords.shape[0]
-        bp = ops.pad_rows(n)
-        if bp != n:
-            pad = torch.zeros((bp - n, 2), dtype=torch.int32, device=coords.device)
-            coords = torch.cat([coords, pad], 0)
-        pred = ops.mlp_fwd(coords.contiguous(), self.cfg, self._wf_pack(), self.params, width=self.width, out_act=self.out_act)
-        return pred[:n]
+        return self._render(_pixel_coords(coords), "bf16")
 
     def render_fp32(self, coords):
         """The same render in EXACT fp32 (BASELINE config c4): fused chain on v_mfma_f32_32x32x2_f32 (npp_mlp_fwd32), the
         reference's own arithmetic type -- no bf16 operand rounding.  The fp32 weight pack is rebuilt when the parameters have
         changed since the last call."""
-        n = coords.shape[0]
-        bp = ops.pad_rows(n)
-        if bp != n:
-            coords = torch.cat([coords, torch.zeros((bp - n, 2), dtype=torch.int32, device=coords.device)], 0)
-        return ops.mlp_fwd32(coords.contiguous(), self.cfg, self._w32_pack(), self.params, out_act=self.out_act, width=self.width)[:n]
+        return self._render(_pixel_coords(coords), "fp32")
 
     # ---- rendering at continuous positions (include/npp_hip.h "continuous coordinates") -------------------------------
     def _w32_pack(self):
@@ -218,41 +241,19 @@ class NPPNet:
         """The network at arbitrary real positions: coords (N, 2) [row y, col x] in the fit's pixel frame (sub-pixel, negative and
         past the border alike; a tensor or an array, converted to float32) -> (N, 3) on the device.  precision: 'bf16' (the fused
         chain of render()) or 'fp32' (the exact chain of render_fp32())."""
-        fn = _render_fn(precision)
         c = torch.as_tensor(coords).to(device=self.device, dtype=torch.float32)
         if c.dim() != 2 or c.shape[1] != 2:
             raise ValueError(f"coords: expected (N, 2), got {tuple(c.shape)}")
-        n = c.shape[0]
-        if n == 0:
-            return torch.empty((0, 3), dtype=torch.float32, device=self.device)
-        bp = ops.pad_rows(n)
-        if bp != n:
-            c = torch.cat([c, c.new_zeros((bp - n, 2))], 0)
-        w = self._w32_pack() if precision == "fp32" else self._wf_pack()
-        return getattr(ops, fn + "_coordf")(c.contiguous(), self.cfg, w, self.params, out_act=self.out_act, width=self.width)[:n]
+        return self._render(c, precision, empty_ok=True)
 
     def render_grid(self, size, origin=(0.0, 0.0), scale=(1.0, 1.0), precision="bf16", chunk_rows=1 << 22):
         """A canvas of size = (H', W') pixels whose pixel (i, j) is the network at (y0 + i / sy, x0 + j / sx) of the fit's frame
         (origin = (y0, x0); scale = (sy, sx) canvas pixels per fit pixel, or one number for both) -> (H', W', 3) float32 on the
         device.  Chunked grid launches of at most chunk_rows pixels: no coordinate buffer is ever built.  Scale 1 at origin 0 is
         render() of the full int32 grid bit for bit; at an integer scale S, pixel (S i, S j) is pixel (i, j) of scale 1."""
-        fn = _render_fn(precision)
-        Hc, Wc = (int(s) for s in size)
-        if Hc < 1 or Wc < 1:
-            raise ValueError(f"size {tuple(size)}: both sides must be >= 1")
-        if int(chunk_rows) < 1:
-            raise ValueError(f"chunk_rows {chunk_rows} must be >= 1")
-        sy, sx = _pair(scale)
-        y0, x0 = _pair(origin)
-        total = Hc * Wc
-        out = torch.empty((total, 3), dtype=torch.float32, device=self.device)
-        w = self._w32_pack() if precision == "fp32" else self._wf_pack()
-        launch = getattr(ops, fn + "_grid")
-        for s0 in range(0, total, int(chunk_rows)):
-            n = min(int(chunk_rows), total - s0)
-            launch(ops.grid_arg(s0, n, Wc, (y0, x0), (sy, sx)), self.cfg, w, self.params, out=out[s0:s0 + n], out_act=self.out_act,
-                   width=self.width)
-        return out.view(Hc, Wc, 3)
+        Hc, Wc, chunk = self._canvas(size, chunk_rows)
+        o, s = _pair(origin), _pair(scale)
+        return self._render(lambda s0, n: ops.grid_arg(s0, n, Wc, o, s), precision, Hc * Wc, chunk).view(Hc, Wc, 3)
 
     def render_view(self, size, M, precision="bf16", chunk_rows=1 << 22, return_inside=False):
         """render_grid under a projective map (view.py): pixel (i, j) of the size = (H', W') canvas is the network at
@@ -262,23 +263,10 @@ class NPPNet:
         rectangle.  Chunked view launches, no coordinate buffer.  The affine map [[1/sy, 0, y0], [0, 1/sx, x0], [0, 0, 1]] with
         power-of-two scales is render_grid bit for bit.  A non-finite or singular M raises ValueError before any launch."""
         from . import view
-        fn = _render_fn(precision)
-        Hc, Wc = (int(s) for s in size)
-        if Hc < 1 or Wc < 1:
-            raise ValueError(f"size {tuple(size)}: both sides must be >= 1")
-        if int(chunk_rows) < 1:
-            raise ValueError(f"chunk_rows {chunk_rows} must be >= 1")
+        Hc, Wc, chunk = self._canvas(size, chunk_rows)
         m32 = view.check_matrix(M).astype(np.float32)
-        total = Hc * Wc
-        out = torch.empty((total, 3), dtype=torch.float32, device=self.device)
-        inside = torch.empty(total, dtype=torch.uint8, device=self.device) if return_inside else None
-        w = self._w32_pack() if precision == "fp32" else self._wf_pack()
-        launch = getattr(ops, fn + "_view")
-        for s0 in range(0, total, int(chunk_rows)):
-            n = min(int(chunk_rows), total - s0)
-            launch(ops.view_arg(s0, n, Wc, m32), self.cfg, w, self.params, out=out[s0:s0 + n],
-                   inside=None if inside is None else inside[s0:s0 + n], out_act=self.out_act, width=self.width)
-        out = out.view(Hc, Wc, 3)
+        inside = torch.empty(Hc * Wc, dtype=torch.uint8, device=self.device) if return_inside else None
+        out = self._render(lambda s0, n: ops.view_arg(s0, n, Wc, m32), precision, Hc * Wc, chunk, inside).view(Hc, Wc, 3)
         return (out, inside.view(Hc, Wc)) if return_inside else out
 
     # ---- model file (modelfile.py) ---------------------------------------------------------

@@ -136,45 +136,34 @@ def selftest(device="cuda"):
     check(lib().npp_selftest_mfma(_p(scratch), _stream()), "npp_selftest_mfma")
 
 
-def embed_fwd(coords, cfg, out_dtype=torch.float32, precise=True):
-    """coords (N,2) int32 (row, col) -> (N, K*462); replaces Embedder_periodic.embed +
-    Embedder.embed + cat (models/embedder.py:140-148, :51-56; train.py:93-105)."""
+def _coord_sym(coords, sym):
+    """The entry point of `sym` for a coordinate tensor: int32 pixel indices, or float32 positions [row y, col x] of the fit's pixel
+    frame (any real value: sub-pixel, negative, past the border) through its _coordf form."""
+    if isinstance(coords, torch.Tensor) and coords.dtype == torch.float32:
+        _req(coords, torch.float32, "coords")
+        return sym + "_coordf"
     _req(coords, torch.int32, "coords")
+    return sym
+
+
+def embed_fwd(coords, cfg, out_dtype=torch.float32, precise=True):
+    """coords (N,2) int32 (row, col) or float32 positions -> (N, K*462); replaces Embedder_periodic.embed +
+    Embedder.embed + cat (models/embedder.py:140-148, :51-56; train.py:93-105)."""
+    sym = _coord_sym(coords, "npp_embed_fwd")
     n = coords.shape[0]
     out = torch.empty((n, cfg.K * NPP_E), dtype=out_dtype, device=coords.device)
     code = {torch.float32: 0, torch.bfloat16: 1}[out_dtype]
-    check(lib().npp_embed_fwd(_p(coords), n, C.byref(cfg), _p(out), code, int(bool(precise)), _stream()),
-          "npp_embed_fwd")
+    check(getattr(lib(), sym)(_p(coords), n, C.byref(cfg), _p(out), code, int(bool(precise)), _stream()), sym)
     return out
 
 
 def warp_fwd(coords, cfg):
-    """(N,2) -> (N, K*22) fp32: the Embedder_periodic stage alone (embedder.py:140-148)."""
-    _req(coords, torch.int32, "coords")
+    """(N,2) int32 or float32 -> (N, K*22) fp32: the Embedder_periodic stage alone (embedder.py:140-148), the same precise
+    arithmetic for both."""
+    sym = _coord_sym(coords, "npp_warp_fwd")
     n = coords.shape[0]
     out = torch.empty((n, cfg.K * 22), dtype=torch.float32, device=coords.device)
-    check(lib().npp_warp_fwd(_p(coords), n, C.byref(cfg), _p(out), _stream()), "npp_warp_fwd")
-    return out
-
-
-def embed_fwd_coordf(coords, cfg, out_dtype=torch.float32, precise=True):
-    """embed_fwd on (N,2) fp32 positions [row y, col x] of the fit's pixel frame (any real value: sub-pixel, negative, past the border)."""
-    _req(coords, torch.float32, "coords")
-    n = coords.shape[0]
-    out = torch.empty((n, cfg.K * NPP_E), dtype=out_dtype, device=coords.device)
-    code = {torch.float32: 0, torch.bfloat16: 1}[out_dtype]
-    check(lib().npp_embed_fwd_coordf(_p(coords), n, C.byref(cfg), _p(out), code, int(bool(precise)), _stream()),
-          "npp_embed_fwd_coordf")
-    return out
-
-
-def warp_fwd_coordf(coords, cfg):
-    """warp_fwd on (N,2) fp32 positions: Embedder_periodic.embed of a float tensor (embedder.py:140-148), the precise arithmetic of
-    warp_fwd."""
-    _req(coords, torch.float32, "coords")
-    n = coords.shape[0]
-    out = torch.empty((n, cfg.K * 22), dtype=torch.float32, device=coords.device)
-    check(lib().npp_warp_fwd_coordf(_p(coords), n, C.byref(cfg), _p(out), _stream()), "npp_warp_fwd_coordf")
+    check(getattr(lib(), sym)(_p(coords), n, C.byref(cfg), _p(out), _stream()), sym)
     return out
 
 
@@ -305,12 +294,7 @@ def pack_weights32(params, K, w32=None, width=NPP_WIDTH):
 def mlp_fwd32(coords_yx, cfg, w32, params, out=None, out_act=1, width=NPP_WIDTH):
     """Exact-fp32 fused embedder + MLP forward (render), coords (Bp,2) int32 with Bp % 64 == 0 -> (Bp,3)."""
     _req(coords_yx, torch.int32, "coords")
-    Bp = coords_yx.shape[0]
-    if out is None:
-        out = torch.empty((Bp, 3), dtype=torch.float32, device=coords_yx.device)
-    check(lib(width).npp_mlp_fwd32(_p(coords_yx), Bp, C.byref(cfg), width, _p(w32), _p(params), _p(out), int(out_act), _stream()),
-          "npp_mlp_fwd32", width)
-    return out
+    return render(coords_yx, cfg, w32, params, "fp32", out=out, out_act=out_act, width=width)
 
 
 # ---- exact-fp32 training chain (include/npp_hip.h "exact-fp32 training of the fused MLP") ------------------------------------
@@ -355,57 +339,10 @@ def mlp_wgrad32(dz, stash, cfg, Bp, K, ksplit, gslabs, width=NPP_WIDTH):
           "npp_mlp_wgrad32", width)
 
 
-def mlp_fwd_coordf(coords, cfg, wf, params, out=None, out_act=1, width=NPP_WIDTH):
-    """Fused bf16 render on fp32 positions: coords (Bp,2) float32 [y, x], Bp % 64 == 0 -> (Bp,3)."""
-    _req(coords, torch.float32, "coords")
-    bp = coords.shape[0]
-    if out is None:
-        out = torch.empty((bp, 3), dtype=torch.float32, device=coords.device)
-    check(lib(width).npp_mlp_fwd_coordf(_p(coords), bp, C.byref(cfg), width, _p(wf), _p(params), _p(out), int(out_act), _stream()),
-          "npp_mlp_fwd_coordf", width)
-    return out
-
-
-def mlp_fwd32_coordf(coords, cfg, w32, params, out=None, out_act=1, width=NPP_WIDTH):
-    """Exact-fp32 render on fp32 positions: coords (Bp,2) float32 [y, x], Bp % 64 == 0 -> (Bp,3)."""
-    _req(coords, torch.float32, "coords")
-    bp = coords.shape[0]
-    if out is None:
-        out = torch.empty((bp, 3), dtype=torch.float32, device=coords.device)
-    check(lib(width).npp_mlp_fwd32_coordf(_p(coords), bp, C.byref(cfg), width, _p(w32), _p(params), _p(out), int(out_act), _stream()),
-          "npp_mlp_fwd32_coordf", width)
-    return out
-
-
 def grid_arg(start, n, canvas_width, origin=(0.0, 0.0), scale=(1.0, 1.0)):
     """npp_grid: canvas pixels [start, start + n) of a canvas `canvas_width` wide, pixel (i, j) at (y0 + i / sy, x0 + j / sx)."""
     from ._lib import Grid
     return Grid(int(start), int(n), int(canvas_width), float(origin[0]), float(origin[1]), float(scale[0]), float(scale[1]))
-
-
-def _grid_out(out, n, device):
-    if out is None:
-        return torch.empty((n, 3), dtype=torch.float32, device=device)
-    _req(out, torch.float32, "out")
-    if out.dim() != 2 or out.shape[1] != 3 or out.shape[0] < n:
-        raise ValueError(f"out: expected at least ({n}, 3), got {tuple(out.shape)}")
-    return out
-
-
-def mlp_fwd_grid(grid, cfg, wf, params, out=None, out_act=1, width=NPP_WIDTH):
-    """Fused bf16 render of grid.n canvas pixels (grid: grid_arg(...)) -> out[:grid.n] (n, 3); no coordinate buffer, no padding."""
-    out = _grid_out(out, grid.n, params.device)
-    check(lib(width).npp_mlp_fwd_grid(C.byref(grid), C.byref(cfg), width, _p(wf), _p(params), _p(out), int(out_act), _stream()),
-          "npp_mlp_fwd_grid", width)
-    return out
-
-
-def mlp_fwd32_grid(grid, cfg, w32, params, out=None, out_act=1, width=NPP_WIDTH):
-    """Exact-fp32 render of grid.n canvas pixels -> out[:grid.n] (n, 3)."""
-    out = _grid_out(out, grid.n, params.device)
-    check(lib(width).npp_mlp_fwd32_grid(C.byref(grid), C.byref(cfg), width, _p(w32), _p(params), _p(out), int(out_act), _stream()),
-          "npp_mlp_fwd32_grid", width)
-    return out
 
 
 def view_arg(start, n, canvas_width, M):
@@ -418,6 +355,15 @@ def view_arg(start, n, canvas_width, M):
     return View(int(start), int(n), int(canvas_width), (C.c_float * 9)(*[float(v) for v in m]))
 
 
+def _grid_out(out, n, device):
+    if out is None:
+        return torch.empty((n, 3), dtype=torch.float32, device=device)
+    _req(out, torch.float32, "out")
+    if out.dim() != 2 or out.shape[1] != 3 or out.shape[0] < n:
+        raise ValueError(f"out: expected at least ({n}, 3), got {tuple(out.shape)}")
+    return out
+
+
 def _view_inside(inside, n):
     if inside is not None:
         _req(inside, torch.uint8, "inside")
@@ -426,20 +372,41 @@ def _view_inside(inside, n):
     return inside
 
 
-def mlp_fwd_view(view, cfg, wf, params, out=None, inside=None, out_act=1, width=NPP_WIDTH):
-    """Fused bf16 render of view.n canvas pixels (view: view_arg(...)) -> out[:view.n] (n, 3); inside (uint8, optional) receives
-    the bytes 0 not in view (the row is zero) / 1 in view / 3 also inside the fit's image rectangle."""
-    out = _grid_out(out, view.n, params.device)
-    check(lib(width).npp_mlp_fwd_view(C.byref(view), C.byref(cfg), width, _p(wf), _p(params), _p(out), _p(_view_inside(inside, view.n)),
-                                      int(out_act), _stream()), "npp_mlp_fwd_view", width)
-    return out
+# The inference entry point of every (kind of coordinate source, precision), called on the library L: the one table of render()
+_RENDER = {("int32", "bf16"): lambda L, *a: L.npp_mlp_fwd_act(*a), ("int32", "fp32"): lambda L, *a: L.npp_mlp_fwd32(*a),
+           ("float32", "bf16"): lambda L, *a: L.npp_mlp_fwd_coordf(*a), ("float32", "fp32"): lambda L, *a: L.npp_mlp_fwd32_coordf(*a),
+           ("grid", "bf16"): lambda L, *a: L.npp_mlp_fwd_grid(*a), ("grid", "fp32"): lambda L, *a: L.npp_mlp_fwd32_grid(*a),
+           ("view", "bf16"): lambda L, *a: L.npp_mlp_fwd_view(*a), ("view", "fp32"): lambda L, *a: L.npp_mlp_fwd32_view(*a)}
 
 
-def mlp_fwd32_view(view, cfg, w32, params, out=None, inside=None, out_act=1, width=NPP_WIDTH):
-    """Exact-fp32 render of view.n canvas pixels -> out[:view.n] (n, 3); inside as in mlp_fwd_view."""
-    out = _grid_out(out, view.n, params.device)
-    check(lib(width).npp_mlp_fwd32_view(C.byref(view), C.byref(cfg), width, _p(w32), _p(params), _p(out), _p(_view_inside(inside, view.n)),
-                                        int(out_act), _stream()), "npp_mlp_fwd32_view", width)
+def render(src, cfg, pack, params, precision="bf16", out=None, inside=None, out_act=1, width=NPP_WIDTH):
+    """The fused embedder + MLP render (no stash) of one coordinate source -> out (rows, 3) float32.  src: an int32 (Bp, 2) tensor of
+    pixel indices or a float32 (Bp, 2) tensor of positions [y, x], Bp % 64 == 0 (out: (Bp, 3)); a grid_arg(...) or a view_arg(...):
+    src.n canvas pixels -> out[:src.n], no coordinate buffer and no padding (out: at least (n, 3)).  precision: 'bf16' (the fused
+    chain; pack = the wf pack) or 'fp32' (the exact chain; pack = the w32 pack).  inside (uint8, a view only, optional) receives
+    the bytes 0 not in view (the row is zero) / 1 in view / 3 also inside the fit's image rectangle.  out_act: 1 sigmoid, 2 tanh, 0 raw."""
+    from ._lib import Grid, View
+    if precision not in ("bf16", "fp32"):
+        raise ValueError(f"precision {precision!r}: 'bf16' (fused chain) or 'fp32' (exact chain)")
+    canvas = isinstance(src, (Grid, View))
+    if inside is not None and not isinstance(src, View):
+        raise ValueError("inside: only a view launch writes inside bytes")
+    if canvas:
+        kind = "view" if isinstance(src, View) else "grid"
+        out = _grid_out(out, src.n, params.device)
+        head = (C.byref(src), C.byref(cfg), width, _p(pack), _p(params), _p(out))
+        tail = (_p(_view_inside(inside, src.n)),) if kind == "view" else ()
+    else:
+        if not (isinstance(src, torch.Tensor) and src.dtype in (torch.int32, torch.float32)):
+            raise TypeError("src: expected an int32 or float32 (Bp, 2) tensor, a grid_arg(...) or a view_arg(...)")
+        kind = "int32" if src.dtype == torch.int32 else "float32"
+        _req(src, src.dtype, "coords")
+        bp = src.shape[0]
+        if out is None:
+            out = torch.empty((bp, 3), dtype=torch.float32, device=src.device)
+        head = (_p(src), bp, C.byref(cfg), width, _p(pack), _p(params), _p(out))
+        tail = (None,) if (kind, precision) == ("int32", "bf16") else ()       # npp_mlp_fwd_act's stash: none
+    check(_RENDER[kind, precision](lib(width), *head, *tail, int(out_act), _stream()), f"render({kind}, {precision})", width)
     return out
 
 

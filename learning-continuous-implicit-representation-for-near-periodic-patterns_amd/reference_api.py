@@ -98,7 +98,7 @@ class Embedder_periodic:
         if c.dtype != torch.int32:
             if c.is_floating_point() and not bool((c == c.round()).all()):
                 # sub-pixel / resampled positions (the module is a function of the plane): the same precise warp on fp32 positions
-                v = ops.warp_fwd_coordf(c.to(torch.float32).contiguous(), self.cfg)
+                v = ops.warp_fwd(c.to(torch.float32).contiguous(), self.cfg)
                 return v if self.include_input else torch.cat([v[:, 1:11], v[:, 12:22]], 1).contiguous()
             c = c.to(torch.int32)
         v = ops.warp_fwd(c.contiguous(), self.cfg)                         # (N, 22): [x_n, 10 x orientation 0, y_n, 10 x orientation 1]

@@ -121,6 +121,85 @@ def test_light_chain_entry_points_validate_on_the_host():
     assert L.npp_linear_bwd_weight_strided(fake, 0, 1, 0, fake, 1, 1, 0, 0, 1, 64, 4, 4, fake, 4, 0, None, 0, None) < 0
 
 
+def test_render_entry_points_validate_on_the_host():
+    """The ten fused-forward entry points and the four embed / warp ones refuse a bad argument before anything is launched (no GPU
+    needed to see it): one bad argument at a time, the return code of its class (the width: NPP_ERR_UNSUPPORTED, everything else:
+    NPP_ERR_ARG) and a message that carries the entry point's name.  One table of bad canvases is refused by the grid pair and the
+    view pair alike with a message that names the quantity, and a launch of no pixels / no rows is a no-op that looks at no pointer."""
+    from npp_amd import ops
+    from npp_amd._lib import EmbedCfg
+    ARG, UNSUPPORTED = -1, -3
+    W = npp_amd.FUSED_WIDTHS[0]
+    L = npp_amd.lib(W)
+    fake = C.c_void_p(64)                                              # never dereferenced: validation comes first
+
+    def cfg(offsets=(0.0, -1.0, 1.0, 0.5, -0.5)):
+        return EmbedCfg.make([[10.0, 100.0]], [[12.0, 14.0]], oracle.SEED0_FREQS, (32, 32), offsets)
+    good = dict(coords=fake, Bp=64, cfg=C.byref(cfg()), width=W, pack=fake, params=fake, out=fake, stash=fake, out_act=1)
+
+    def refused(name, call, code, **bad):
+        assert call(**{**good, **bad}) == code, (name, bad)
+        msg = L.npp_last_error_string()
+        assert name.encode() in msg, (name, bad, msg)
+        return msg
+
+    # (entry point, how it orders the arguments, has it an out_act argument)
+    rows = {
+        "npp_mlp_fwd": (lambda a: (a["coords"], a["Bp"], a["cfg"], a["width"], a["pack"], a["params"], a["out"], None, None), False),
+        "npp_mlp_fwd_act": (lambda a: (a["coords"], a["Bp"], a["cfg"], a["width"], a["pack"], a["params"], a["out"], None, a["out_act"], None), True),
+        "npp_mlp_fwd32_train": (lambda a: (a["coords"], a["Bp"], a["cfg"], a["width"], a["pack"], a["params"], a["out"], a["stash"], a["out_act"], None), True),
+    }
+    for name in ("npp_mlp_fwd_coordf", "npp_mlp_fwd32", "npp_mlp_fwd32_coordf"):
+        rows[name] = (lambda a: (a["coords"], a["Bp"], a["cfg"], a["width"], a["pack"], a["params"], a["out"], a["out_act"], None), True)
+    canvas = {}
+    for kind, arg in (("grid", ops.grid_arg(0, 64, 16)), ("view", ops.view_arg(0, 64, 16, np.eye(3)))):
+        for name in (f"npp_mlp_fwd_{kind}", f"npp_mlp_fwd32_{kind}"):
+            inside = (None,) if kind == "view" else ()
+            canvas[name] = (lambda a, arg=arg, inside=inside: (C.byref(a.get("src", arg)), a["cfg"], a["width"], a["pack"], a["params"], a["out"],
+                                                                *inside, a["out_act"], None), True)
+    assert len(rows) + len(canvas) == 10
+    for name, (order, has_act) in {**rows, **canvas}.items():
+        def call(_order=order, _fn=getattr(L, name), **a):
+            return _fn(*_order(a))
+        refused(name, call, UNSUPPORTED, width=W + 1)
+        if name in rows:
+            for bp in (0, 63, -64):
+                refused(name, call, ARG, Bp=bp)
+            refused(name, call, ARG, coords=None)
+        for ptr in ("pack", "params", "out"):
+            refused(name, call, ARG, **{ptr: None})
+        if has_act:
+            for act in (-1, 3):
+                assert b"out_act" in refused(name, call, ARG, out_act=act)
+        refused(name, call, ARG, cfg=None)
+        assert b"period" in refused(name, call, ARG, cfg=C.byref(cfg(offsets=(0.0, -12.0, 1.0, 0.5, -0.5))))      # 12 - 12 = 0
+    refused("npp_mlp_fwd32_train", lambda **a: L.npp_mlp_fwd32_train(*rows["npp_mlp_fwd32_train"][0](a)), ARG, stash=None)
+
+    # the stand-alone embedder and warp: row count, null pointers, configuration
+    for name, extra in (("npp_embed_fwd", (0, 1)), ("npp_embed_fwd_coordf", (0, 1)), ("npp_warp_fwd", ()), ("npp_warp_fwd_coordf", ())):
+        def call(_fn=getattr(L, name), _extra=extra, **a):
+            return _fn(a["coords"], a["Bp"], a["cfg"], a["out"], *_extra, None)
+        refused(name, call, ARG, Bp=-1)
+        refused(name, call, ARG, coords=None)
+        refused(name, call, ARG, out=None)
+        refused(name, call, ARG, cfg=None)
+        assert b"period" in refused(name, call, ARG, cfg=C.byref(cfg(offsets=(0.0, -14.0, 1.0, 0.5, -0.5))))
+        assert call(**{**good, "Bp": 0, "coords": None, "out": None}) == 0          # no rows: a no-op
+
+    # one table of bad canvases for the grid pair and the view pair: (start, n, canvas width) -> the quantity the message names
+    bad_canvases = (((0, 64, 0), b"canvas width 0"), ((0, 64, (1 << 24) + 1), b"2^24"), ((-1, 64, 16), b">= 0"), ((0, -1, 16), b">= 0"),
+                    (((1 << 24) * 16, 1, 16), b"2^24"))                             # the last one: row index 2^24
+    for name, (order, _) in canvas.items():
+        make = (lambda s, n, w: ops.view_arg(s, n, w, np.eye(3))) if name.endswith("view") else ops.grid_arg
+
+        def call(_order=order, _fn=getattr(L, name), **a):
+            return _fn(*_order(a))
+        for args, what in bad_canvases:
+            assert what in refused(name, call, ARG, src=make(*args)), (name, args)
+        # no pixels: NPP_OK before any pointer is looked at
+        assert call(**{**good, "src": make(5, 0, 16), "pack": None, "params": None, "out": None}) == 0
+
+
 def test_light16_entry_points_validate_on_the_host():
     """The 16-bit candidate chains (csrc/npp_light16.hip): size queries against the documented layout, and the argument checks that come
     before any launch -- batch a multiple of 64, strides that hold one candidate's arrays, at most NPP_MAX_STACK candidates in the

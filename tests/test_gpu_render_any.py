@@ -61,6 +61,43 @@ def test_scale_one_is_todays_render_and_integer_upscales_nest(dev, K, W):
             assert torch.equal(up[::S, ::S], r), (prec, S)
 
 
+def _built_widths():
+    import npp_amd
+    return list(npp_amd.FUSED_WIDTHS)
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp32"])
+@pytest.mark.parametrize("W", _built_widths())
+@pytest.mark.parametrize("K", [1, 3])
+def test_every_source_kind_through_the_one_path(dev, K, W, precision):
+    """ops.render on the four kinds of coordinate source -- int32 indices, the same integers as float32, the grid and the identity
+    view -- over the 13 x 11 = 143 pixels of a 13 x 11 fit (three 64-row tiles, the last one ragged): the same bits on the 143 rows,
+    inside bytes all 3, and the grid and view launches leave rows 143..191 of a prefilled 192-row output alone."""
+    from npp_amd import ops
+    from npp_amd.model import NPPNet
+    H, Wd = 13, 11
+    n, bp = H * Wd, 192
+    angles, periods, _ = oracle.synthetic_periodicity(RES[0], K)      # (periods of a larger image: every period + offset stays > 0)
+    net = NPPNet(angles, periods, oracle.SEED0_FREQS, (H, Wd), params=oracle.init_params(K, W=W, seed=7 * K + W), device=dev, ksplit=1,
+                 width=W)
+    pack = net._w32_pack() if precision == "fp32" else net._wf_pack()
+    idx = torch.cat([_int_grid(H, Wd, dev), torch.zeros((bp - n, 2), dtype=torch.int32, device=dev)], 0).contiguous()
+
+    def run(src, **kw):
+        out = torch.full((bp, 3), 5.0, dtype=torch.float32, device=dev)
+        ops.render(src, net.cfg, pack, net.params, precision=precision, out=out, width=W, **kw)
+        return out
+    ref = run(idx)
+    assert bool(torch.isfinite(ref).all()) and float(ref[:n].std()) > 0.0
+    assert torch.equal(run(idx.to(torch.float32))[:n], ref[:n])
+    inside = torch.full((bp,), 9, dtype=torch.uint8, device=dev)
+    for src, kw in ((ops.grid_arg(0, n, Wd), {}), (ops.view_arg(0, n, Wd, np.eye(3)), {"inside": inside})):
+        out = run(src, **kw)
+        assert torch.equal(out[:n], ref[:n]), type(src).__name__
+        assert bool((out[n:] == 5.0).all()), type(src).__name__
+    assert bool((inside[:n] == 3).all()) and bool((inside[n:] == 9).all())
+
+
 @pytest.mark.parametrize("K,W", KW)
 def test_float_positions_equal_the_grid_form(dev, K, W):
     """(3) the same positions built on the host in fp32 (model.canvas_coords) and passed to render_at == render_grid, bitwise."""
@@ -83,7 +120,7 @@ def test_chunked_and_ragged_launches_write_exactly_n_rows(dev, K, W):
     net, *_ = _net(dev, K, W)
     size, origin, scale = (150, 233), (-4.5, 7.25), (1.5, 2.0)
     total = size[0] * size[1]
-    for prec, fn, w in (("bf16", ops.mlp_fwd_grid, net.wf), ("fp32", ops.mlp_fwd32_grid, net._w32_pack())):
+    for prec, w in (("bf16", net.wf), ("fp32", net._w32_pack())):
         whole = net.render_grid(size, origin=origin, scale=scale, precision=prec).reshape(-1, 3)
         assert torch.equal(net.render_grid(size, origin=origin, scale=scale, precision=prec, chunk_rows=64 * 37 + 17).reshape(-1, 3), whole)
         assert torch.equal(net.render_grid(size, origin=origin, scale=scale, precision=prec, chunk_rows=size[1] + 1).reshape(-1, 3), whole)
@@ -91,13 +128,13 @@ def test_chunked_and_ragged_launches_write_exactly_n_rows(dev, K, W):
         for k in (0, 1, 5, 40):
             n = 64 * k + 17
             out = torch.full((n + 200, 3), 12345.0, dtype=torch.float32, device=dev)
-            fn(ops.grid_arg(s0, n, size[1], origin, scale), net.cfg, w, net.params, out=out, out_act=1, width=W)
+            ops.render(ops.grid_arg(s0, n, size[1], origin, scale), net.cfg, w, net.params, precision=prec, out=out, out_act=1, width=W)
             assert torch.equal(out[:n], whole[s0:s0 + n]), (prec, k)
             assert bool((out[n:] == 12345.0).all()), (prec, k)          # the clamped tail rows are not stored
             s0 += n
         # the very last pixel of the canvas, as the last row of a ragged launch
         out = torch.full((64 + 1, 3), -7.0, dtype=torch.float32, device=dev)
-        fn(ops.grid_arg(total - 17, 17, size[1], origin, scale), net.cfg, w, net.params, out=out, out_act=1, width=W)
+        ops.render(ops.grid_arg(total - 17, 17, size[1], origin, scale), net.cfg, w, net.params, precision=prec, out=out, out_act=1, width=W)
         assert torch.equal(out[:17], whole[total - 17:]) and bool((out[17:] == -7.0).all())
 
 
@@ -143,7 +180,7 @@ def test_against_the_reference_at_subpixel_and_outside_positions(dev):
         assert float((v.cpu() - torch.from_numpy(g["warp"][k])).abs().max()) < 2e-5
         ci = torch.from_numpy(np.round(c)).to(dev)                                     # integer-valued floats
         assert torch.equal(ep.embed(ci.clone()), ops.warp_fwd(ci.to(torch.int32).contiguous(), ep.cfg))
-        assert torch.equal(ops.warp_fwd_coordf(ci.contiguous(), ep.cfg), ops.warp_fwd(ci.to(torch.int32).contiguous(), ep.cfg))
+        assert torch.equal(ops.warp_fwd(ci.contiguous(), ep.cfg), ops.warp_fwd(ci.to(torch.int32).contiguous(), ep.cfg))
     P = oracle.init_params(3, W=256, seed=int(g["param_seed"]))
     net = NPPNet(angles, periods, freqs, res, params=P, device=dev, ksplit=1, width=256)
     f32 = net.render_at(ct, precision="fp32").cpu().numpy()
@@ -151,7 +188,7 @@ def test_against_the_reference_at_subpixel_and_outside_positions(dev):
     assert np.abs(f32 - g["pred"]).max() < 1e-4
     assert np.abs(b16 - g["pred"]).max() < 2e-2
     # the stand-alone embedder on float positions against the reference's embedding
-    e = ops.embed_fwd_coordf(ct[:64].contiguous(), net.cfg, torch.float32, precise=True).cpu().numpy()
+    e = ops.embed_fwd(ct[:64].contiguous(), net.cfg, torch.float32, precise=True).cpu().numpy()
     assert np.abs(e - g["emb64"]).max() < 1e-4
 
 
@@ -216,10 +253,10 @@ def test_abi_argument_errors(dev):
     """(9) zero / negative / non-finite scale, canvas width 0, an index >= 2^24: NPP_ERR_ARG with a message; n = 0 is a no-op."""
     from npp_amd import ops, NppError
     net, *_ = _net(dev, 1, 256)
-    for fn, w in ((ops.mlp_fwd_grid, net.wf), (ops.mlp_fwd32_grid, net._w32_pack())):
+    for prec, w in (("bf16", net.wf), ("fp32", net._w32_pack())):
         def call(start, n, cw, origin=(0.0, 0.0), scale=(1.0, 1.0)):
             out = torch.full((max(n, 1), 3), 5.0, dtype=torch.float32, device=dev)
-            fn(ops.grid_arg(start, n, cw, origin, scale), net.cfg, w, net.params, out=out, width=256)
+            ops.render(ops.grid_arg(start, n, cw, origin, scale), net.cfg, w, net.params, precision=prec, out=out, width=256)
             return out
         for scale in ((0.0, 1.0), (1.0, -2.0), (float("nan"), 1.0), (1.0, float("inf"))):
             with pytest.raises(NppError, match=r"failed \(-1\).*scale"):

@@ -83,16 +83,16 @@ def test_a_launch_stores_exactly_n_rows(dev, K, W):
     from npp_amd import ops
     net = _net(dev, K, W)
     total = R.CANVAS[0] * R.CANVAS[1]
-    for fn, w, prec in ((ops.mlp_fwd_view, net._wf_pack(), "bf16"), (ops.mlp_fwd32_view, net._w32_pack(), "fp32")):
+    for w, prec in ((net._wf_pack(), "bf16"), (net._w32_pack(), "fp32")):
         whole = net.render_view(R.CANVAS, R.HORIZON, precision=prec).reshape(-1, 3)
         for s0, n in ((0, 1), (CHUNK, 777), (total - 17, 17)):
             out = torch.full((n + 70, 3), -7.0, dtype=torch.float32, device=dev)
             inside = torch.full((n + 70,), 9, dtype=torch.uint8, device=dev)
-            fn(ops.view_arg(s0, n, R.CANVAS[1], R.HORIZON), net.cfg, w, net.params, out=out, inside=inside, out_act=1, width=W)
+            ops.render(ops.view_arg(s0, n, R.CANVAS[1], R.HORIZON), net.cfg, w, net.params, precision=prec, out=out, inside=inside, out_act=1, width=W)
             assert torch.equal(_bits(out[:n]), _bits(whole[s0:s0 + n])), (prec, s0, n)
             assert bool((out[n:] == -7.0).all()) and bool((inside[n:] == 9).all()) and bool((inside[:n] != 9).all())
         out = torch.full((4, 3), -7.0, dtype=torch.float32, device=dev)
-        fn(ops.view_arg(5, 0, R.CANVAS[1], R.HORIZON), net.cfg, w, net.params, out=out, width=W)     # n = 0: nothing launched
+        ops.render(ops.view_arg(5, 0, R.CANVAS[1], R.HORIZON), net.cfg, w, net.params, precision=prec, out=out, width=W)     # n = 0: nothing launched
         assert bool((out == -7.0).all())
 
 
@@ -101,11 +101,11 @@ def test_launchers_refuse_bad_views(dev):
     net = _net(dev, 1, 256)
     bad = np.eye(3)
     bad[2, 1] = np.nan
-    for fn, w in ((ops.mlp_fwd_view, net._wf_pack()), (ops.mlp_fwd32_view, net._w32_pack())):
+    for prec, w in (("bf16", net._wf_pack()), ("fp32", net._w32_pack())):
         out = torch.full((64, 3), 5.0, dtype=torch.float32, device=dev)
 
         def call(start, n, cw, M=np.eye(3)):
-            fn(ops.view_arg(start, n, cw, M), net.cfg, w, net.params, out=out, width=256)
+            ops.render(ops.view_arg(start, n, cw, M), net.cfg, w, net.params, precision=prec, out=out, width=256)
         for args, msg in (((0, 64, 16, bad), r"m\[7\].*not finite"), ((0, 64, 0), "canvas width 0"), ((-1, 64, 16), ">= 0"),
                           (((1 << 24) * 16, 1, 16), r"2\^24"), ((0, 64, (1 << 24) + 1), r"2\^24")):
             with pytest.raises(NppError, match=r"failed \(-1\).*" + msg):
