@@ -202,6 +202,38 @@ int npp_mlp_fwd32_view(const npp_view* view, const npp_embed_cfg* cfg, int width
 /* The positions and inside bytes of such a launch by plain C++ on the host (the same rule, compiled without contraction): out_yx
  * (n, 2) [y, x] ((0, 0) for a pixel not in view), inside (n) or null; H, W: the fit's image size (cfg->H, cfg->W). */
 int npp_view_coords_host(const npp_view* view, int H, int W, float* out_yx, uint8_t* inside);
+/* ---- supersampled launches: ss x ss samples per canvas pixel, averaged in the kernel ----------------------------------------
+ * The _grid_ss / _view_ss forms are the _grid / _view forms with ss in {1, 2, 4, 8} samples per canvas pixel in each direction and
+ * their mean as the pixel's colour.  ss^2 divides the 64-row tile of both chains, so a tile holds 64 / ss^2 whole pixels and the
+ * mean never crosses a workgroup: one launch, no atomics, no intermediate buffer.  The rule:
+ *   offsets       off[a] = (2 a + 1) / (2 ss) - 0.5 for a = 0 .. ss - 1 (exact in fp32).
+ *   sample order  sample s = a ss + b of canvas pixel (i, j) sits at the canvas position fi = (float)i + off[a], fj = (float)j +
+ *                 off[b], one fp32 add each; with ss > 1 a canvas row or column index must stay below 2^20 so that this add is exact.
+ *   grid form     y = y0 + fi / sy, x = x0 + fj / sx (IEEE quotient, then a separate add).
+ *   view form     d, y, x from (fi, fj) in the operation order of the _view forms (no contraction).  A sample is in view iff d > 0
+ *                 and y and x are finite; a sample not in view computes on (0, 0) and does not count.
+ *   chain rows    row r of a launch is sample r % ss^2 of pixel start + min(r / ss^2, n - 1); a launch runs n ss^2 rows and stores
+ *                 exactly n output rows.
+ *   pixel colour  after the output nonlinearity: acc = +0.0f; for s = 0 .. ss^2 - 1 in that order acc = acc + o_s if the sample
+ *                 counts (one rounded fp32 add each); colour = acc / (float)count (IEEE quotient).  In a grid launch every sample
+ *                 counts and count = ss^2.
+ *   inside byte   of a view launch: the byte the point launch writes for the pixel centre (i, j), unchanged, so masks do not depend
+ *                 on ss.  Where that byte is 0, or where no sample counts, the pixel stores (0, 0, 0) and byte 0.
+ *   ss = 1        is the _grid / _view launch bit for bit (these entry points forward to it).
+ * NPP_ERR_ARG (with a message) for ss outside {1, 2, 4, 8}, for an index that reaches 2^20 with ss > 1, for n ss^2 rows beyond the
+ * 2^31 - 1 tiles of a launch, and for everything the _grid / _view forms refuse; n == 0 stays a no-op. */
+int npp_mlp_fwd_grid_ss(const npp_grid* grid, int ss, const npp_embed_cfg* cfg, int width, const void* d_wf, const float* d_params,
+                        float* d_out, int out_act, void* stream);
+int npp_mlp_fwd32_grid_ss(const npp_grid* grid, int ss, const npp_embed_cfg* cfg, int width, const void* d_w32, const float* d_params,
+                          float* d_out, int out_act, void* stream);
+int npp_mlp_fwd_view_ss(const npp_view* view, int ss, const npp_embed_cfg* cfg, int width, const void* d_wf, const float* d_params,
+                        float* d_out, uint8_t* d_inside, int out_act, void* stream);
+int npp_mlp_fwd32_view_ss(const npp_view* view, int ss, const npp_embed_cfg* cfg, int width, const void* d_w32, const float* d_params,
+                          float* d_out, uint8_t* d_inside, int out_act, void* stream);
+/* The same rule by plain C++ on the host: the (n ss^2, 2) fp32 positions [y, x] of such a launch in chain-row order ((0, 0) for a
+ * sample not in view), sample_in_view (n ss^2 bytes, 0 / 1, may be null) and the per-pixel inside bytes (n, may be null). */
+int npp_grid_samples_host(const npp_grid* grid, int ss, float* out_yx);
+int npp_view_samples_host(const npp_view* view, int ss, int H, int W, float* out_yx, uint8_t* sample_in_view, uint8_t* inside);
 /* npp_mlp_fwd_act (inference) on fp32 positions: coords (Bp, 2) -> d_pred (Bp, 3), Bp a multiple of NPP_ROW_TILE. */
 int npp_mlp_fwd_coordf(const float* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_wf,
                        const float* d_params, float* d_pred, int out_act, void* stream);

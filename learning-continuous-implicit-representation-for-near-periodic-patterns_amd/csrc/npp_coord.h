@@ -1,6 +1,7 @@
 // npp_coord.h -- how a row's position enters the forward kernels and how its colour leaves them (include/npp_hip.h "continuous
 // coordinates"), with the host-side argument checks the entry points of those kernels share.  A new coordinate mode is one
-// CoordMode value, one branch in row_coord and one in store_rgb, one entry point per chain and one table row in ops.render.
+// CoordMode value, one branch in row_coord and one in store_rgb, one entry point per chain and one table row in ops.render.  (The
+// supersampled modes also need the samples of a pixel together: average_rgb, behind a barrier after store_rgb.)
 #pragma once
 #include "npp_common.h"
 
@@ -13,6 +14,9 @@ int check_embed_cfg(const npp_embed_cfg* c, const char* who);
 int check_canvas(int64_t start, int64_t n, int32_t width, const char* who);
 int check_grid(const npp_grid* g, const char* who);
 int check_view(const npp_view* v, const char* who);
+// What supersampling adds to a checked canvas (include/npp_hip.h "supersampled launches"): ss in {1, 2, 4, 8}; with ss > 1 indices
+// below 2^20 and n ss^2 rows within one launch
+int check_ss(int ss, int64_t start, int64_t n, int32_t width, const char* who);
 
 // The checks every fused-forward entry point makes before it launches, in this order: network width (NPP_ERR_UNSUPPORTED), the row
 // count, null pointers, out_act (NPP_ERR_ARG).  canvas: `rows` is the pixel count n of a grid / view launch (already >= 0 by
@@ -38,7 +42,9 @@ static inline int fwd_entry_check(const char* who, const npp_embed_cfg* cfg, int
 
 // ---- coordinate intake of the render paths ------------------------------------------------------------------------------------
 // Coordinate modes of the forward kernels: how row r's (y, x) enters.  A template parameter: the int32 form compiles as before.
-enum CoordMode { kCoordI32 = 0, kCoordF32 = 1, kCoordGrid = 2, kCoordView = 3 };
+// The SS modes are the grid and the view with ss x ss samples per canvas pixel, averaged in the store epilogue (src.ss > 1).
+enum CoordMode { kCoordI32 = 0, kCoordF32 = 1, kCoordGrid = 2, kCoordView = 3, kCoordGridSS = 4, kCoordViewSS = 5 };
+constexpr bool coord_is_ss(int cm) { return cm == kCoordGridSS || cm == kCoordViewSS; }
 
 // What a view launch adds to the forward kernels' arguments (the other modes never read it)
 struct ViewArgs {
@@ -53,6 +59,7 @@ struct CoordSrc {
   const float* coordsf;
   npp_grid g;
   ViewArgs view;
+  int32_t ss;             // the SS modes: samples per canvas pixel in each direction (2, 4 or 8)
 };
 
 // One separately rounded fp32 operation: the _rn intrinsics on the device, the plain operator on the host (every source is compiled
@@ -71,9 +78,8 @@ NPP_VIEW_OP(view_div, __fdiv_rn, /)
 // Canvas pixel p (row-major) of a view (include/npp_hip.h npp_view): d = (m6 i + m7 j) + m8, y = ((m0 i + m1 j) + m2) / d,
 // x = ((m3 i + m4 j) + m5) / d; i, j < 2^24 (checked at launch).  Returns the inside byte: 0 not in view (d <= 0 or a non-finite
 // position; y = x = 0 then, so nothing non-finite enters the chain), 1 in view, 3 also inside [-0.5, H - 0.5) x [-0.5, W - 0.5).
-__host__ __device__ __forceinline__ uint8_t view_coord(const npp_view& v, int H, int W, int64_t p, float& y, float& x) {
-  const int64_t i = p / v.width;
-  const float fi = (float)i, fj = (float)(int32_t)(p - i * v.width);
+// view_at: the same at the canvas position (fi, fj), which a supersampled launch places between the pixel centres.
+__host__ __device__ __forceinline__ uint8_t view_at(const npp_view& v, int H, int W, float fi, float fj, float& y, float& x) {
   const float d = view_add(view_add(view_mul(v.m[6], fi), view_mul(v.m[7], fj)), v.m[8]);
   y = view_div(view_add(view_add(view_mul(v.m[0], fi), view_mul(v.m[1], fj)), v.m[2]), d);
   x = view_div(view_add(view_add(view_mul(v.m[3], fi), view_mul(v.m[4], fj)), v.m[5]), d);
@@ -82,6 +88,10 @@ __host__ __device__ __forceinline__ uint8_t view_coord(const npp_view& v, int H,
     return 0;
   }
   return y >= -0.5f && y < (float)H - 0.5f && x >= -0.5f && x < (float)W - 0.5f ? 3 : 1;
+}
+__host__ __device__ __forceinline__ uint8_t view_coord(const npp_view& v, int H, int W, int64_t p, float& y, float& x) {
+  const int64_t i = p / v.width;
+  return view_at(v, H, W, (float)i, (float)(int32_t)(p - i * v.width), y, x);
 }
 
 // Row r of a view launch: canvas pixel start + min(r, n - 1), as in a grid launch
@@ -100,12 +110,43 @@ __device__ __forceinline__ void grid_coord(const npp_grid& g, int64_t r, float& 
   x = __fadd_rn(g.x0, __fdiv_rn((float)j, g.sx));
 }
 
+// ---- supersampled launches (include/npp_hip.h "supersampled launches") ---------------------------------------------------------
+// Row r of a launch with ss x ss samples per pixel is sample r % ss^2 of canvas pixel start + min(r / ss^2, n - 1); ss^2 divides the
+// 64-row tile, so a tile holds 64 / ss^2 whole pixels.  Sample s = a ss + b sits at the canvas position (i + off[a], j + off[b]),
+// off[a] = (2 a + 1) / (2 ss) - 0.5: exact in fp32, and so is the sum for i, j < 2^20 (checked at launch).
+__host__ __device__ __forceinline__ float ss_off(int ss, int a) { return view_add(view_div((float)(2 * a + 1), (float)(2 * ss)), -0.5f); }
+__host__ __device__ __forceinline__ void ss_canvas_pos(int32_t width, int ss, int64_t start, int64_t n, int64_t r, float& fi, float& fj) {
+  const int lg = __builtin_ctz((unsigned)ss);                 // ss is a power of two
+  const int64_t q = r >> (2 * lg);
+  const int s = (int)(r & ((1 << (2 * lg)) - 1));
+  const int64_t p = start + (q < n ? q : n - 1);
+  const int64_t i = p / width;
+  fi = view_add((float)i, ss_off(ss, s >> lg));
+  fj = view_add((float)(int32_t)(p - i * width), ss_off(ss, s & (ss - 1)));
+}
+// ... of a grid: the grid rule on that position (an IEEE quotient, then a separate add)
+__host__ __device__ __forceinline__ void grid_sample(const npp_grid& g, int ss, int64_t r, float& y, float& x) {
+  float fi, fj;
+  ss_canvas_pos(g.width, ss, g.start, g.n, r, fi, fj);
+  y = view_add(g.y0, view_div(fi, g.sy));
+  x = view_add(g.x0, view_div(fj, g.sx));
+}
+// ... of a view: view_at's operation order; returns the sample's inside byte (0: it does not count and computes on (0, 0))
+__host__ __device__ __forceinline__ uint8_t view_sample(const npp_view& v, int H, int W, int ss, int64_t r, float& y, float& x) {
+  float fi, fj;
+  ss_canvas_pos(v.width, ss, v.start, v.n, r, fi, fj);
+  return view_at(v, H, W, fi, fj, y, x);
+}
+
 // (y, x) of row r in coordinate mode CM: int32 pixel indices (coords, (N, 2) [y, x]), fp32 positions (src.coordsf, the same shape),
 // the implicit grid or the view.  Returns the inside byte of the position: a view's (0: not in view, y = x = 0), 3 in every other mode.
 template <int CM>
 __device__ __forceinline__ uint8_t row_coord(const int32_t* coords, const CoordSrc& src, int64_t r, float& y, float& x) {
   if (CM == kCoordView) return view_row(src.view, r, y, x);
-  if (CM == kCoordGrid) {
+  if (CM == kCoordViewSS) return view_sample(src.view.v, src.view.H, src.view.W, src.ss, r, y, x);
+  if (CM == kCoordGridSS) {
+    grid_sample(src.g, src.ss, r, y, x);
+  } else if (CM == kCoordGrid) {
     grid_coord(src.g, r, y, x);
   } else if (CM == kCoordF32) {
     const float2 c = ((const float2*)src.coordsf)[r];
@@ -121,10 +162,20 @@ __device__ __forceinline__ uint8_t row_coord(const int32_t* coords, const CoordS
 
 // Channel c of output row `row` leaves the chain as o: a grid launch stores exactly g.n rows; a view launch exactly view.v.n, with
 // the inside byte formed again from the map (nothing is carried through the chain), zeros for a pixel not in view and the byte
-// itself by the thread of channel 0; every other launch stores all its rows.
+// itself by the thread of channel 0; every other launch stores all its rows.  The SS modes store nothing here: o goes to
+// stage[64 rows][3] in LDS, and behind it a view's thread of channel 0 leaves whether its sample counts; average_rgb follows behind
+// a barrier.  `stage` is 4 * kStageWords bytes of LDS that nothing else uses until the kernel ends (null in every other mode).
+constexpr int kStageWords = NPP_ROW_TILE * 4;
 template <int CM>
-__device__ __forceinline__ void store_rgb(const CoordSrc& src, float* pred, int64_t row, int c, float o) {
-  if (CM == kCoordView) {
+__device__ __forceinline__ void store_rgb(const CoordSrc& src, float* pred, int64_t row, int c, float o, float* stage = nullptr) {
+  if (coord_is_ss(CM)) {
+    const int lr = (int)(row & (NPP_ROW_TILE - 1));
+    stage[lr * 3 + c] = o;
+    if (CM == kCoordViewSS && c == 0) {
+      float y, x;
+      ((uint32_t*)stage)[NPP_ROW_TILE * 3 + lr] = view_sample(src.view.v, src.view.H, src.view.W, src.ss, row, y, x) != 0;
+    }
+  } else if (CM == kCoordView) {
     if (row < src.view.v.n) {
       float y, x;
       const uint8_t in = view_coord(src.view.v, src.view.H, src.view.W, src.view.v.start + row, y, x);   // (row < n: view_row without its clamp)
@@ -132,6 +183,35 @@ __device__ __forceinline__ void store_rgb(const CoordSrc& src, float* pred, int6
       if (c == 0 && src.view.inside) src.view.inside[row] = in;
     }
   } else if (CM != kCoordGrid || row < src.g.n) pred[row * 3 + c] = o;
+}
+
+// The second half of an SS store, by every thread of the workgroup behind a barrier after store_rgb: thread 3 q + c < (64 / ss^2) * 3
+// forms channel c of the tile's pixel q -- acc = +0, then the ss^2 staged samples in order, one rounded add for each that counts (in a
+// grid all do), and an IEEE quotient by their number -- and stores it if the pixel is one of the launch's n.  A view's pixel keeps the
+// inside byte of its centre (view_coord, what the point launch writes); where that is 0 or no sample counts it stores zeros and byte 0.
+template <int CM>
+__device__ __forceinline__ void average_rgb(const CoordSrc& src, float* pred, int64_t row0, int tid, const float* stage) {
+  const int lg2 = 2 * __builtin_ctz((unsigned)src.ss);
+  if (tid >= (NPP_ROW_TILE >> lg2) * 3) return;
+  const int q = tid / 3, c = tid - q * 3;
+  const int64_t pix = (row0 >> lg2) + q;
+  if (pix >= (CM == kCoordViewSS ? src.view.v.n : src.g.n)) return;
+  const uint32_t* counts = (const uint32_t*)stage + NPP_ROW_TILE * 3;
+  float acc = 0.0f;
+  int cnt = 0;
+  for (int s = 0; s < (1 << lg2); ++s) {
+    const int lr = (q << lg2) + s;
+    if (CM == kCoordViewSS && !counts[lr]) continue;
+    acc = __fadd_rn(acc, stage[lr * 3 + c]);
+    ++cnt;
+  }
+  uint8_t in = 3;
+  if (CM == kCoordViewSS) {
+    float y, x;
+    in = cnt ? view_coord(src.view.v, src.view.H, src.view.W, src.view.v.start + pix, y, x) : 0;
+    if (c == 0 && src.view.inside) src.view.inside[pix] = in;
+  }
+  pred[pix * 3 + c] = in ? __fdiv_rn(acc, (float)cnt) : 0.0f;
 }
 
 // ---- the warp table of the fused forward kernels --------------------------------------------------------------------------------

@@ -78,6 +78,25 @@ int check_view(const npp_view* v, const char* who) {
   return check_canvas(v->start, v->n, v->width, who);
 }
 
+// What ss x ss samples per pixel add to a canvas that check_canvas passed (include/npp_hip.h "supersampled launches")
+int check_ss(int ss, int64_t start, int64_t n, int32_t width, const char* who) {
+  if (ss != 1 && ss != 2 && ss != 4 && ss != 8) { set_error("%s: ss=%d must be 1, 2, 4 or 8 samples per pixel and direction", who, ss); return NPP_ERR_ARG; }
+  if (ss == 1) return NPP_OK;
+  constexpr int64_t kExact = 1 << 20;                        // index + sample offset (sixteenths) is exact in fp32 below this
+  if (width > kExact) { set_error("%s: canvas width %d with ss=%d: column indices would reach 2^20", who, width, ss); return NPP_ERR_ARG; }
+  if (n == 0) return NPP_OK;
+  if ((start + n - 1) / width >= kExact) {
+    set_error("%s: canvas pixels [%lld, %lld + %lld) at width %d with ss=%d: row indices would reach 2^20", who, (long long)start,
+              (long long)start, (long long)n, width, ss);
+    return NPP_ERR_ARG;
+  }
+  if ((n * ss * ss + NPP_ROW_TILE - 1) / NPP_ROW_TILE > 0x7fffffffLL) {
+    set_error("%s: n=%lld x ss^2=%d rows are too many for one launch", who, (long long)n, ss * ss);
+    return NPP_ERR_ARG;
+  }
+  return NPP_OK;
+}
+
 #ifndef NPP_EMB_ROWS
 #define NPP_EMB_ROWS 32
 #endif

@@ -672,7 +672,8 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[NTW][kNB], char* out, int
 // parameter for the same reason as STACK (the run-time test cost the default launch 0.9 us in a same-box A/B)
 // CM: coordinate mode (npp_coord.h CoordMode) of the render paths -- fp32 positions (npp_mlp_fwd_coordf) or the implicit canvas
 // grid (npp_mlp_fwd_grid) or that canvas under a projective map (npp_mlp_fwd_view); all read the nonlinearity from A_.out_act like
-// ACT.  kCoordI32 is every other launch, unchanged.
+// ACT; the SS modes (npp_mlp_fwd_grid_ss / _view_ss) are the last two with ss x ss samples per canvas pixel, averaged behind the
+// output nonlinearity.  kCoordI32 is every other launch, unchanged.
 template <int TRAIN, bool MULTI, bool EMB_IN = false, bool STACK = false, bool ACT = false, int CM = kCoordI32>
 __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdArgs A_, EmbedDev e_arg, NetDesc d) {
   static_assert(CM == kCoordI32 || (TRAIN == 0 && !EMB_IN && !STACK), "the render coordinate modes are inference-only");
@@ -701,6 +702,8 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
   EmbedDev& ed = *(EmbedDev*)(sX + kRowTile);
   WarpEnt* tWarp = (WarpEnt*)((char*)&ed + kSmemE);
   float* sRGB = (float*)R0;             // [4 waves][64 rows][3], reused after the last barrier
+  float* sStage = sRGB + (kNT / 2) * kRowTile * 3;   // the SS modes: kStageWords behind it (npp_coord.h store_rgb)
+  static_assert(((kNT / 2) * kRowTile * 3 + kStageWords) * 4 <= kRegionBytes, "LDS");
   if (STACK) {
     // the image's constants come from global memory: one dword per thread, ONE load latency (thread 0 alone walked them in a rolled
     // loop of dependent load -> LDS store round trips: ~0.2 us each x sizeof / 4 on the critical path of every workgroup)
@@ -946,7 +949,11 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
       for (int w = 0; w < kNT / 2; ++w) z += sRGB[(w * kRowTile + row) * 3 + c];   // P's neuron tiles, in order
       float o = 1.0f / (1.0f + __expf(-z));                         // helpers.py:56 sigmoid
       if ((EMB_IN || ACT || CM != kCoordI32) && A_.out_act != 1) o = A_.out_act == 2 ? tanhf(z) : z;   // helpers.py:57-58 tanh (--normalize_type 2) / raw network output
-      store_rgb<CM>(A_.src, s_pred, row0 + row, c, o);
+      store_rgb<CM>(A_.src, s_pred, row0 + row, c, o, sStage);
+    }
+    if (coord_is_ss(CM)) {              // the ss x ss samples of a pixel -> their ordered mean (npp_coord.h)
+      wg_barrier();
+      average_rgb<CM>(A_.src, s_pred, row0, L.tid, sStage);
     }
   }
 #pragma unroll
@@ -967,15 +974,16 @@ using namespace npp;
 
 // Every launched instantiation of mlp_fwd_kernel, as one selection over (kernel form, stash form T, K > 1).  The entry point names
 // the form; T: 0 no stash (inference), 1 the 16-bit training stash, 2 the 8-bit one (npp_tune "stash8").  The stacked form always
-// trains and the render forms never do, so only those T exist for them: 3 forms x 3 T + stacked x 2 T + 3 render forms, x 2 for K.
-enum FwdForm { kFwdPlain, kFwdEmbIn, kFwdStack, kFwdAct, kFwdCoordF, kFwdGrid, kFwdView };
+// trains and the render forms never do, so only those T exist for them: 3 forms x 3 T + stacked x 2 T + 5 render forms, x 2 for K.
+enum FwdForm { kFwdPlain, kFwdEmbIn, kFwdStack, kFwdAct, kFwdCoordF, kFwdGrid, kFwdView, kFwdGridSS, kFwdViewSS };
 struct FwdLaunch {
   const FwdArgs& A; const EmbedDev& e; const NetDesc& d;
   dim3 grid; hipStream_t stream; const char* who;
   template <int T, FwdForm F>
   int go() const {
     constexpr bool EMB_IN = F == kFwdEmbIn, STACK = F == kFwdStack, ACT = F == kFwdAct;      // ACT: the output nonlinearity is read from the arguments
-    constexpr int CM = F == kFwdCoordF ? kCoordF32 : F == kFwdGrid ? kCoordGrid : F == kFwdView ? kCoordView : kCoordI32;
+    constexpr int CM = F == kFwdCoordF ? kCoordF32 : F == kFwdGrid ? kCoordGrid : F == kFwdView ? kCoordView :
+                       F == kFwdGridSS ? kCoordGridSS : F == kFwdViewSS ? kCoordViewSS : kCoordI32;
     const dim3 block(kThreads);
     return d.K > 1 ? launch_lds<mlp_fwd_kernel<T, true, EMB_IN, STACK, ACT, CM>>(who, grid, block, kSmemFwd, kSmemFwd, stream, A, e, d)
                    : launch_lds<mlp_fwd_kernel<T, false, EMB_IN, STACK, ACT, CM>>(who, grid, block, kSmemFwd, kSmemFwd, stream, A, e, d);
@@ -991,7 +999,8 @@ static int fwd_launch(FwdForm f, const FwdArgs& A, const EmbedDev& e, const NetD
   if (f == kFwdEmbIn) return T == 2 ? L.go<2, kFwdEmbIn>() : T == 1 ? L.go<1, kFwdEmbIn>() : L.go<0, kFwdEmbIn>();
   if (f == kFwdAct) return T == 2 ? L.go<2, kFwdAct>() : T == 1 ? L.go<1, kFwdAct>() : L.go<0, kFwdAct>();
   if (f == kFwdPlain) return T == 2 ? L.go<2, kFwdPlain>() : T == 1 ? L.go<1, kFwdPlain>() : L.go<0, kFwdPlain>();
-  return f == kFwdCoordF ? L.go<0, kFwdCoordF>() : f == kFwdGrid ? L.go<0, kFwdGrid>() : L.go<0, kFwdView>();
+  return f == kFwdCoordF ? L.go<0, kFwdCoordF>() : f == kFwdGrid ? L.go<0, kFwdGrid>() : f == kFwdView ? L.go<0, kFwdView>() :
+         f == kFwdGridSS ? L.go<0, kFwdGridSS>() : L.go<0, kFwdViewSS>();
 }
 
 // The body of the entry points that launch on a coordinate tensor (d_actT: the training stash, null for a render)
@@ -1063,6 +1072,31 @@ extern "C" int npp_mlp_fwd_view(const npp_view* view, const npp_embed_cfg* cfg, 
   CoordSrc src{};
   src.view.v = *view; src.view.inside = d_inside; src.view.H = cfg->H; src.view.W = cfg->W;
   return fwd_canvas(who, kFwdView, view->n, src, cfg, d_wf, d_params, d_out, out_act, stream);
+}
+
+// ss x ss samples per canvas pixel, averaged in the store epilogue (include/npp_hip.h "supersampled launches"): n ss^2 rows, n stored
+extern "C" int npp_mlp_fwd_grid_ss(const npp_grid* grid, int ss, const npp_embed_cfg* cfg, int width, const void* d_wf,
+                                   const float* d_params, float* d_out, int out_act, void* stream) {
+  const char* who = "npp_mlp_fwd_grid_ss";
+  if (ss == 1) return npp_mlp_fwd_grid(grid, cfg, width, d_wf, d_params, d_out, out_act, stream);
+  int rc = check_grid(grid, who);
+  if (rc || (rc = check_ss(ss, grid->start, grid->n, grid->width, who)) ||
+      (rc = fwd_entry_check(who, cfg, width, grid->n, true, nullptr, d_wf, d_params, d_out, out_act)) || grid->n == 0) return rc;
+  CoordSrc src{};
+  src.g = *grid; src.ss = ss;
+  return fwd_canvas(who, kFwdGridSS, grid->n * ss * ss, src, cfg, d_wf, d_params, d_out, out_act, stream);
+}
+
+extern "C" int npp_mlp_fwd_view_ss(const npp_view* view, int ss, const npp_embed_cfg* cfg, int width, const void* d_wf,
+                                   const float* d_params, float* d_out, uint8_t* d_inside, int out_act, void* stream) {
+  const char* who = "npp_mlp_fwd_view_ss";
+  if (ss == 1) return npp_mlp_fwd_view(view, cfg, width, d_wf, d_params, d_out, d_inside, out_act, stream);
+  int rc = check_view(view, who);
+  if (rc || (rc = check_ss(ss, view->start, view->n, view->width, who)) ||
+      (rc = fwd_entry_check(who, cfg, width, view->n, true, nullptr, d_wf, d_params, d_out, out_act)) || view->n == 0) return rc;
+  CoordSrc src{};
+  src.view.v = *view; src.view.inside = d_inside; src.view.H = cfg->H; src.view.W = cfg->W; src.ss = ss;
+  return fwd_canvas(who, kFwdViewSS, view->n * ss * ss, src, cfg, d_wf, d_params, d_out, out_act, stream);
 }
 
 // ---- stacked form: M images per launch (npp_common.h "stacked launches") ----------------------------------------------------

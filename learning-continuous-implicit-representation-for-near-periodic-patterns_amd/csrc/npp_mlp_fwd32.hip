@@ -239,6 +239,8 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
   // ---- rgb_linear 128 -> 3 + output activation (models/helpers.py:55-58)
   wg_barrier();
   float* sRGB = (float*)R;                         // [4 waves][64 rows][3]
+  float* sStage = sRGB + (kNT / 2) * kRowTile * 3; // the SS modes: kStageWords behind it (the region is free by now)
+  static_assert(((kNT / 2) * kRowTile * 3 + kStageWords) * 4 <= kRegion32, "LDS");
   {
     const float* Wr = P + d.w_off[LRGB];
     float part[kNB][3];
@@ -271,7 +273,11 @@ __global__ __launch_bounds__(kT32, 2) void mlp_fwd32_kernel(Fwd32Args A_, EmbedD
 #pragma unroll
     for (int w = 0; w < kNT / 2; ++w) z += sRGB[(w * kRowTile + row) * 3 + c];
     const float o = A_.out_act == 1 ? 1.0f / (1.0f + expf(-z)) : (A_.out_act == 2 ? tanhf(z) : z);
-    store_rgb<CM>(A_.src, A_.pred, row0 + row, c, o);
+    store_rgb<CM>(A_.src, A_.pred, row0 + row, c, o, sStage);
+  }
+  if (coord_is_ss(CM)) {                             // the ss x ss samples of a pixel -> their ordered mean (npp_coord.h)
+    wg_barrier();
+    average_rgb<CM>(A_.src, A_.pred, row0, tid, sStage);
   }
 }
 
@@ -369,6 +375,31 @@ extern "C" int npp_mlp_fwd32_view(const npp_view* view, const npp_embed_cfg* cfg
   Fwd32Args A = fwd32_args(view->n, d_w32, d_params, d_out, out_act);
   A.src.view.v = *view; A.src.view.inside = d_inside; A.src.view.H = cfg->H; A.src.view.W = cfg->W;
   return fwd32_launch<kCoordView>(A, cfg, stream, who);
+}
+
+// ss x ss samples per canvas pixel, averaged in the store epilogue (include/npp_hip.h "supersampled launches"): n ss^2 rows, n stored
+extern "C" int npp_mlp_fwd32_grid_ss(const npp_grid* grid, int ss, const npp_embed_cfg* cfg, int width, const void* d_w32,
+                                     const float* d_params, float* d_out, int out_act, void* stream) {
+  const char* who = "npp_mlp_fwd32_grid_ss";
+  if (ss == 1) return npp_mlp_fwd32_grid(grid, cfg, width, d_w32, d_params, d_out, out_act, stream);
+  int rc = check_grid(grid, who);
+  if (rc || (rc = check_ss(ss, grid->start, grid->n, grid->width, who)) ||
+      (rc = fwd_entry_check(who, cfg, width, grid->n, true, nullptr, d_w32, d_params, d_out, out_act)) || grid->n == 0) return rc;
+  Fwd32Args A = fwd32_args(grid->n * ss * ss, d_w32, d_params, d_out, out_act);
+  A.src.g = *grid; A.src.ss = ss;
+  return fwd32_launch<kCoordGridSS>(A, cfg, stream, who);
+}
+
+extern "C" int npp_mlp_fwd32_view_ss(const npp_view* view, int ss, const npp_embed_cfg* cfg, int width, const void* d_w32,
+                                     const float* d_params, float* d_out, uint8_t* d_inside, int out_act, void* stream) {
+  const char* who = "npp_mlp_fwd32_view_ss";
+  if (ss == 1) return npp_mlp_fwd32_view(view, cfg, width, d_w32, d_params, d_out, d_inside, out_act, stream);
+  int rc = check_view(view, who);
+  if (rc || (rc = check_ss(ss, view->start, view->n, view->width, who)) ||
+      (rc = fwd_entry_check(who, cfg, width, view->n, true, nullptr, d_w32, d_params, d_out, out_act)) || view->n == 0) return rc;
+  Fwd32Args A = fwd32_args(view->n * ss * ss, d_w32, d_params, d_out, out_act);
+  A.src.view.v = *view; A.src.view.inside = d_inside; A.src.view.H = cfg->H; A.src.view.W = cfg->W; A.src.ss = ss;
+  return fwd32_launch<kCoordViewSS>(A, cfg, stream, who);
 }
 
 // The forward of the exact-fp32 fit: npp_mlp_fwd32 plus the stash (d_stash: sizes[1] of npp_train_workspace32)

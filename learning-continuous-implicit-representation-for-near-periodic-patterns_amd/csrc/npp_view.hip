@@ -123,3 +123,35 @@ extern "C" int npp_view_coords_host(const npp_view* view, int H, int W, float* o
   }
   return NPP_OK;
 }
+
+// The sample positions of a supersampled grid launch (npp_mlp_fwd_grid_ss / npp_mlp_fwd32_grid_ss) on the host: grid_sample of npp_coord.h
+extern "C" int npp_grid_samples_host(const npp_grid* grid, int ss, float* out_yx) {
+  const char* who = "npp_grid_samples_host";
+  int rc = check_grid(grid, who);
+  if (rc || (rc = check_ss(ss, grid->start, grid->n, grid->width, who)) || grid->n == 0) return rc;
+  if (!out_yx) { set_error("%s: null pointer", who); return NPP_ERR_ARG; }
+  for (int64_t r = 0; r < grid->n * ss * ss; ++r) grid_sample(*grid, ss, r, out_yx[2 * r], out_yx[2 * r + 1]);
+  return NPP_OK;
+}
+
+// ... and of a supersampled view launch: view_sample per sample, view_coord of the pixel centre for the inside bytes
+extern "C" int npp_view_samples_host(const npp_view* view, int ss, int H, int W, float* out_yx, uint8_t* sample_in_view, uint8_t* inside) {
+  const char* who = "npp_view_samples_host";
+  int rc = check_view(view, who);
+  if (rc || (rc = check_ss(ss, view->start, view->n, view->width, who))) return rc;
+  if (H < 1 || W < 1) { set_error("%s: image size %d x %d must be >= 1", who, H, W); return NPP_ERR_ARG; }
+  if (view->n == 0) return NPP_OK;
+  if (!out_yx) { set_error("%s: null pointer", who); return NPP_ERR_ARG; }
+  const int ss2 = ss * ss;
+  for (int64_t q = 0; q < view->n; ++q) {
+    int cnt = 0;
+    for (int64_t r = q * ss2; r < (q + 1) * ss2; ++r) {
+      const uint8_t in = view_sample(*view, H, W, ss, r, out_yx[2 * r], out_yx[2 * r + 1]);
+      cnt += in != 0;
+      if (sample_in_view) sample_in_view[r] = in != 0;
+    }
+    float y, x;
+    if (inside) inside[q] = cnt ? view_coord(*view, H, W, view->start + q, y, x) : 0;
+  }
+  return NPP_OK;
+}

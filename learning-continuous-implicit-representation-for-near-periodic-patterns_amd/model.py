@@ -184,10 +184,11 @@ class NPPNet:
             ws["n_rows"] = n_rows
 
     # ---- the path ---------------------------------------------------------------------
-    def _render(self, src, precision, total=None, chunk_rows=None, inside=None, empty_ok=False):
+    def _render(self, src, precision, total=None, chunk_rows=None, inside=None, empty_ok=False, supersample=1):
         """The one render path (ops.render on the pack of `precision`).  src an (n, 2) int32 / float32 tensor: padded to whole 64-row
         tiles -> (n, 3).  src a function (start, n) -> ops.grid_arg / ops.view_arg with total canvas pixels: launches of at most
-        chunk_rows pixels -> (total, 3) (and their inside bytes into `inside`)."""
+        chunk_rows chain rows, i.e. max(1, chunk_rows // supersample^2) pixels -> (total, 3) (and their inside bytes into `inside`)."""
+        ss = ops.check_supersample(supersample)
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"precision {precision!r}: 'bf16' (fused chain) or 'fp32' (exact chain)")
         if total is None and empty_ok and src.shape[0] == 0:
@@ -201,10 +202,11 @@ class NPPNet:
                 src = torch.cat([src, src.new_zeros((bp - n, 2))], 0)
             return ops.render(src.contiguous(), self.cfg, pack, self.params, **kw)[:n]
         out = torch.empty((total, 3), dtype=torch.float32, device=self.device)
-        for s0 in range(0, total, chunk_rows):
-            n = min(chunk_rows, total - s0)
+        chunk = max(1, chunk_rows // (ss * ss))
+        for s0 in range(0, total, chunk):
+            n = min(chunk, total - s0)
             ops.render(src(s0, n), self.cfg, pack, self.params, out=out[s0:s0 + n],
-                       inside=None if inside is None else inside[s0:s0 + n], **kw)
+                       inside=None if inside is None else inside[s0:s0 + n], supersample=ss, **kw)
         return out
 
     @staticmethod
@@ -246,27 +248,34 @@ class NPPNet:
             raise ValueError(f"coords: expected (N, 2), got {tuple(c.shape)}")
         return self._render(c, precision, empty_ok=True)
 
-    def render_grid(self, size, origin=(0.0, 0.0), scale=(1.0, 1.0), precision="bf16", chunk_rows=1 << 22):
+    def render_grid(self, size, origin=(0.0, 0.0), scale=(1.0, 1.0), precision="bf16", chunk_rows=1 << 22, supersample=1):
         """A canvas of size = (H', W') pixels whose pixel (i, j) is the network at (y0 + i / sy, x0 + j / sx) of the fit's frame
         (origin = (y0, x0); scale = (sy, sx) canvas pixels per fit pixel, or one number for both) -> (H', W', 3) float32 on the
         device.  Chunked grid launches of at most chunk_rows pixels: no coordinate buffer is ever built.  Scale 1 at origin 0 is
-        render() of the full int32 grid bit for bit; at an integer scale S, pixel (S i, S j) is pixel (i, j) of scale 1."""
+        render() of the full int32 grid bit for bit; at an integer scale S, pixel (S i, S j) is pixel (i, j) of scale 1.
+        supersample = S in (1, 2, 4, 8): every pixel is the mean of S x S samples spread evenly over its footprint (offsets
+        (2 a + 1) / (2 S) - 0.5 of a pixel), averaged inside the launch -- antialiasing for a canvas coarser than the fit, at S^2
+        times the chain rows and no extra memory; chunk_rows keeps bounding the rows of a launch, and the result does not depend on it."""
         Hc, Wc, chunk = self._canvas(size, chunk_rows)
         o, s = _pair(origin), _pair(scale)
-        return self._render(lambda s0, n: ops.grid_arg(s0, n, Wc, o, s), precision, Hc * Wc, chunk).view(Hc, Wc, 3)
+        return self._render(lambda s0, n: ops.grid_arg(s0, n, Wc, o, s), precision, Hc * Wc, chunk,
+                            supersample=supersample).view(Hc, Wc, 3)
 
-    def render_view(self, size, M, precision="bf16", chunk_rows=1 << 22, return_inside=False):
+    def render_view(self, size, M, precision="bf16", chunk_rows=1 << 22, return_inside=False, supersample=1):
         """render_grid under a projective map (view.py): pixel (i, j) of the size = (H', W') canvas is the network at
         ((m0 i + m1 j) + m2, (m3 i + m4 j) + m5) / ((m6 i + m7 j) + m8) of the fit's frame, M the row-major 3 x 3 map, converted to
         float32 once -> (H', W', 3) float32 on the device, and with return_inside also (H', W') uint8: 0 the pixel is not in view
         (behind the map's horizon or at a non-finite position; it renders zero), 1 in view, 3 in view and inside the fit's image
         rectangle.  Chunked view launches, no coordinate buffer.  The affine map [[1/sy, 0, y0], [0, 1/sx, x0], [0, 0, 1]] with
-        power-of-two scales is render_grid bit for bit.  A non-finite or singular M raises ValueError before any launch."""
+        power-of-two scales is render_grid bit for bit.  A non-finite or singular M raises ValueError before any launch.
+        supersample = S as in render_grid, the sample positions going through the map; a sample that is not in view does not count,
+        and the inside bytes stay those of the pixel centres (a pixel whose centre is not in view renders zero)."""
         from . import view
         Hc, Wc, chunk = self._canvas(size, chunk_rows)
         m32 = view.check_matrix(M).astype(np.float32)
         inside = torch.empty(Hc * Wc, dtype=torch.uint8, device=self.device) if return_inside else None
-        out = self._render(lambda s0, n: ops.view_arg(s0, n, Wc, m32), precision, Hc * Wc, chunk, inside).view(Hc, Wc, 3)
+        out = self._render(lambda s0, n: ops.view_arg(s0, n, Wc, m32), precision, Hc * Wc, chunk, inside,
+                           supersample=supersample).view(Hc, Wc, 3)
         return (out, inside.view(Hc, Wc)) if return_inside else out
 
     # ---- model file (modelfile.py) ---------------------------------------------------------

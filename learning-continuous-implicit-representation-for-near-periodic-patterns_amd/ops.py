@@ -376,26 +376,44 @@ def _view_inside(inside, n):
 _RENDER = {("int32", "bf16"): lambda L, *a: L.npp_mlp_fwd_act(*a), ("int32", "fp32"): lambda L, *a: L.npp_mlp_fwd32(*a),
            ("float32", "bf16"): lambda L, *a: L.npp_mlp_fwd_coordf(*a), ("float32", "fp32"): lambda L, *a: L.npp_mlp_fwd32_coordf(*a),
            ("grid", "bf16"): lambda L, *a: L.npp_mlp_fwd_grid(*a), ("grid", "fp32"): lambda L, *a: L.npp_mlp_fwd32_grid(*a),
-           ("view", "bf16"): lambda L, *a: L.npp_mlp_fwd_view(*a), ("view", "fp32"): lambda L, *a: L.npp_mlp_fwd32_view(*a)}
+           ("view", "bf16"): lambda L, *a: L.npp_mlp_fwd_view(*a), ("view", "fp32"): lambda L, *a: L.npp_mlp_fwd32_view(*a),
+           ("grid_ss", "bf16"): lambda L, *a: L.npp_mlp_fwd_grid_ss(*a), ("grid_ss", "fp32"): lambda L, *a: L.npp_mlp_fwd32_grid_ss(*a),
+           ("view_ss", "bf16"): lambda L, *a: L.npp_mlp_fwd_view_ss(*a), ("view_ss", "fp32"): lambda L, *a: L.npp_mlp_fwd32_view_ss(*a)}
+SUPERSAMPLES = (1, 2, 4, 8)     # samples per canvas pixel and direction of a supersampled launch (include/npp_hip.h)
 
 
-def render(src, cfg, pack, params, precision="bf16", out=None, inside=None, out_act=1, width=NPP_WIDTH):
+def check_supersample(supersample):
+    """supersample as an int; ValueError (by name) unless it is one of SUPERSAMPLES."""
+    if isinstance(supersample, bool) or not isinstance(supersample, (int, np.integer)) or int(supersample) not in SUPERSAMPLES:
+        raise ValueError(f"supersample {supersample!r}: must be one of {SUPERSAMPLES} samples per canvas pixel in each direction")
+    return int(supersample)
+
+
+def render(src, cfg, pack, params, precision="bf16", out=None, inside=None, out_act=1, width=NPP_WIDTH, supersample=1):
     """The fused embedder + MLP render (no stash) of one coordinate source -> out (rows, 3) float32.  src: an int32 (Bp, 2) tensor of
     pixel indices or a float32 (Bp, 2) tensor of positions [y, x], Bp % 64 == 0 (out: (Bp, 3)); a grid_arg(...) or a view_arg(...):
     src.n canvas pixels -> out[:src.n], no coordinate buffer and no padding (out: at least (n, 3)).  precision: 'bf16' (the fused
     chain; pack = the wf pack) or 'fp32' (the exact chain; pack = the w32 pack).  inside (uint8, a view only, optional) receives
-    the bytes 0 not in view (the row is zero) / 1 in view / 3 also inside the fit's image rectangle.  out_act: 1 sigmoid, 2 tanh, 0 raw."""
+    the bytes 0 not in view (the row is zero) / 1 in view / 3 also inside the fit's image rectangle.  out_act: 1 sigmoid, 2 tanh, 0 raw.
+    supersample (a grid or a view only): S in SUPERSAMPLES; every pixel is the ordered mean of S x S samples, formed inside the one
+    launch of n S^2 chain rows (include/npp_hip.h "supersampled launches"); 1 is the point-sampled launch."""
     from ._lib import Grid, View
+    ss = check_supersample(supersample)
     if precision not in ("bf16", "fp32"):
         raise ValueError(f"precision {precision!r}: 'bf16' (fused chain) or 'fp32' (exact chain)")
     canvas = isinstance(src, (Grid, View))
     if inside is not None and not isinstance(src, View):
         raise ValueError("inside: only a view launch writes inside bytes")
+    if ss != 1 and not canvas:
+        raise ValueError(f"supersample={ss}: only a grid_arg(...) or a view_arg(...) is supersampled, not a tensor of positions "
+                         "(place the samples yourself)")
     if canvas:
         kind = "view" if isinstance(src, View) else "grid"
         out = _grid_out(out, src.n, params.device)
         head = (C.byref(src), C.byref(cfg), width, _p(pack), _p(params), _p(out))
-        tail = (_p(_view_inside(inside, src.n)),) if kind == "view" else ()
+        if ss != 1:
+            kind, head = kind + "_ss", (head[0], ss) + head[1:]
+        tail = (_p(_view_inside(inside, src.n)),) if kind in ("view", "view_ss") else ()
     else:
         if not (isinstance(src, torch.Tensor) and src.dtype in (torch.int32, torch.float32)):
             raise TypeError("src: expected an int32 or float32 (Bp, 2) tensor, a grid_arg(...) or a view_arg(...)")
@@ -418,6 +436,27 @@ def view_coords_host(view, res):
     check(lib().npp_view_coords_host(C.byref(view), int(res[0]), int(res[1]), C.c_void_p(yx.ctypes.data), C.c_void_p(inside.ctypes.data)),
           "npp_view_coords_host")
     return yx, inside
+
+
+def grid_samples_host(grid, supersample):
+    """npp_grid_samples_host: the (n S^2, 2) fp32 sample positions [y, x] of a supersampled grid launch in chain-row order, by plain
+    C++ on the host."""
+    ss = check_supersample(supersample)
+    yx = np.zeros((grid.n * ss * ss, 2), np.float32)
+    check(lib().npp_grid_samples_host(C.byref(grid), ss, C.c_void_p(yx.ctypes.data)), "npp_grid_samples_host")
+    return yx
+
+
+def view_samples_host(view, supersample, res):
+    """npp_view_samples_host: the (n S^2, 2) fp32 sample positions of a supersampled view launch, which of them are in view
+    (n S^2,) and the per-pixel inside bytes (n,) it writes, by plain C++ on the host; res = (H, W) of the fit."""
+    ss = check_supersample(supersample)
+    yx = np.zeros((view.n * ss * ss, 2), np.float32)
+    counts = np.zeros(view.n * ss * ss, np.uint8)
+    inside = np.zeros(view.n, np.uint8)
+    check(lib().npp_view_samples_host(C.byref(view), ss, int(res[0]), int(res[1]), C.c_void_p(yx.ctypes.data),
+                                      C.c_void_p(counts.ctypes.data), C.c_void_p(inside.ctypes.data)), "npp_view_samples_host")
+    return yx, counts, inside
 
 
 def _warp_args(M, size, mode):

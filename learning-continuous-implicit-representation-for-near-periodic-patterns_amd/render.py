@@ -13,7 +13,13 @@ ceil(H sy) x ceil(W sx): the fit's own canvas at that density.  The PNG is writt
 With --view (the view.json `python -m npp_amd.rectify` wrote) the canvas is the photograph's frame and the network is evaluated
 directly at the photograph's pixel positions mapped through photo_to_rect (NPPNet.render_view): no rendered image is resampled.
 --into P.png writes the photograph with the render in place of its pixels inside the fit's rectangle (--beyond: wherever the plane
-is in view; --mask: only where that photo-frame mask is black, i.e. unknown); every other pixel keeps the photograph's bytes."""
+is in view; --mask: only where that photo-frame mask is black, i.e. unknown); every other pixel keeps the photograph's bytes.
+
+    python -m npp_amd.render --model M.npz --out thumb.png --scale 0.25 --supersample auto
+
+--supersample S (1, 2, 4, 8 or auto; default 1) renders every canvas pixel as the mean of S x S samples spread over its footprint,
+averaged inside the render launch: antialiasing for a canvas that is coarser than the fit (a --scale below 1, the far end of a
+--view).  auto takes the smallest S that brings the coarsest spot down to view.MINIFY_WARN fit pixels per sample, at most 8."""
 import argparse
 import math
 import os
@@ -31,7 +37,9 @@ def parse(argv=None):
     ap.add_argument("--size", type=int, nargs=2, default=None, metavar=("H", "W"), help="canvas size (default ceil(H sy) x ceil(W sx))")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"], help="bf16: the fused chain of the fit; fp32: the exact chain")
     ap.add_argument("--npy", default=None, help="also write the (H, W, 3) float32 canvas as .npy")
-    ap.add_argument("--chunk_rows", type=int, default=1 << 22, help="canvas pixels per launch")
+    ap.add_argument("--chunk_rows", type=int, default=1 << 22, help="canvas pixels per launch (times S^2 samples: chain rows per launch)")
+    ap.add_argument("--supersample", default=None, metavar="S",
+                    help="S x S samples per canvas pixel, averaged in the launch: 1, 2, 4, 8 or auto (default 1: point sampling)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--view", default=None, help="view.json of `python -m npp_amd.rectify`: render in the photograph's frame")
     ap.add_argument("--into", default=None, help="with --view: the photograph (PNG) to put the render into")
@@ -60,7 +68,18 @@ def parse(argv=None):
     if args.chunk_rows < 1:
         ap.error(f"--chunk_rows {args.chunk_rows}: must be >= 1")
     args.scale = (sy, sx)
+    args.supersample_given = args.supersample is not None        # the closing line names S only when the flag was given
+    if args.supersample != "auto":
+        if args.supersample not in (None, "1", "2", "4", "8"):
+            ap.error(f"--supersample {args.supersample}: must be 1, 2, 4, 8 or auto")
+        args.supersample = int(args.supersample or 1)
     return args, ap
+
+
+def auto_supersample(scale):
+    """--supersample auto of a grid render: view.supersample_for's rule on the fit pixels per canvas pixel, max(1 / sy, 1 / sx)."""
+    from . import view
+    return view.supersample_for_density(max(1.0 / scale[0], 1.0 / scale[1]))
 
 
 def main(argv=None):
@@ -85,15 +104,22 @@ def main(argv=None):
     from . import io as nio
     from .model import NPPNet
     net = NPPNet.load(args.model, device=args.device)
-    img = net.render_grid(size, origin=tuple(args.origin), scale=(sy, sx), precision=args.precision, chunk_rows=args.chunk_rows)
+    ss = auto_supersample((sy, sx)) if args.supersample == "auto" else args.supersample
+    img = net.render_grid(size, origin=tuple(args.origin), scale=(sy, sx), precision=args.precision, chunk_rows=args.chunk_rows,
+                          supersample=ss)
     img = img.cpu().numpy()
     nio.imsave(args.out, img)               # what dump_testset writes as pred_rgb_img.png (a tanh output is clipped there too)
     if args.npy:
         import numpy as np
         np.save(args.npy, img)
     print(f"rendered {size[0]} x {size[1]} ({args.precision}) at scale ({sy:g}, {sx:g}), origin ({args.origin[0]:g}, {args.origin[1]:g}) "
-          f"of a {H} x {W} fit -> {args.out}")
+          f"of a {H} x {W} fit" + _ss_note(args, ss) + f" -> {args.out}")
     return img
+
+
+def _ss_note(args, ss):
+    """What the closing line says about supersampling: nothing unless the flag was given."""
+    return f", {ss} x {ss} samples per pixel" + (" (auto)" if args.supersample == "auto" else "") if args.supersample_given else ""
 
 
 def _main_view(args, ap, res):
@@ -115,12 +141,14 @@ def _main_view(args, ap, res):
     for flag, a in (("--into", photo), ("--mask", mask)):
         if a is not None and tuple(a.shape[:2]) != tuple(size):
             ap.error(f"{flag}: {a.shape[0]} x {a.shape[1]}, the view's photograph is {size[0]} x {size[1]}")
-    print(view.density_report(v["photo_to_rect"], size, "sampling density of the photograph on the fit's plane"))
+    ss = view.supersample_for(v["photo_to_rect"], size) if args.supersample == "auto" else args.supersample
+    print(view.density_report(v["photo_to_rect"], size, "sampling density of the photograph on the fit's plane", ss))
 
     from . import io as nio
     from .model import NPPNet
     net = NPPNet.load(args.model, device=args.device)
-    img, inside = net.render_view(size, v["photo_to_rect"], precision=args.precision, chunk_rows=args.chunk_rows, return_inside=True)
+    img, inside = net.render_view(size, v["photo_to_rect"], precision=args.precision, chunk_rows=args.chunk_rows, return_inside=True,
+                                  supersample=ss)
     if photo is not None:
         from PIL import Image
         Image.fromarray(view.composite(photo, img, inside, mask=mask, beyond=args.beyond).cpu().numpy()).save(args.out)
@@ -131,7 +159,7 @@ def _main_view(args, ap, res):
         np.save(args.npy, img)
     n_in, n_fit = int((inside != 0).sum()), int((inside == 3).sum())
     print(f"rendered {size[0]} x {size[1]} ({args.precision}) under {args.view}: {n_in} pixels in view, {n_fit} inside the "
-          f"{res[0]} x {res[1]} fit" + (f", put into {args.into}" if args.into else "") + f" -> {args.out}")
+          f"{res[0]} x {res[1]} fit" + _ss_note(args, ss) + (f", put into {args.into}" if args.into else "") + f" -> {args.out}")
     return img
 
 

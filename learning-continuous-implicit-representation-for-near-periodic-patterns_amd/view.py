@@ -133,12 +133,36 @@ def sampling_density(M, size):
     return float(dens.min()), float(dens.max())
 
 
-def density_report(M, size, what):
-    """One line for the commands: the density range, with a warning when the view minifies by more than MINIFY_WARN."""
+SUPERSAMPLES = (1, 2, 4, 8)      # samples per canvas pixel and direction the render launches take (NPPNet.render_view supersample=)
+
+
+def supersample_for_density(density):
+    """The smallest S in SUPERSAMPLES whose S x S samples per canvas pixel bring `density` target pixels per canvas pixel down to
+    density / S <= MINIFY_WARN per sample; the largest S where none does (an infinite density included)."""
+    for S in SUPERSAMPLES:
+        if density / S <= MINIFY_WARN:
+            return S
+    return SUPERSAMPLES[-1]
+
+
+def supersample_for(M, size):
+    """supersample_for_density of the largest sampling_density of the view over the size = (H, W) canvas: what
+    `python -m npp_amd.render --view ... --supersample auto` renders with."""
+    return supersample_for_density(sampling_density(M, size)[1])
+
+
+def density_report(M, size, what, supersample=1):
+    """One line for the commands: the density range, with a warning when the view minifies by more than MINIFY_WARN per sample
+    (supersample = S: S x S samples per canvas pixel, named in the line when S > 1)."""
     lo, hi = sampling_density(M, size)
     line = f"{what}: {lo:.3f} .. {hi:.3f} target pixels per canvas pixel"
-    if hi > MINIFY_WARN:
-        line += f"  WARNING: minifies by more than {MINIFY_WARN} -- point sampling aliases there (no antialiasing)"
+    if supersample == 1:
+        if hi > MINIFY_WARN:
+            line += f"  WARNING: minifies by more than {MINIFY_WARN} -- point sampling aliases there (no antialiasing)"
+        return line
+    line += f", {supersample} x {supersample} samples per canvas pixel ({lo / supersample:.3f} .. {hi / supersample:.3f} per sample)"
+    if hi / supersample > MINIFY_WARN:
+        line += f"  WARNING: still minifies by more than {MINIFY_WARN} per sample -- it aliases there"
     return line
 
 
