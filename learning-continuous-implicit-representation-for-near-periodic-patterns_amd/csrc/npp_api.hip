@@ -6,7 +6,8 @@
 #include <string.h>
 #include <vector>
 
-#include "npp_common.h"
+#include "npp_adam.h"
+#include "npp_chain16.h"
 #include "npp_stash_census.h"
 
 namespace npp {

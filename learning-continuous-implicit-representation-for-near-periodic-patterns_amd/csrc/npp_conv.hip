@@ -31,7 +31,7 @@
 #include <string.h>
 #include <type_traits>
 
-#include "npp_common.h"
+#include "npp_robust.h"
 #include "npp_trunk_layout.h"
 #ifdef NPP_DIAG
 #include "npp_diag.h"          // tools/npp_diag.h: diagnostic builds only (in-kernel time stamps)

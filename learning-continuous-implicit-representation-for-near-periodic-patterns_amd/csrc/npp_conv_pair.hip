@@ -15,7 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "npp_common.h"
+#include "npp_robust.h"
 #include "npp_trunk_layout.h"
 #ifdef NPP_DIAG
 #include "npp_diag.h"          // tools/npp_diag.h: diagnostic builds only (in-kernel time stamps)

@@ -21,7 +21,7 @@
 //   draw = -dD on 0 < raw < 1 ; dxh = draw yh^T ; dx = (dxh - xh (xh . dxh)) / |x - mu|.
 #include <stdlib.h>
 
-#include "npp_common.h"
+#include "npp_robust.h"
 #include <type_traits>
 #include "npp_trunk_layout.h"
 

@@ -91,7 +91,7 @@ __global__ void light_pack_kernel(LightArgs a, LightPackDesc pd, float* __restri
 }
 
 // ---- optimizer.step() + zero_grad() + re-pack in one launch ---------------------------------------------------------------------
-// Adam over the stacked blobs (torch.optim.Adam single-tensor maths, adam_update in npp_common.h), every updated weight scattered into
+// Adam over the stacked blobs (torch.optim.Adam single-tensor maths, adam_update in npp_adam.h), every updated weight scattered into
 // the packs through the inverse of light_pack_kernel's map, the gradient cleared on the way; the extra block column (blockIdx.x ==
 // gridDim.x - 1) steps the candidate's six adaptive-loss latents and clears one loss word.
 struct LightAdamArgs {

@@ -1,8 +1,9 @@
 // npp_light16.hip -- NPP_Net_light's training chains on the 16-bit matrix pipe (VERDICT r3 "f1 in 16-bit"):
 // the proposal-ranking fits of NPP_proposal/search.py:85-147 (one NPP_Net_light per candidate, models/networks.py:176-263 with
 // len(freq_scales) == 1, D = 4, W = 256, snake) with bf16 operands, fp32 accumulation and fp32 master weights -- the numeric
-// contract of the main loop's coordinate MLP (npp_mlp_fwd.hip / npp_mlp_bwd.hip), whose building blocks these kernels share
-// (npp_common.h: weight-stream ring, mma_ring, fragment regions in LDS, W-format stashes).  npp_light.hip is the exact-fp32
+// contract of the main loop's coordinate MLP (npp_mlp_fwd.hip / npp_mlp_bwd.hip), whose building blocks these kernels run
+// (npp_chain16.h: weight-stream ring and mma_ring, fragment regions in LDS, bias prefetch, the backward's z prefetch and epilogue,
+// W-format stashes; own to this file: the forward epilogue l16_epi and the rgb heads).  npp_light.hip is the exact-fp32
 // form of the same chains (v_mfma_f32_32x32x2_f32, 157 TFLOP/s peak); this one runs v_mfma_f32_32x32x16_bf16.
 //
 //   forward   x_per(20) -> 4 x [256, snake] -> feature_linear1 (256, linear) -> [f1 | x_pos(42)] -> pos_linears.0 (128, snake)
@@ -18,6 +19,7 @@
 // linear ones.
 #include <stdlib.h>
 
+#include "npp_chain16.h"
 #include "npp_light_common.h"
 
 namespace npp {
@@ -94,7 +96,7 @@ __global__ void light16_pack_kernel(L16Args a, L16Pack pd, bf16x8* __restrict__ 
 }
 
 // ---- optimizer.step() + the packs of the next forward / backward in one launch ----------------------------------------------------
-// Adam over the stacked fp32 blobs (adam_update, npp_common.h); the gradient of a parameter is the sum of the weight-gradient
+// Adam over the stacked fp32 blobs (adam_update, npp_adam.h); the gradient of a parameter is the sum of the weight-gradient
 // launch's split-K slabs in slab order (plain stores there, no atomics: bit-reproducible); every updated weight is scattered as bf16
 // into both packs through the inverse of light16_pack_kernel's map.  The extra block column steps the candidate's six
 // adaptive-loss latents and clears one loss word.
@@ -149,18 +151,7 @@ __global__ __launch_bounds__(256) void light16_adam_pack_kernel(L16AdamArgs a, L
 // 27 us for this element-wise kernel: its loads are 64-byte pieces of 32 different rows per instruction, and that costs more than the
 // 2-byte scattered stores it removes.)
 
-// ---- shared pieces ----------------------------------------------------------------------------------------------------------------
-template <int NTW>
-__device__ __forceinline__ void l16_bias(f32x16 (&acc)[NTW][kNB], const float* __restrict__ bias, int nt0, const Lane& L) {
-#pragma unroll
-  for (int nt = 0; nt < NTW; ++nt) {
-    f32x16 bv;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) bv[r] = bias[(nt0 + nt) * 32 + acc_row(r, L.h)];
-#pragma unroll
-    for (int bt = 0; bt < kNB; ++bt) acc[nt][bt] = bv;
-  }
-}
+// ---- pieces of this file's own (the rest: npp_chain16.h) ----------------------------------------------------------------------------
 // forward epilogue: SNAKE: z -> fp16 stash, a = snake(z) -> fragments of the next layer; linear: the bf16 fragments are the stash.
 // acc keeps the fp32 activation (pos_linears.0 -> rgb_linear reads it back)
 template <bool SNAKE, int NTW>
@@ -208,7 +199,8 @@ __device__ __forceinline__ bool l16_item(int n_wg, int C, int& c, int& wg) {
   wg = l - c * n_wg;
   return true;
 }
-// The weight-stream ring of npp_common.h (WRing / mma_ring) with the depth as a parameter.  What bounds these chains, measured with
+// The weight stream is the ring of npp_chain16.h (WRing / mma_ring), every part padded to a multiple of its depth (l16_tot), so
+// that each starts at slot 0 and hands the ring over to the next part, or to nobody (kNoW).  What bounds these chains, measured with
 // timing-only builds on 9 candidates x 2048 rows (288 workgroups; forward / backward launch, us):  as shipped 31.6 / 40.3;  no stash
 // stores (NPP_DIAG_NOSTASH) 27.6 / 27.8;  no MFMAs (NPP_DIAG_L16_NOMFMA) 27.4 / 38.2;  neither 23.2 / 26.6;  ring depth 8 instead of
 // 4, candidate-contiguous XCD numbering, bias prefetch: no change each.  I.e. the skeleton -- every workgroup streams its candidate's
@@ -217,75 +209,7 @@ __device__ __forceinline__ bool l16_item(int n_wg, int C, int& c, int& wg) {
 // dz stores cost 12 us.  128-row workgroups (144 of them: one per CU, half the weight bytes per row) were then built (kernels templated on
 // the batch tiles per workgroup, tests green) and measured: forward 32.5 -> 39.6 us, backward 40.9 -> 41.4 -- with one wave per SIMD a
 // workgroup's MFMA + epilogue time per row adds to its weight stream instead of hiding under it.  Not kept.
-#ifndef NPP_LIGHT16_RING
-#define NPP_LIGHT16_RING 4
-#endif
-constexpr int kLRD = NPP_LIGHT16_RING;
-template <int NTW> struct LRing { bf16x8 w[kLRD][NTW]; wrsrc_t rsrc; };
-template <int NTW, int NT>
-__device__ __forceinline__ void lslot_load(LRing<NTW>& r, int slot, wptr_t wp, int ks, int nt0, int lane) {
-  typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-#pragma unroll
-  for (int nt = 0; nt < NTW; ++nt) {
-    const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(r.rsrc, lane * 16, (int)((wp + (uint32_t)((ks * NT + nt0 + nt) * 64)) * 16u), 0);
-    r.w[slot][nt] = __builtin_bit_cast(bf16x8, raw);
-  }
-}
-template <int NTW, int NT>
-__device__ __forceinline__ void lring_fill(LRing<NTW>& r, wptr_t wp, int nt0, int lane) {
-#pragma unroll
-  for (int q = 0; q < kLRD; ++q) lslot_load<NTW, NT>(r, q, wp, q, nt0, lane);
-}
-// schedule positions [0, KSTOT) of a part with KSREAL real k-steps (KSTOT a multiple of the depth, so that every part starts at slot 0);
-// after the MFMAs of position ks its slot is refilled with this part's k-step ks + depth or, past the part's end, the next part's
-template <int KSREAL, int KSTOT, int NTW, int NT>
-__device__ __forceinline__ void lmma(f32x16 (&acc)[NTW][kNB], const char* region, wptr_t wp, wptr_t next_wp, int nt0, const Lane& L, LRing<NTW>& ring) {
-  static_assert(KSTOT % kLRD == 0 && KSREAL <= KSTOT, "ring schedule");
-  bf16x8 xn[kNB];
-#pragma unroll
-  for (int bt = 0; bt < kNB; ++bt) xn[bt] = lds_frag(region, 0, bt, L.lane);
-#pragma unroll
-  for (int ks = 0; ks < KSTOT; ++ks) {
-    const int slot = ks % kLRD;
-    if (ks < KSREAL) {
-      bf16x8 x[kNB];
-#pragma unroll
-      for (int bt = 0; bt < kNB; ++bt) x[bt] = xn[bt];
-      if (ks + 1 < KSREAL) {
-#pragma unroll
-        for (int bt = 0; bt < kNB; ++bt) xn[bt] = lds_frag(region, ks + 1, bt, L.lane);
-      }
-#pragma unroll
-      for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-        for (int bt = 0; bt < kNB; ++bt) {
-          acc[nt][bt] = mfma_bf16(ring.w[slot][nt], x[bt], acc[nt][bt]);
-        }
-    }
-    if (ks + kLRD < KSREAL) lslot_load<NTW, NT>(ring, slot, wp, ks + kLRD, nt0, L.lane);
-    else if (ks + kLRD >= KSTOT && next_wp != kNoW) lslot_load<NTW, NT>(ring, slot, next_wp, ks + kLRD - KSTOT, nt0, L.lane);
-    asm volatile("" ::: "memory");   // pin the refill here: no hoisting of later loads
-  }
-}
-constexpr int l16_tot(int ks) { return (ks + kLRD - 1) / kLRD * kLRD; }
-
-template <int NTW> struct L16Bias { float v[NTW][16]; };
-template <int NTW>
-__device__ __forceinline__ void l16_bias_fetch(L16Bias<NTW>& bp, const float* __restrict__ bias, int nt0, const Lane& L) {
-#pragma unroll
-  for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) bp.v[nt][r] = bias[(nt0 + nt) * 32 + acc_row(r, L.h)];
-}
-template <int NTW>
-__device__ __forceinline__ void l16_bias_apply(f32x16 (&acc)[NTW][kNB], const L16Bias<NTW>& bp) {
-#pragma unroll
-  for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-    for (int bt = 0; bt < kNB; ++bt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[nt][bt][r] = bp.v[nt][r];
-}
+constexpr int l16_tot(int ks) { return (ks + kRD - 1) / kRD * kRD; }      // schedule positions of a part with ks real k-steps
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kL16Threads, 2) void light16_fwd_kernel(L16Args a, L16Pack pd, int n_wg, int C) {
@@ -308,10 +232,10 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_fwd_kernel(L16Args a, 
   const int nt0 = 2 * L.wave;
   auto arr = [&](int ks_off) -> char* { return actF + wfmt_array_base(ks_off, L.n_wg); };
 
-  LRing<2> ring;
-  LRing<1> ringp;
+  WRing<2> ring;
+  WRing<1> ringp;
   ring.rsrc = ringp.rsrc = make_wrsrc(a.pack + (int64_t)c * a.pack_stride16, pd.total);
-  lring_fill<2, kNT>(ring, (wptr_t)pd.f_off[LF_L0], nt0, L.lane);
+  wring_fill<2, kNT>(ring, (wptr_t)pd.f_off[LF_L0], nt0, L.lane);
 
   // inputs -> fragments: x_per (2 k-steps, region R1) and x_pos (4 k-steps, region RX), both also into their stash arrays
   {
@@ -333,12 +257,12 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_fwd_kernel(L16Args a, 
   f32x16 acc[2][kNB];
   constexpr int A = kKSAct;
   // (the NEXT layer's bias values are fetched before the current layer's epilogue: their L2 latency hides under it and the barrier)
-  L16Bias<2> bn;
-  L16Bias<1> bnp;
+  BiasPre<2> bn;
+  BiasPre<1> bnp;
   // periodic_linears.0: 20 (32 slots) -> 256, snake: R1 -> R0
-  l16_bias<2>(acc, P + a.L.b_off[0], nt0, L);
-  lmma<2, l16_tot(2), 2, kNT>(acc, R1, (wptr_t)pd.f_off[LF_L0], (wptr_t)pd.f_off[LF_L1], nt0, L, ring);
-  l16_bias_fetch<2>(bn, P + a.L.b_off[1], nt0, L);
+  init_bias<2>(acc, P + a.L.b_off[0], nt0, L);
+  mma_ring<0, l16_tot(2), 2, l16_tot(2), 2, kNT>(acc, R1, 0, (wptr_t)pd.f_off[LF_L0], (wptr_t)pd.f_off[LF_L1], nt0, L, ring);
+  bias_fetch<2>(bn, P + a.L.b_off[1], nt0, L);
   l16_epi<true, 2>(acc, R0, nt0, arr(L16A_Z0), A, wg, L);
   wg_barrier();
   // periodic_linears.1 .. 3: R0 -> R1 -> R0 -> R1
@@ -346,25 +270,25 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_fwd_kernel(L16Args a, 
   for (int l = 1; l <= 3; ++l) {
     char* in = (l & 1) ? R0 : R1;
     char* out = (l & 1) ? R1 : R0;
-    l16_bias_apply<2>(acc, bn);
-    lmma<A, l16_tot(A), 2, kNT>(acc, in, (wptr_t)pd.f_off[LF_L0 + l], (wptr_t)pd.f_off[LF_L0 + l + 1], nt0, L, ring);
-    l16_bias_fetch<2>(bn, P + a.L.b_off[l == 3 ? 5 : l + 1], nt0, L);
+    bias_apply<2>(acc, bn);
+    mma_ring<0, l16_tot(A), A, l16_tot(A), 2, kNT>(acc, in, 0, (wptr_t)pd.f_off[LF_L0 + l], (wptr_t)pd.f_off[LF_L0 + l + 1], nt0, L, ring);
+    bias_fetch<2>(bn, P + a.L.b_off[l == 3 ? 5 : l + 1], nt0, L);
     l16_epi<true, 2>(acc, out, nt0, arr(L16A_Z0 + A * l), A, wg, L);
     wg_barrier();
   }
   // feature_linear1 (linear): R1 -> R0, also the first 16 k-steps of the [f1 | x_pos] stash
-  l16_bias_apply<2>(acc, bn);
-  lmma<A, l16_tot(A), 2, kNT>(acc, R1, (wptr_t)pd.f_off[LF_F1], kNoW, nt0, L, ring);
-  lring_fill<1, kNT / 2>(ringp, (wptr_t)pd.f_off[LF_POS], L.wave, L.lane);
-  l16_bias_fetch<1>(bnp, P + a.L.b_off[4], L.wave, L);
+  bias_apply<2>(acc, bn);
+  mma_ring<0, l16_tot(A), A, l16_tot(A), 2, kNT>(acc, R1, 0, (wptr_t)pd.f_off[LF_F1], kNoW, nt0, L, ring);
+  wring_fill<1, kNT / 2>(ringp, (wptr_t)pd.f_off[LF_POS], L.wave, L.lane);
+  bias_fetch<1>(bnp, P + a.L.b_off[4], L.wave, L);
   l16_epi<false, 2>(acc, R0, nt0, arr(L16A_HP), kL16KsHp, wg, L);
   wg_barrier();
   // pos_linears.0: [f1 (R0) | x_pos (RX)] -> 128, snake; one neuron tile per wave
   f32x16 accp[1][kNB];
   constexpr wptr_t UP = (kNT / 2) * 64;
-  l16_bias_apply<1>(accp, bnp);
-  lmma<A, l16_tot(A), 1, kNT / 2>(accp, R0, (wptr_t)pd.f_off[LF_POS], (wptr_t)pd.f_off[LF_POS] + A * UP, L.wave, L, ringp);
-  lmma<4, l16_tot(4), 1, kNT / 2>(accp, RX, (wptr_t)pd.f_off[LF_POS] + A * UP, kNoW, L.wave, L, ringp);
+  bias_apply<1>(accp, bnp);
+  mma_ring<0, l16_tot(A), A, l16_tot(A), 1, kNT / 2>(accp, R0, 0, (wptr_t)pd.f_off[LF_POS], (wptr_t)pd.f_off[LF_POS] + A * UP, L.wave, L, ringp);
+  mma_ring<0, l16_tot(4), 4, l16_tot(4), 1, kNT / 2>(accp, RX, 0, (wptr_t)pd.f_off[LF_POS] + A * UP, kNoW, L.wave, L, ringp);
   l16_epi<true, 1>(accp, nullptr, L.wave, arr(L16A_ZP), kLPosOut / 16, wg, L);
   // rgb_linear 128 -> 3 + sigmoid (models/helpers.py:55-56): per-lane partial dot over its 16 neurons, lane halves by shuffle,
   // the four waves through LDS
@@ -407,49 +331,6 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_fwd_kernel(L16Args a, 
 }
 
 // ---- backward (data gradients) ------------------------------------------------------------------------------------------------
-struct L16ZPre { f16x8 z[2][kNB][2]; };
-__device__ __forceinline__ void l16_zfetch(L16ZPre& zp, const char* z_array, int wg, int kt0, const Lane& L) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int bt = 0; bt < kNB; ++bt)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) zp.z[t][bt][s] = *(const f16x8*)(z_array + wfmt_unit(kKSAct, wg, 2 * (kt0 + t) + s, bt, L.b, L.h));
-}
-template <bool DERIV>
-__device__ __forceinline__ void l16_bepi(f32x16 (&acc)[2][kNB], char* out, const L16ZPre* zp, char* dz_array, int wg, int kt0, const Lane& L) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int ntg = kt0 + t;
-#pragma unroll
-    for (int bt = 0; bt < kNB; ++bt) {
-      f32x16 g = acc[t][bt];
-      if (DERIV) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const f16x8 zf = zp->z[t][bt][s];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) g[8 * s + j] *= 1.0f + __builtin_amdgcn_sinf((float)zf[j] * (2.0f * kInv2Pi));     // activations.py:29-35: 1 + sin 2z
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const bf16x8 f = pack_acc(g, s);
-        if (out) lds_store_frag(out, 2 * ntg + s, bt, L.lane, f);
-        dz_store(dz_array + wfmt_unit(kKSAct, wg, 2 * ntg + s, bt, L.b, L.h), f);
-      }
-    }
-  }
-}
-__device__ __forceinline__ void l16_zero(f32x16 (&acc)[2][kNB]) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int bt = 0; bt < kNB; ++bt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][bt][r] = 0.0f;
-}
-
 __global__ __launch_bounds__(kL16Threads, 2) void light16_bwd_kernel(L16Args a, L16Pack pd, int n_wg, int C) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* R0 = smem;
@@ -474,9 +355,9 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_bwd_kernel(L16Args a, 
   auto dzr = [&](int ks_off) { return dzF + wfmt_array_base(ks_off, L.n_wg); };
 
   // everything the prologue needs from memory first: the weight ring of the first data-gradient part, rgb_linear's rows, z_p
-  LRing<2> ring;
+  WRing<2> ring;
   ring.rsrc = make_wrsrc(a.pack + (int64_t)c * a.pack_stride16, pd.total);
-  lring_fill<2, kNT>(ring, (wptr_t)pd.b_off[LB_POS], kt0, L.lane);
+  wring_fill<2, kNT>(ring, (wptr_t)pd.b_off[LB_POS], kt0, L.lane);
   f16x8 zp_pre[kNB][2];
 #pragma unroll
   for (int bt = 0; bt < kNB; ++bt)
@@ -531,12 +412,12 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_bwd_kernel(L16Args a, 
   wg_barrier();
 
   f32x16 acc[2][kNB];
-  L16ZPre zpre;
+  ZPre<false> zpre;
   constexpr int KP = kLPosOut / 16, A = kKSAct;
   // d f1 = W_pos[:, :256]^T d z_p  (feature_linear1 is linear: this IS its d z; x_pos gets no gradient): R0 -> R1
-  l16_zero(acc);
-  lmma<KP, l16_tot(KP), 2, kNT>(acc, R0, (wptr_t)pd.b_off[LB_POS], (wptr_t)pd.b_off[LB_F1], kt0, L, ring);
-  l16_bepi<false>(acc, R1, nullptr, dzr(L16D_F1), wg, kt0, L);
+  zero_acc(acc);
+  mma_ring<0, l16_tot(KP), KP, l16_tot(KP), 2, kNT>(acc, R0, 0, (wptr_t)pd.b_off[LB_POS], (wptr_t)pd.b_off[LB_F1], kt0, L, ring);
+  bwd_epilogue<false, false>(acc, R1, nullptr, dzr(L16D_F1), wg, kt0, L);
   wg_barrier();
   // d z_3 = (W_f1^T d f1) * snake'(z_3), d z_2 = (W_3^T d z_3) * snake'(z_2), ..., d z_0: R1 -> R0 -> R1 -> R0
 #pragma unroll
@@ -544,10 +425,10 @@ __global__ __launch_bounds__(kL16Threads, 2) void light16_bwd_kernel(L16Args a, 
     const int l = 3 - j;                           // hidden layer whose d z this step produces
     char* in = (j & 1) ? R0 : R1;
     char* out = (j & 1) ? R1 : R0;
-    l16_zero(acc);
-    l16_zfetch(zpre, zs(L16A_Z0 + A * l), wg, kt0, L);
-    lmma<A, l16_tot(A), 2, kNT>(acc, in, (wptr_t)pd.b_off[LB_F1 + j], j == 3 ? kNoW : (wptr_t)pd.b_off[LB_F1 + j + 1], kt0, L, ring);
-    l16_bepi<true>(acc, j == 3 ? nullptr : out, &zpre, dzr(L16D_Z0 + A * l), wg, kt0, L);
+    zero_acc(acc);
+    z_prefetch(zpre, zs(L16A_Z0 + A * l), wg, kt0, L);
+    mma_ring<0, l16_tot(A), A, l16_tot(A), 2, kNT>(acc, in, 0, (wptr_t)pd.b_off[LB_F1 + j], j == 3 ? kNoW : (wptr_t)pd.b_off[LB_F1 + j + 1], kt0, L, ring);
+    bwd_epilogue<true, false>(acc, j == 3 ? nullptr : out, &zpre, dzr(L16D_Z0 + A * l), wg, kt0, L);
     if (j != 3) wg_barrier();
   }
 }

@@ -4,7 +4,8 @@
 #pragma once
 #include <math.h>
 
-#include "npp_common.h"
+#include "npp_adam.h"
+#include "npp_robust.h"
 #include "npp_light_layout.h"
 
 namespace npp {
@@ -43,7 +44,7 @@ struct LightLossArgs {
 // Head of a backward chain, whole workgroup (THREADS threads own ROWS pixel rows of candidate c from row0 on; the block is number `slot` of
 // the candidate's n_slots): d raw = d pred * pred (1 - pred) for thread tid's element (row tid / 3, channel tid % 3) goes to
 // store(g, d raw), g = the element's index in (C, B, 3).  With the pixel loss folded in (lo.gt): d pred = d img2mse(robust_loss_adaptive)
-// / d pred right here (models/mse_calculator.py:13-27 without a mask: the arithmetic of pixel_loss_body, npp_common.h); the loss and
+// / d pred right here (models/mse_calculator.py:13-27 without a mask: the arithmetic of pixel_loss_body, npp_robust.h); the loss and
 // the latent gradients by atomics, or (lo.part) per block in a fixed order.  Ends behind a workgroup barrier that follows every store().
 template <int THREADS, int ROWS, class Store>
 __device__ __forceinline__ void light_loss_head(const LightLossArgs& lo, const float* __restrict__ pred, const float* __restrict__ dpred, int c,
@@ -118,10 +119,10 @@ __device__ __forceinline__ void light_loss_head(const LightLossArgs& lo, const f
 // ---- the latent column of the Adam launches (blockIdx.x == gridDim.x - 1) -----------------------------------------------------------------
 struct LightLatentArgs {
   float *lat, *lat_m, *lat_v, *dlat, *zero;               // (C, 6) x 4, (C)
-  float step_size, b1, b2, inv_sqrt_bc2, eps;             // torch.optim.Adam's single-tensor maths (adam_update, npp_common.h): the weights' too
+  float step_size, b1, b2, inv_sqrt_bc2, eps;             // torch.optim.Adam's single-tensor maths (adam_update, npp_adam.h): the weights' too
   const float* part; int32_t n_part; float* loss_cur;     // the _det forms: the blocks' partial sums of light_loss_head, added here in block order
 };
-// Adam's step-dependent scalars: adam_words (npp_common.h), as in npp_adam_step
+// Adam's step-dependent scalars: adam_words (npp_adam.h), as in npp_adam_step
 static inline LightLatentArgs light_latent_args(float* d_lat, float* d_lat_m, float* d_lat_v, float* d_dlat, float* d_zero, float lr, float beta1,
                                          float beta2, float eps, int step, const float* d_part, int n_part, float* d_loss_cur) {
   const AdamWords w = adam_words(lr, beta1, beta2, step);

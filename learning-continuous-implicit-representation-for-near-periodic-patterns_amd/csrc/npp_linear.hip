@@ -17,7 +17,7 @@
 // all 37 -- LDS traffic (stores ~190 + reads ~250-500 array cycles per workgroup-chunk) and the MFMA pipe (1024 cycles per
 // wave-chunk) add up rather than overlap; a 64 x 64 tile per WAVE with the contraction split over the waves would halve the
 // LDS reads at the price of a cross-wave reduction (not built: estimated 37 -> 31 us).
-#include "npp_common.h"
+#include "npp_robust.h"
 #include "npp_light_layout.h"
 
 namespace npp {

@@ -9,11 +9,12 @@
 //   beta = 2-alpha, u = (x/c)^2/beta + 1, e = alpha/2
 //   d rho/dx = x/c^2 u^(e-1) ; d rho/dc = -x^2/c^3 u^(e-1) ;
 //   d rho/da = -(2/a^2)(u^e - 1) + (beta/a) u^e (ln(u)/2 + e (x/c)^2/(beta^2 u))
-#include "npp_common.h"
+#include "npp_adam.h"
+#include "npp_robust.h"
 
 namespace npp {
 
-// (body: pixel_loss_body in npp_common.h -- shared with the fused patch-in launch of npp_conv.hip)
+// (body: pixel_loss_body in npp_robust.h -- shared with the fused patch-in launch of npp_conv.hip)
 __global__ __launch_bounds__(256) void pixel_loss_kernel(PixelLossArgs a) { pixel_loss_body(a, (int)blockIdx.x, (int)gridDim.x); }
 // nbatch independent losses in one launch (blockIdx.y): predictions / gradients (N,3) back to back, 6 latents and one loss word
 // per problem; the targets are shared when gt_stride == 0.
@@ -32,10 +33,10 @@ __global__ __launch_bounds__(256) void pixel_loss_batched_kernel(PixelLossArgs a
 // tail (optional, handled by one extra block): a second small parameter group -- the adaptive-loss
 // latents, whose gradient accumulator is consumed and cleared -- and an accumulator to clear for the
 // next iteration, so that one launch replaces optimizer.step() over both groups plus zero_grad().
-// (AdamTail, adam_tail_block: npp_common.h -- shared with the fused Adam + re-pack launch of npp_api.hip)
+// (AdamTail, adam_tail_block: npp_adam.h -- shared with the fused Adam + re-pack launch of npp_api.hip)
 // VEC = 4: one float4 per thread and array (slab_stride a multiple of 4, 16-byte aligned pointers; the last n % 4 elements go
 // one by one), four slab loads in flight before the order-preserving summation: the kernel is a pure HBM stream of
-// (n_slabs + 5) * 4 B per parameter.  VEC = 1: an element per thread.  (adam_quad, slab_sum: npp_common.h)
+// (n_slabs + 5) * 4 B per parameter.  VEC = 1: an element per thread.  (adam_quad, slab_sum: npp_adam.h)
 template <int VEC>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ m,
                                                    float* __restrict__ v, const float* __restrict__ g,

@@ -8,7 +8,7 @@
 // dropout inactive in eval) -> spatial_average (:16-17) -> sum over taps; the caller's
 // torch.mean over the batch (NPP_completion/train.py:249) is folded into `scale`.
 // Backward: d/d feats0 (through the channel normalisation) and d/d latents (per channel).
-#include "npp_common.h"
+#include "npp_robust.h"
 #include "npp_trunk_layout.h"
 
 namespace npp {

@@ -11,7 +11,7 @@
 // the accumulator tile of one layer reused, after x snake'(z) and conversion to bf16, as
 // the B operand of the next.  snake'(z) = 1 + sin 2z is derived from the fp16 pre-activation
 // fragments the forward kernel stashed (one 16-byte load per lane per fragment).
-#include "npp_common.h"
+#include "npp_chain16.h"
 
 namespace npp {
 
@@ -46,70 +46,8 @@ struct BwdArgs {
   int64_t crop_stride, cmask_stride, dxb_stride;   // floats per image: rgb crops [fake | real], mask crops, LPIPS gradient
 };
 
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][kNB]) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int bt = 0; bt < kNB; ++bt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][bt][r] = 0.0f;
-}
-
-// The z fragments a layer's epilogue needs (stash, cold in HBM), fetched BEFORE the layer's MFMA loop so that their
-// latency is covered by it instead of stalling every epilogue (32 VGPRs).
-// S8 (stash8): the forward left snake'(z) itself, one unsigned byte per element in the W8-format (npp_common.h kSd8Scale): 8-byte
-// units, no sine here
-template <bool S8> struct ZPre { f16x8 z[2][kNB][2]; };
-template <> struct ZPre<true> { u32x2 z[2][kNB][2]; };
-template <bool S8>
-__device__ __forceinline__ void z_prefetch(ZPre<S8>& zp, const char* z_array, int wg, int kt0, const Lane& L) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int bt = 0; bt < kNB; ++bt)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        if constexpr (S8) zp.z[t][bt][s] = *(const u32x2*)(z_array + wfmt8_unit(kKSAct, wg, 2 * (kt0 + t) + s, 32 * bt + L.b, L.h));
-        else zp.z[t][bt][s] = *(const f16x8*)(z_array + wfmt_unit(kKSAct, wg, 2 * (kt0 + t) + s, bt, L.b, L.h));
-      }
-}
-
-// dz = acc (x stashed snake derivative); fragments -> LDS for the next dgrad, rows -> dzT.
-template <bool HAS_S, bool S8>
-__device__ __forceinline__ void bwd_epilogue(f32x16 (&acc)[2][kNB], char* out, const ZPre<S8>* zp, char* dz_array,
-                                             int wg, int kt0, const Lane& L) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int ntg = kt0 + t;
-#pragma unroll
-    for (int bt = 0; bt < kNB; ++bt) {
-      f32x16 g = acc[t][bt];
-      if (HAS_S) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          if constexpr (S8) {
-            const u32x2 sd = zp->z[t][bt][s];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) g[8 * s + j] *= u8_byte_f32(sd[j >> 2], j & 3) * kSd8Inv;
-          } else {
-            const f16x8 zf = zp->z[t][bt][s];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)      // snake'(z) = 1 + sin 2z  (activations.py:29-35)
-              g[8 * s + j] *= 1.0f + __builtin_amdgcn_sinf((float)zf[j] * (2.0f * kInv2Pi));
-          }
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const bf16x8 f = pack_acc(g, s);
-        if (out) lds_store_frag(out, 2 * ntg + s, bt, L.lane, f);
-        if (S8) stash8_store(dz_array + wfmt8_unit(kKSAct, wg, 2 * ntg + s, 32 * bt + L.b, L.h), pack8_bf8_acc(g, s));
-        else dz_store(dz_array + wfmt_unit(kKSAct, wg, 2 * ntg + s, bt, L.b, L.h), f);
-      }
-    }
-  }
-}
-
+// (zero_acc, ZPre / z_prefetch and bwd_epilogue -- the data-gradient accumulators, the prefetched z fragments and dz = acc x
+// snake'(z) -> LDS fragments + stash -- are npp_chain16.h's: npp_light16.hip runs the same ones)
 // S8 (npp_tune "stash8"): the gradients leave as bf8 in the W8-format (npp_layout.h).  The whole chain is linear in dL/draw, so the
 // workgroup runs it on dL/draw * 2^(kDz8Lift - e), e = floor(log2 max |dL/draw|) over its 64 rows: the stored bytes then sit in
 // bf8's range whatever the loss normalisation is, and the E8M0 byte of 2^(e - kDz8Lift) goes to the tile's scale word, which

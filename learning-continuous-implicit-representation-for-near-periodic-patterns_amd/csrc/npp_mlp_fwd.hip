@@ -26,6 +26,7 @@
 //
 // Algorithmic work: 2 * ((K+1)*462*256 + 11*256^2 + 384) FLOP per row;
 // the zero padding of 462 -> 480 slots per proposal is not counted.
+#include "npp_chain16.h"
 #include "npp_coord.h"
 #include <cstring>
 
@@ -75,7 +76,7 @@ constexpr bool kM16 = NPP_FWD_MFMA16 != 0;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // neuron (within the wave's 32-neuron tile) of accumulator element idx for this lane
 __device__ __forceinline__ int acc_nrow(int idx, const Lane& L) {
-  return kM16 ? 16 * (idx >> 3) + 4 * (L.lane >> 4) + (idx & 3) : acc_row(idx, L.h);
+  return acc_row_map<kM16>(idx, L);
 }
 constexpr int kWavesF = NPP_FWD_WAVES;
 constexpr int kNTW = kNT / kWavesF;                             // neuron tiles per wave in 256-wide layers
@@ -127,43 +128,11 @@ struct EmbTabs {
   int64_t emb_ld;
 };
 
-// acc[nt][bt] <- bias of this wave's neuron tiles (row constants as the initial accumulator)
-template <int NTW>
-__device__ __forceinline__ void init_bias(f32x16 (&acc)[NTW][kNB], const float* __restrict__ bias, int nt0,
-                                          const Lane& L) {
-#pragma unroll
-  for (int nt = 0; nt < NTW; ++nt) {
-    f32x16 bv;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) bv[r] = bias[(nt0 + nt) * 32 + acc_nrow(r, L)];
-#pragma unroll
-    for (int bt = 0; bt < kNB; ++bt) acc[nt][bt] = bv;
-  }
-}
-
-// The same in two halves: the NEXT layer's bias values are fetched before the current layer's epilogue (their L2 latency
-// hides under it and the barrier) and moved into the accumulators where init_bias used to load them.
-template <int NTW> struct BiasPre { float v[NTW][16]; };
-template <int NTW>
-__device__ __forceinline__ void bias_fetch(BiasPre<NTW>& bp, const float* __restrict__ bias, int nt0, const Lane& L) {
-#pragma unroll
-  for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) bp.v[nt][r] = bias[(nt0 + nt) * 32 + acc_nrow(r, L)];
-}
-template <int NTW>
-__device__ __forceinline__ void bias_apply(f32x16 (&acc)[NTW][kNB], const BiasPre<NTW>& bp) {
-#pragma unroll
-  for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-    for (int bt = 0; bt < kNB; ++bt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[nt][bt][r] = bp.v[nt][r];
-}
+// (init_bias, BiasPre / bias_fetch / bias_apply: npp_chain16.h, with this file's accumulator row map -- <NTW, kM16>)
 
 // The 22 warped coordinates (a1, models/embedder.py:110-133) of proposal p for the 64 rows ->
 // sV[i][row] (fp32).  Table-driven: wave w takes i = w, w+4, ...; the entry is wave-uniform.
-// ---- 16x16x32 form of the weight ring and of mma_ring (npp_common.h holds the 32x32x16 originals, which the backward chain uses)
+// ---- 16x16x32 form of the weight ring and of mma_ring (npp_chain16.h holds the 32x32x16 originals, which the backward chain uses)
 // The ring keeps its 4 k-steps x NTW fragments of storage; fragment (k-step pair KB, 16-neuron tile mt) lives in
 // w[2 (KB & 1) + (mt & 1)][mt >> 1] and is ONE buffer load that gathers 4 runs of 16 slots from the pack's k-steps 2 KB, 2 KB + 1.
 template <int NTW, int NT>
@@ -564,7 +533,7 @@ __device__ __forceinline__ void slot_from_halves(const float (&lo)[4], const flo
 
 // TRAIN: 0 inference, 1 the 16-bit stash, 2 (npp_tune "stash8") two W8 arrays per layer instead: the layer's output (snake(z) or
 // the linear output) as fp8 units in `stash8_array` -- what npp_mlp_wgrad8 contracts -- and, for a snake layer, snake'(z) = 1 +
-// sin 2z as unsigned bytes (npp_common.h kSd8Scale) in `stash_array` -- what npp_mlp_bwd multiplies by: 2 bytes per element
+// sin 2z as unsigned bytes (npp_chain16.h kSd8Scale) in `stash_array` -- what npp_mlp_bwd multiplies by: 2 bytes per element
 // where the 16-bit stash writes the 2-byte fp16 z that both consumers re-derive from
 __device__ __forceinline__ uint32_t pack4_fp8(const float (&v)[4]) {
   int x = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
@@ -771,11 +740,11 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
   }
   // ---- L0: emb(p0) -> 256, snake.  LDS ring = R1, out -> R0
   WRING_FILL(kNTW, kNT, ring, wl(L0), nt0, L);
-  init_bias<kNTW>(acc, P + d.b_off[L0], nt0, L);
+  init_bias<kNTW, kM16>(acc, P + d.b_off[L0], nt0, L);
   mma_embedding<TRAIN, kNTW, kNT, EMB_IN>(acc, e, 0, R1, sV, sY, sX, wl(L0), wl(L1), nt0, s_actE, wg, L, ring);
   BiasPre<kNTW> bn;
   BiasPre<1> bnp;
-  bias_fetch<kNTW>(bn, P + d.b_off[L1], nt0, L);
+  bias_fetch<kNTW, kM16>(bn, P + d.b_off[L1], nt0, L);
   epilogue<true, TRAIN, kNTW>(acc, R0, nt0, kNT, arow(0), wg, L, nullptr, arow8(0));
   wg_barrier();
 
@@ -786,7 +755,7 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
     char* out = (l & 1) ? R1 : R0;
     bias_apply<kNTW>(acc, bn);
     MMA_RING<0, A, A, A, kNTW, kNT>(acc, in, 0, wl(l), (l == L4 && !EMB_IN && kOverlapPro) ? wl(L5) + kKSEmb * U : wl(l + 1), nt0, L, ring);
-    bias_fetch<kNTW>(bn, P + d.b_off[l + 1], nt0, L);
+    bias_fetch<kNTW, kM16>(bn, P + d.b_off[l + 1], nt0, L);
     epilogue<true, TRAIN, kNTW>(acc, out, nt0, kNT, arow(l), wg, L, nullptr, arow8(l));
     wg_barrier();
   }
@@ -804,19 +773,19 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
     mma_embedding<0, kNTW, kNT, EMB_IN>(acc, e, 0, R1, sV, sY, sX, wl(L5), wl(L5) + kKSEmb * U, nt0, s_actF, wg, L, ring);
     MMA_RING<0, A, A, A, kNTW, kNT>(acc, R0, 0, wl(L5) + kKSEmb * U, wl(L6), nt0, L, ring);
   }
-  bias_fetch<kNTW>(bn, P + d.b_off[L6], nt0, L);
+  bias_fetch<kNTW, kM16>(bn, P + d.b_off[L6], nt0, L);
   epilogue<true, TRAIN, kNTW>(acc, R1, nt0, kNT, arow(5), wg, L, nullptr, arow8(5));
   wg_barrier();
 
   // ---- L6: R1 -> R0, L7: R0 -> R1
   bias_apply<kNTW>(acc, bn);
   MMA_RING<0, A, A, A, kNTW, kNT>(acc, R1, 0, wl(L6), wl(L7), nt0, L, ring);
-  bias_fetch<kNTW>(bn, P + d.b_off[L7], nt0, L);
+  bias_fetch<kNTW, kM16>(bn, P + d.b_off[L7], nt0, L);
   epilogue<true, TRAIN, kNTW>(acc, R0, nt0, kNT, arow(6), wg, L, nullptr, arow8(6));
   wg_barrier();
   bias_apply<kNTW>(acc, bn);
   MMA_RING<0, A, A, A, kNTW, kNT>(acc, R0, 0, wl(L7), wl(LF1), nt0, L, ring);
-  bias_fetch<kNTW>(bn, P + d.b_off[LF1], nt0, L);
+  bias_fetch<kNTW, kM16>(bn, P + d.b_off[LF1], nt0, L);
   epilogue<true, TRAIN, kNTW>(acc, R1, nt0, kNT, arow(7), wg, L, nullptr, arow8(7));
   wg_barrier();
 
@@ -826,8 +795,8 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
   MMA_RING<0, A, A, A, kNTW, kNT>(acc, R1, 0, wl(LF1), MULTI ? wl(LS) : kNoW, nt0, L, ring);
   const bool p_wave = L.wave < kNT / 2;            // P has 4 neuron tiles: with 8 waves the upper four only keep the barriers
   if (!MULTI && p_wave) WRING_FILL(1, kNT / 2, ringp, wl(LP), L.wave, L);
-  if (MULTI) bias_fetch<kNTW>(bn, P + d.b_off[LS], nt0, L);
-  else if (p_wave) bias_fetch<1>(bnp, P + d.b_off[LP], L.wave, L);
+  if (MULTI) bias_fetch<kNTW, kM16>(bn, P + d.b_off[LS], nt0, L);
+  else if (p_wave) bias_fetch<1, kM16>(bnp, P + d.b_off[LP], L.wave, L);
   epilogue<false, TRAIN, kNTW>(acc, R0, nt0, kNT, arow(kActF1), wg, L, nullptr, arow8(kActF1));
   wg_barrier();
 
@@ -853,7 +822,7 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
                                    /*next_warp_p=*/(kOverlapPro && p + 1 < d.K) ? p + 1 : -1);
     }
     WRING_FILL(kNTW, kNT, ring, wl(LF2), nt0, L);        // flies under the epilogue
-    bias_fetch<kNTW>(bn, P + d.b_off[LF2], nt0, L);
+    bias_fetch<kNTW, kM16>(bn, P + d.b_off[LF2], nt0, L);
     epilogue<true, TRAIN, kNTW>(acc, R1, nt0, kNT, arow(kActAS), wg, L, nullptr, arow8(kActAS));
     wg_barrier();
     // ---- F2 = feature_linear2 (linear): R1 -> R0
@@ -861,7 +830,7 @@ __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdAr
     MMA_RING<0, A, A, A, kNTW, kNT>(acc, R1, 0, wl(LF2), kNoW, nt0, L, ring);
     if (p_wave) {
       WRING_FILL(1, kNT / 2, ringp, wl(LP), L.wave, L);
-      bias_fetch<1>(bnp, P + d.b_off[LP], L.wave, L);
+      bias_fetch<1, kM16>(bnp, P + d.b_off[LP], L.wave, L);
     }
     // P needs f1 again, and this epilogue recycles its region: the wave takes ITS f1 fragments (the only ones its own f2 stores
     // overwrite) out of R0 first and hands them back through R1 after the barrier -- live across one epilogue, not across S and F2

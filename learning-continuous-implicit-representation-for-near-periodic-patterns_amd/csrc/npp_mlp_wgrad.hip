@@ -27,7 +27,7 @@
 //
 // Algorithmic work: 2 * sum_l n_out*n_in FLOP per batch row (embedding pad slots and the
 // padding of the 3-row rgb job are not counted).
-#include "npp_common.h"
+#include "npp_chain16.h"
 #include "npp_light_layout.h"
 #include <stdlib.h>
 #include <type_traits>

@@ -1,5 +1,5 @@
 """Every form of the Adam step on the same inputs, compared as BITS (torch.equal, no tolerance): the update, the slab sum and the
-host's scalar rule are each written once (csrc/npp_common.h: adam_update, slab_sum / adam_quad, adam_words), and the
+host's scalar rule are each written once (csrc/npp_adam.h: adam_update, slab_sum / adam_quad, adam_words), and the
 forms below are what calls them -- the flat blob forms (argument, device-word, with the latent tail; vector and scalar kernel),
 the fused Adam + re-pack launch (argument, device-word, against Adam followed by pack), its stacked form, and the latent group
 of the patch losses (losses.LatentGroup).

@@ -28,8 +28,10 @@ def rel_l2(a, b):
 def _pair(dev, C, H=96, seed=11):
     from npp_amd.light import NPPNetLightBatch, default_light_init
     rng = np.random.RandomState(seed)
-    angles = np.array([[0.0, 90.0], [30.0, 120.0], [10.0, 80.0], [45.0, 135.0], [5.0, 95.0]], np.float32)[:C]
-    periods = np.array([[12.0, 9.0], [7.0, 15.0], [20.0, 6.0], [11.0, 11.0], [16.0, 8.0]], np.float32)[:C]
+    angles = np.array([[0.0, 90.0], [30.0, 120.0], [10.0, 80.0], [45.0, 135.0], [5.0, 95.0],
+                       [20.0, 110.0], [60.0, 150.0], [15.0, 100.0], [35.0, 125.0]], np.float32)[:C]
+    periods = np.array([[12.0, 9.0], [7.0, 15.0], [20.0, 6.0], [11.0, 11.0], [16.0, 8.0],
+                        [9.0, 13.0], [14.0, 10.0], [8.0, 18.0], [17.0, 7.0]], np.float32)[:C]
     freqs = (rng.randn(10) * 10).astype(np.float32)
     init = default_light_init(256, 4)
     cands = [(angles[i], periods[i]) for i in range(C)]
@@ -39,10 +41,12 @@ def _pair(dev, C, H=96, seed=11):
     return n32, n16, rng
 
 
-@pytest.mark.parametrize("C,B", [(3, 256), (5, 64), (1, 2048)])
+@pytest.mark.parametrize("C,B", [(3, 256), (5, 64), (1, 2048), (1, 64), (9, 128)])
 def test_bf16_chains_vs_fp32_chains_one_step(dev, C, B):
     """Same weights, same rows: predictions, the loss words, every weight / bias gradient of every candidate (the split-K slabs summed),
-    and the packs after the Adam launch against a fresh pack of the updated master weights."""
+    and the packs after the Adam launch against a fresh pack of the updated master weights.  (1, 64): one work item, the seven surplus
+    workgroups of the grid leave before any barrier; (9, 128): 18 items on a grid of 24, three per XCD with an uneven last XCD -- the
+    smallest shapes at which the candidate-contiguous XCD numbering and the ring's hand-over to "no next part" can go wrong."""
     from npp_amd import ops
     H = 96
     n32, n16, rng = _pair(dev, C, H)

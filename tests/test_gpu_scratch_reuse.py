@@ -610,7 +610,7 @@ def test_pixel_loss_partials_into_the_adam_tail_at_changing_row_counts(dev):
     nets = {False: mk(), True: mk()}
     assert ops.DETERMINISTIC and nets[False].fused_repack
     shapes = [2048, 26624, 2048, 256, 2048, 26624, 256, 2048, 26624]
-    blocks = lambda n: min(1024, (n + 255) // 256)               # noqa: E731  pixel_loss_blocks (csrc/npp_common.h)
+    blocks = lambda n: min(1024, (n + 255) // 256)               # noqa: E731  pixel_loss_blocks (csrc/npp_robust.h)
     assert [blocks(n) for n in shapes[:5]] == [8, 104, 8, 1, 8]
     sc, sh = [1 / 0.229, 1 / 0.224, 1 / 0.225], [-0.485 / 0.229, -0.456 / 0.224, -0.406 / 0.225]
     beta1 = float(np.float32(1.0) - np.float32(0.9))             # the kernel's (1.0f - b1)

@@ -86,7 +86,7 @@ _WORD_STEPS = tuple(range(1, 3001)) + (10000, 50000)
 
 @pytest.mark.parametrize("width", npp_amd.FUSED_WIDTHS)
 def test_adam_words_equal_the_librarys_rule_as_bits(width):
-    """ops.adam_words is the Python statement of the one C rule (adam_words in csrc/npp_common.h, exported as npp_adam_words, which
+    """ops.adam_words is the Python statement of the one C rule (adam_words in csrc/npp_adam.h, exported as npp_adam_words, which
     every argument-form Adam entry calls): equal as bits over the fits' whole step range, in both libraries."""
     import ctypes
     L = npp_amd.lib(width)
