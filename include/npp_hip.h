@@ -1187,6 +1187,27 @@ int npp_warp_image_u8(const uint8_t* d_src, int Hs, int Ws, int C, int Ho, int W
                       uint8_t* d_inside, void* stream);
 int npp_warp_image_u8_host(const uint8_t* src, int Hs, int Ws, int C, int Ho, int Wo, const double m[9], int mode, uint8_t* out,
                            uint8_t* inside);
+/* The antialiased warp: ss x ss samples per canvas pixel, ss in {1, 2, 4, 8}, reduced in the launch.  Sample s = a ss + b
+ * (a, b = 0 .. ss - 1) of canvas pixel (i, j) sits at the canvas position (i + off[a], j + off[b]), off[a] = (2 a + 1) / (2 ss) - 0.5
+ * in float64 (the offset and the sum are exact), and goes through the map as above: d, y, x in the written order, every product and
+ * sum rounded separately.  Its value v_s (float64) is, in mode 1, the UNROUNDED blend v of above (before floor(v + 0.5)) and, in
+ * mode 0, the tapped byte as a double.  A sample COUNTS iff it is in the source by its mode's test above.
+ * reduce 0, mean: acc = +0.0; for s = 0 .. ss^2 - 1 in this order acc = acc + v_s for each sample that counts (one rounded add each);
+ *   the byte is floor(acc / cnt + 0.5) clamped to [0, 255], cnt the number of samples that count, one IEEE quotient.
+ * reduce 1, min: the smallest v_s over the samples that count, then the same floor(. + 0.5) and clamp (for masks: a canvas pixel is
+ *   as white as its darkest sample).
+ * inside is 255 iff the pixel CENTRE is in the source (the test above at (i, j)) AND at least one sample counts; otherwise every
+ * channel is 0 and inside is 0 -- a pixel whose centre is outside stays empty even when some of its samples count.  Two consequences
+ * of "a sample that is not in the source does not count": under bilinear the outermost canvas pixels of an identity-like map average
+ * only their inward samples, and a source one pixel high (or wide) yields no bilinear sample at ss > 1 (every offset is a fraction,
+ * and 0 <= y <= Hs - 1 = 0 admits none).  ss = 1: off = 0 and acc = 0 + v, so either reduce is npp_warp_image_u8 byte for byte.
+ * One thread per canvas pixel loops over its samples in order: no atomics, no state between calls, the result does not depend on
+ * the launch geometry.  Arguments as above, and ss outside {1, 2, 4, 8} or reduce outside {0, 1}: NPP_ERR_ARG and a message that
+ * names the argument, nothing launched.  Not built: other filters (Lanczos, EWA), other ss, a per-pixel adaptive ss, float images. */
+int npp_warp_image_u8_ss(const uint8_t* d_src, int Hs, int Ws, int C, int Ho, int Wo, const double m[9], int mode, int ss, int reduce,
+                         uint8_t* d_out, uint8_t* d_inside, void* stream);
+int npp_warp_image_u8_ss_host(const uint8_t* src, int Hs, int Ws, int C, int Ho, int Wo, const double m[9], int mode, int ss, int reduce,
+                              uint8_t* out, uint8_t* inside);
 
 /* ---- quality report: SSIM and region-wise PSNR / MAE of an image against a ground truth (metrics.py) ------------------------- */
 /* Both images are (H, W, 3) fp32 in [0, 1], read as they lie; all arithmetic and every output is float64.  No entry keeps state in

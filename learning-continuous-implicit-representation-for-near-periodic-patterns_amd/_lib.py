@@ -223,6 +223,8 @@ SYMBOLS = {
     "npp_far_points": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "npp_warp_image_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _i32, _vp, _vp, _vp]),
     "npp_warp_image_u8_host": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _i32, _vp, _vp]),
+    "npp_warp_image_u8_ss": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _i32, _i32, _i32, _vp, _vp, _vp]),
+    "npp_warp_image_u8_ss_host": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _i32, _i32, _i32, _vp, _vp]),
     "npp_ssim_map": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "npp_region_sums_blocks": (_i32, [_i32, _i32]),
     "npp_region_sums": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),

@@ -2,7 +2,8 @@
 // coverage mask, and the host twins of the view rule.  The warp's positions and bilinear blend are float64 in the operation order
 // include/npp_hip.h writes down, every product and sum rounded separately: one function body serves the kernel (spelt __d*_rn) and
 // the host twin (plain operators; the file is built with -ffp-contract=off and the pragma holds it without the flag), so NumPy, the
-// host and the device agree bit for bit.  One thread per canvas pixel, all channels; no atomics, no state between calls.
+// host and the device agree bit for bit.  One thread per canvas pixel, all channels; no atomics, no state between calls.  The
+// antialiased warp (npp_warp_image_u8_ss) is the same thread looping over its pixel's ss x ss samples in the rule's order.
 #include "npp_coord.h"
 
 namespace npp {
@@ -56,12 +57,113 @@ __host__ __device__ __forceinline__ void warp_pixel(const uint8_t* __restrict__ 
   if (inside) *inside = in ? 255 : 0;
 }
 
+// ---- ss x ss samples per canvas pixel (include/npp_hip.h npp_warp_image_u8_ss) -----------------------------------------------------
+// warp_pixel's rule taken apart for a loop over samples: the position and its taps once per sample (warp_tap), the unrounded value
+// per channel (warp_value), the rounding once per pixel (warp_byte).  warp_pixel itself stays as it was written, so that the point
+// kernel's code is instruction for instruction what it was; ss = 1 through these gives its bytes.
+
+// One canvas position (fi, fj) under the map: whether it is in the source by its mode's test, where its taps lie (byte offsets of
+// channel 0; nearest: o00 alone) and the bilinear weights.  A position outside computes on source pixel (0, 0).
+struct WarpTap {
+  bool in;
+  int64_t o00, o01, o10, o11;
+  double fy, fx, gy, gx;
+};
+
+__host__ __device__ __forceinline__ WarpTap warp_tap(int Hs, int Ws, int C, const WarpMap& M, int mode, double fi, double fj) {
+  WarpTap t;
+  const double d = warp_add(warp_add(warp_mul(M.m[6], fi), warp_mul(M.m[7], fj)), M.m[8]);
+  const double y = warp_div(warp_add(warp_add(warp_mul(M.m[0], fi), warp_mul(M.m[1], fj)), M.m[2]), d);
+  const double x = warp_div(warp_add(warp_add(warp_mul(M.m[3], fi), warp_mul(M.m[4], fj)), M.m[5]), d);
+  bool in = d > 0.0 && __builtin_isfinite(y) && __builtin_isfinite(x);
+  if (mode == 0) {
+    // the comparisons are on the floored doubles: no integer conversion of a position out of range
+    const double ry = floor(warp_add(y, 0.5)), rx = floor(warp_add(x, 0.5));
+    in = in && ry >= 0.0 && ry < (double)Hs && rx >= 0.0 && rx < (double)Ws;
+    t.o00 = t.o01 = t.o10 = t.o11 = ((int64_t)(in ? (int)ry : 0) * Ws + (in ? (int)rx : 0)) * C;
+    t.fy = t.fx = t.gy = t.gx = 0.0;
+  } else {
+    in = in && y >= 0.0 && y <= (double)(Hs - 1) && x >= 0.0 && x <= (double)(Ws - 1);
+    const double y0f = in ? floor(y) : 0.0, x0f = in ? floor(x) : 0.0;
+    const int y0 = (int)y0f, x0 = (int)x0f;
+    const int y1 = y0 + 1 < Hs ? y0 + 1 : Hs - 1, x1 = x0 + 1 < Ws ? x0 + 1 : Ws - 1;
+    t.fy = in ? warp_sub(y, y0f) : 0.0;
+    t.fx = in ? warp_sub(x, x0f) : 0.0;
+    t.gy = warp_sub(1.0, t.fy);
+    t.gx = warp_sub(1.0, t.fx);
+    const int64_t r0 = (int64_t)y0 * Ws * C, r1 = (int64_t)y1 * Ws * C;
+    t.o00 = r0 + (int64_t)x0 * C;
+    t.o01 = r0 + (int64_t)x1 * C;
+    t.o10 = r1 + (int64_t)x0 * C;
+    t.o11 = r1 + (int64_t)x1 * C;
+  }
+  t.in = in;
+  return t;
+}
+
+// Channel c of the source at a tap, before rounding: the tapped byte (nearest) or the blend in the written order (bilinear)
+__host__ __device__ __forceinline__ double warp_value(const uint8_t* __restrict__ src, const WarpTap& t, int mode, int c) {
+  if (mode == 0) return (double)src[t.o00 + c];
+  const double a00 = (double)src[t.o00 + c], a01 = (double)src[t.o01 + c], a10 = (double)src[t.o10 + c], a11 = (double)src[t.o11 + c];
+  const double top = warp_add(warp_mul(t.gx, a00), warp_mul(t.fx, a01)), bot = warp_add(warp_mul(t.gx, a10), warp_mul(t.fx, a11));
+  return warp_add(warp_mul(t.gy, top), warp_mul(t.fy, bot));
+}
+
+__host__ __device__ __forceinline__ uint8_t warp_byte(double v) {
+  v = floor(warp_add(v, 0.5));
+  v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
+  return (uint8_t)(int)v;
+}
+
+// Canvas pixel (i, j) from its samples: sample a ss + b at (i + off[a], j + off[b]), reduced in that order over the samples that
+// count; the pixel keeps the inside byte of its centre, and is empty where that is 0 or no sample counts.
+__host__ __device__ __forceinline__ double warp_ss_off(int ss, int a) {
+  return warp_sub(warp_div((double)(2 * a + 1), (double)(2 * ss)), 0.5);
+}
+
+__host__ __device__ __forceinline__ void warp_pixel_ss(const uint8_t* __restrict__ src, int Hs, int Ws, int C, const WarpMap& M, int mode,
+                                                       int ss, int reduce, int i, int j, uint8_t* __restrict__ out,
+                                                       uint8_t* __restrict__ inside) {
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};                   // reduce 0: the ordered sum; reduce 1: the smallest value so far
+  int cnt = 0;
+  if (warp_tap(Hs, Ws, C, M, mode, (double)i, (double)j).in) {      // a centre outside: empty whatever its samples say
+    for (int a = 0; a < ss; ++a) {
+      const double fi = warp_add((double)i, warp_ss_off(ss, a));
+      for (int b = 0; b < ss; ++b) {
+        const WarpTap t = warp_tap(Hs, Ws, C, M, mode, fi, warp_add((double)j, warp_ss_off(ss, b)));
+        if (!t.in) continue;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)                       // unrolled with a guard: acc stays in registers
+          if (c < C) {
+            const double v = warp_value(src, t, mode, c);
+            acc[c] = reduce == 0 ? warp_add(acc[c], v) : (cnt == 0 || v < acc[c] ? v : acc[c]);
+          }
+        ++cnt;
+      }
+    }
+  }
+  const double n = (double)(cnt ? cnt : 1);
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    if (c < C) out[c] = cnt ? warp_byte(reduce == 0 ? warp_div(acc[c], n) : acc[c]) : 0;
+  if (inside) *inside = cnt ? 255 : 0;
+}
+
 __global__ __launch_bounds__(256) void warp_image_kernel(const uint8_t* __restrict__ src, int Hs, int Ws, int C, int Ho, int Wo, WarpMap M,
                                                          int mode, uint8_t* __restrict__ out, uint8_t* __restrict__ inside) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= (int64_t)Ho * Wo) return;
   const int i = (int)(p / Wo), j = (int)(p - (int64_t)i * Wo);
   warp_pixel(src, Hs, Ws, C, M, mode, i, j, out + p * C, inside ? inside + p : nullptr);
+}
+
+__global__ __launch_bounds__(256) void warp_image_ss_kernel(const uint8_t* __restrict__ src, int Hs, int Ws, int C, int Ho, int Wo,
+                                                            WarpMap M, int mode, int ss, int reduce, uint8_t* __restrict__ out,
+                                                            uint8_t* __restrict__ inside) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (int64_t)Ho * Wo) return;
+  const int i = (int)(p / Wo), j = (int)(p - (int64_t)i * Wo);
+  warp_pixel_ss(src, Hs, Ws, C, M, mode, ss, reduce, i, j, out + p * C, inside ? inside + p : nullptr);
 }
 
 static int warp_check(const char* who, const void* src, int Hs, int Ws, int C, int Ho, int Wo, const double* m, int mode, const void* out) {
@@ -74,6 +176,15 @@ static int warp_check(const char* who, const void* src, int Hs, int Ws, int C, i
   if (mode != 0 && mode != 1) { set_error("%s: mode=%d (0 nearest, 1 bilinear)", who, mode); return NPP_ERR_ARG; }
   for (int k = 0; k < 9; ++k)
     if (!isfinite(m[k])) { set_error("%s: matrix entry m[%d] = %g is not finite", who, k, m[k]); return NPP_ERR_ARG; }
+  return NPP_OK;
+}
+
+static int warp_check_ss(const char* who, const void* src, int Hs, int Ws, int C, int Ho, int Wo, const double* m, int mode, int ss,
+                         int reduce, const void* out) {
+  const int rc = warp_check(who, src, Hs, Ws, C, Ho, Wo, m, mode, out);
+  if (rc) return rc;
+  if (ss != 1 && ss != 2 && ss != 4 && ss != 8) { set_error("%s: ss=%d samples per canvas pixel and direction (1, 2, 4 or 8)", who, ss); return NPP_ERR_ARG; }
+  if (reduce != 0 && reduce != 1) { set_error("%s: reduce=%d (0 mean, 1 min)", who, reduce); return NPP_ERR_ARG; }
   return NPP_OK;
 }
 
@@ -102,6 +213,31 @@ extern "C" int npp_warp_image_u8_host(const uint8_t* src, int Hs, int Ws, int C,
     for (int j = 0; j < Wo; ++j) {
       const int64_t p = (int64_t)i * Wo + j;
       warp_pixel(src, Hs, Ws, C, M, mode, i, j, out + p * C, inside ? inside + p : nullptr);
+    }
+  return NPP_OK;
+}
+
+extern "C" int npp_warp_image_u8_ss(const uint8_t* d_src, int Hs, int Ws, int C, int Ho, int Wo, const double m[9], int mode, int ss,
+                                    int reduce, uint8_t* d_out, uint8_t* d_inside, void* stream) {
+  const int rc = warp_check_ss("npp_warp_image_u8_ss", d_src, Hs, Ws, C, Ho, Wo, m, mode, ss, reduce, d_out);
+  if (rc) return rc;
+  WarpMap M;
+  for (int k = 0; k < 9; ++k) M.m[k] = m[k];
+  hipLaunchKernelGGL(warp_image_ss_kernel, dim3((unsigned)(((int64_t)Ho * Wo + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_src, Hs,
+                     Ws, C, Ho, Wo, M, mode, ss, reduce, d_out, d_inside);
+  return check_launch("npp_warp_image_u8_ss");
+}
+
+extern "C" int npp_warp_image_u8_ss_host(const uint8_t* src, int Hs, int Ws, int C, int Ho, int Wo, const double m[9], int mode, int ss,
+                                         int reduce, uint8_t* out, uint8_t* inside) {
+  const int rc = warp_check_ss("npp_warp_image_u8_ss_host", src, Hs, Ws, C, Ho, Wo, m, mode, ss, reduce, out);
+  if (rc) return rc;
+  WarpMap M;
+  for (int k = 0; k < 9; ++k) M.m[k] = m[k];
+  for (int i = 0; i < Ho; ++i)
+    for (int j = 0; j < Wo; ++j) {
+      const int64_t p = (int64_t)i * Wo + j;
+      warp_pixel_ss(src, Hs, Ws, C, M, mode, ss, reduce, i, j, out + p * C, inside ? inside + p : nullptr);
     }
   return NPP_OK;
 }

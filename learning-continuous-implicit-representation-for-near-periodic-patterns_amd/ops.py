@@ -459,44 +459,66 @@ def view_samples_host(view, supersample, res):
     return yx, counts, inside
 
 
-def _warp_args(M, size, mode):
+WARP_REDUCES = ("mean", "min")      # how the antialiased warp reduces a pixel's samples (include/npp_hip.h npp_warp_image_u8_ss)
+
+
+def check_warp(mode, supersample=1, reduce="mean"):
+    """(mode code, ss, reduce code) of a warp; ValueError by the argument's name for a value the library does not take."""
+    if mode not in ("nearest", "bilinear"):
+        raise ValueError(f"mode {mode!r}: 'nearest' or 'bilinear'")
+    ss = check_supersample(supersample)
+    if reduce not in WARP_REDUCES:
+        raise ValueError(f"reduce {reduce!r}: one of {WARP_REDUCES}")
+    return int(mode == "bilinear"), ss, WARP_REDUCES.index(reduce)
+
+
+def _warp_args(M, size, mode, supersample, reduce):
     m = np.asarray(M, dtype=np.float64).reshape(-1)
     if m.size != 9:
         raise ValueError(f"M: expected a 3 x 3 matrix, got {np.shape(M)}")
-    if mode not in ("nearest", "bilinear"):
-        raise ValueError(f"mode {mode!r}: 'nearest' or 'bilinear'")
+    md, ss, rd = check_warp(mode, supersample, reduce)
     Ho, Wo = (int(s) for s in size)
     if Ho < 1 or Wo < 1:
         raise ValueError(f"size {tuple(size)}: both sides must be >= 1")
-    return (C.c_double * 9)(*[float(v) for v in m]), Ho, Wo, int(mode == "bilinear")
+    return (C.c_double * 9)(*[float(v) for v in m]), Ho, Wo, md, ss, rd
 
 
-def warp_image_u8(img_u8, M, size, mode="bilinear"):
+def warp_image_u8(img_u8, M, size, mode="bilinear", supersample=1, reduce="mean"):
     """(Hs, Ws) or (Hs, Ws, C <= 4) uint8 on the device -> the size = (Ho, Wo) canvas under the map M (canvas pixel -> source
-    position, float64) and its (Ho, Wo) coverage mask (255 inside the source): include/npp_hip.h npp_warp_image_u8."""
+    position, float64) and its (Ho, Wo) coverage mask (255 inside the source): include/npp_hip.h npp_warp_image_u8.  supersample = S
+    in SUPERSAMPLES, reduce 'mean' or 'min': S x S samples per canvas pixel, reduced in the launch (npp_warp_image_u8_ss); the
+    defaults are the point launch."""
     _req(img_u8, torch.uint8, "img_u8")
     if img_u8.dim() not in (2, 3) or img_u8.numel() == 0:
         raise ValueError("img_u8: expected a non-empty (H, W) or (H, W, C)")
-    m, Ho, Wo, md = _warp_args(M, size, mode)
+    m, Ho, Wo, md, ss, rd = _warp_args(M, size, mode, supersample, reduce)
     Cn = 1 if img_u8.dim() == 2 else img_u8.shape[2]
     out = torch.empty((Ho, Wo) + tuple(img_u8.shape[2:]), dtype=torch.uint8, device=img_u8.device)
     inside = torch.empty((Ho, Wo), dtype=torch.uint8, device=img_u8.device)
-    check(lib().npp_warp_image_u8(_p(img_u8), img_u8.shape[0], img_u8.shape[1], Cn, Ho, Wo, m, md, _p(out), _p(inside), _stream()),
-          "npp_warp_image_u8")
+    if (ss, rd) == (1, 0):
+        check(lib().npp_warp_image_u8(_p(img_u8), img_u8.shape[0], img_u8.shape[1], Cn, Ho, Wo, m, md, _p(out), _p(inside), _stream()),
+              "npp_warp_image_u8")
+    else:
+        check(lib().npp_warp_image_u8_ss(_p(img_u8), img_u8.shape[0], img_u8.shape[1], Cn, Ho, Wo, m, md, ss, rd, _p(out), _p(inside),
+                                         _stream()), "npp_warp_image_u8_ss")
     return out, inside
 
 
-def warp_image_u8_host(img_u8, M, size, mode="bilinear"):
+def warp_image_u8_host(img_u8, M, size, mode="bilinear", supersample=1, reduce="mean"):
     """warp_image_u8 on a NumPy array, by the library's host twin."""
     img = np.ascontiguousarray(img_u8, np.uint8)
     if img.ndim not in (2, 3) or img.size == 0:
         raise ValueError("img_u8: expected a non-empty (H, W) or (H, W, C)")
-    m, Ho, Wo, md = _warp_args(M, size, mode)
+    m, Ho, Wo, md, ss, rd = _warp_args(M, size, mode, supersample, reduce)
     Cn = 1 if img.ndim == 2 else img.shape[2]
     out = np.empty((Ho, Wo) + img.shape[2:], np.uint8)
     inside = np.empty((Ho, Wo), np.uint8)
-    check(lib().npp_warp_image_u8_host(C.c_void_p(img.ctypes.data), img.shape[0], img.shape[1], Cn, Ho, Wo, m, md,
-                                       C.c_void_p(out.ctypes.data), C.c_void_p(inside.ctypes.data)), "npp_warp_image_u8_host")
+    src, dst, ins = C.c_void_p(img.ctypes.data), C.c_void_p(out.ctypes.data), C.c_void_p(inside.ctypes.data)
+    if (ss, rd) == (1, 0):
+        check(lib().npp_warp_image_u8_host(src, img.shape[0], img.shape[1], Cn, Ho, Wo, m, md, dst, ins), "npp_warp_image_u8_host")
+    else:
+        check(lib().npp_warp_image_u8_ss_host(src, img.shape[0], img.shape[1], Cn, Ho, Wo, m, md, ss, rd, dst, ins),
+              "npp_warp_image_u8_ss_host")
     return out, inside
 
 

@@ -215,18 +215,23 @@ def canvas_coords(M, size, res=(1, 1), start=0, n=None, device="cpu", return_ins
     return (yx, inside) if return_inside else yx
 
 
-def warp_image(img_u8, M, size, mode="bilinear", device=None):
+def warp_image(img_u8, M, size, mode="bilinear", device=None, supersample=1, reduce="mean"):
     """The size = (Ho, Wo) canvas whose pixel (i, j) reads the (Hs, Ws[, C <= 4]) uint8 image at M(i, j) (float64; 'bilinear' or
     'nearest': include/npp_hip.h npp_warp_image_u8), and its (Ho, Wo) coverage mask, 255 where the position lies in the image.
-    device None / "cpu": NumPy arrays through the library's host twin; otherwise device tensors in and out."""
+    supersample = S in SUPERSAMPLES: every canvas pixel is reduced from S x S samples spread over its footprint, of which those in
+    the image count -- reduce 'mean' (their ordered float64 mean: antialiasing) or 'min' (the darkest: a mask stays black where any
+    sample is black) -- and the mask is 255 where the pixel centre lies in the image and a sample counts (npp_warp_image_u8_ss).
+    The defaults are the point warp.  device None / "cpu": NumPy arrays through the library's host twin; otherwise device tensors
+    in and out.  ValueError by the argument's name, before a device is touched."""
     from . import ops
+    ops.check_warp(mode, supersample, reduce)
     if _is_cpu(device):
-        return ops.warp_image_u8_host(np.asarray(img_u8), check_matrix(M), size, mode)
+        return ops.warp_image_u8_host(np.asarray(img_u8), check_matrix(M), size, mode, supersample, reduce)
     import torch
     dev = ops.select_device(device)
     t = img_u8 if isinstance(img_u8, torch.Tensor) else torch.from_numpy(np.array(img_u8))
     t = t.to(device=dev, dtype=torch.uint8).contiguous()
-    return ops.warp_image_u8(t, check_matrix(M), size, mode)
+    return ops.warp_image_u8(t, check_matrix(M), size, mode, supersample, reduce)
 
 
 def composite(photo_u8, render, inside, mask=None, beyond=False):
