@@ -824,9 +824,10 @@ __global__ void cx_dx_finish_kernel(const float* __restrict__ x, int N, int C, i
 // The same finish written STRAIGHT into the trunk's flat bf16 gradient tensor (npp_trunk_layout.h), gated by the ReLU of the tapped
 // layer: dz = dx * [y > 0] -- what cx_dx_finish_kernel + npp_trunk_grad_in did in two launches and an fp32 round trip
 // (round 4).  One thread = one 16-byte unit (8 channels of one position): the position's dot product and inverse norm are
-// formed once per unit.  Border / tail positions of the run are rewritten as zeros (the layout's invariant).
-__global__ void cx_dx_finish_flat_kernel(const float* __restrict__ x, const float* __restrict__ dxh, int N, int C, int H, int W,
-                                         CxWs w, const f16x8* __restrict__ yact, bf16x8* __restrict__ dz, int64_t nposp,
+// formed once per unit.  Border / tail positions of the run are rewritten as zeros (the layout's invariant); the run is rounded up to
+// whole position blocks, and where that reaches into images N .. N_total - 1 of the tensor those are NOT this call's to write.
+__global__ void cx_dx_finish_flat_kernel(const float* __restrict__ x, const float* __restrict__ dxh, int N, int N_total, int C, int H,
+                                         int W, CxWs w, const f16x8* __restrict__ yact, bf16x8* __restrict__ dz, int64_t nposp,
                                          int64_t npos_range, int n_dot) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int chunks = C / 8;
@@ -835,6 +836,7 @@ __global__ void cx_dx_finish_flat_kernel(const float* __restrict__ x, const floa
   const int64_t p = t - (int64_t)c8 * npos_range;
   const int Wp = W + 2, S = (H + 2) * Wp, hw = H * W;
   const int n = (int)(p / S), r = (int)(p - (int64_t)n * S), yy = r / Wp, xx = r - yy * Wp;
+  if (n >= N && n < N_total) return;
   const int64_t u = (int64_t)c8 * nposp + kConvGuard + p;
   bf16x8 o;
 #pragma unroll
@@ -1170,8 +1172,8 @@ static int cx_launch(const float* d_fx, const float* d_fy, int N, int C, int hw,
         set_error("%s: bad flat-output description", who); return NPP_ERR_ARG;
       }
       const int64_t range = conv_npos_round(N, flat->H, flat->W), nt = range * (C / 8);
-      hipLaunchKernelGGL(cx_dx_finish_flat_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, d_fx, d_dfx, N, C, flat->H, flat->W,
-                         w, (const f16x8*)flat->yact, (bf16x8*)flat->dz, conv_nposp(flat->N_total, flat->H, flat->W), range, C / 32);
+      hipLaunchKernelGGL(cx_dx_finish_flat_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, d_fx, d_dfx, N, flat->N_total, C, flat->H,
+                         flat->W, w, (const f16x8*)flat->yact, (bf16x8*)flat->dz, conv_nposp(flat->N_total, flat->H, flat->W), range, C / 32);
       return check_launch(who);
     }
     const int64_t ne = nh * C;
