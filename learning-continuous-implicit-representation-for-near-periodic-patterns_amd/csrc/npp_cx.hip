@@ -1,8 +1,4 @@
-// npp_cx.hip -- K5 integer patch gather and K6 contextual-loss core (forward + d/dx).
-//
-// K5 replaces extract_glimpse(mode='nearest', padding 'zeros') as models/sampler.py:171-178,
-// 284-291 calls it (utils/extract_glimpse.py:53-79): an integer crop [c - P/2, c + P/2) with
-// zeros outside the image; the reference first tiles the whole image once per crop.
+// npp_cx.hip -- K6 contextual-loss core (forward + d/dx).
 //
 // K6 replaces contextual_loss(x, y, band_width, weight, 'cosine')
 // (externel_lib/contextual_loss/functional.py:9-63, :127-163) and its autograd backward w.r.t.
@@ -27,23 +23,6 @@
 
 namespace npp {
 
-// ---------------------------------------------------------------- K5 patch gather
-__global__ void patch_gather_kernel(const float* __restrict__ img, const float* __restrict__ mask, int H, int W,
-                                    const int32_t* __restrict__ centres, int M, int P, float* __restrict__ out_rgb,
-                                    float* __restrict__ out_mask) {
-  const int m = blockIdx.y;
-  const int cy = centres[2 * m], cx = centres[2 * m + 1];
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < P * P; idx += gridDim.x * blockDim.x) {
-    const int py = idx / P, px = idx - py * P;
-    const int y = cy - P / 2 + py, x = cx - P / 2 + px;
-    const bool in = y >= 0 && y < H && x >= 0 && x < W;
-    const int64_t src = (int64_t)y * W + x;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out_rgb[((int64_t)m * 3 + c) * P * P + idx] = in ? img[src * 3 + c] : 0.0f;
-    if (out_mask) out_mask[(int64_t)m * P * P + idx] = in ? mask[src] : 0.0f;
-  }
-}
-
 // ---------------------------------------------------------------- K6 contextual loss
 struct CxWs {           // workspace carve (floats unless noted)
   float* mu;            // [groups][mu_stride]: mean over the GROUP's y samples (one group = one image of a stacked launch)
@@ -63,21 +42,69 @@ struct CxWs {           // workspace carve (floats unless noted)
   // sample groups (npp_cx_fwd_bwd_groups): group m = the nk samples from batch index iter[m].x0 on; iter == null: one group of N
   const StackIter* iter;
   int32_t M, mu_stride, N, dot_slots;
-  int32_t min_in_rows;  // the row pass (cx_rows_fwd32_kernel) takes the row minima of D itself: cx_sim_kernel issues no atomicMin
+  int32_t sim_atomic_min;  // cx_sim_kernel issues the atomicMin into dmin (the big forms: cx_rows_fwd_big_kernel reads dmin; the row
+                           // pass of every smaller map holds the whole row in registers and takes its minimum itself)
 };
+// ---- the rules that more than one kernel applies, one body each
+__device__ __forceinline__ int cx_groups(const CxWs& w) { return w.iter ? w.M : 1; }
+// group g = samples cx_group_first(g) .. + cx_group_count(g) - 1 (no table: one group of all N)
+__device__ __forceinline__ int cx_group_first(const CxWs& w, int g) { return w.iter ? w.iter[g].x0 : 0; }
+__device__ __forceinline__ int cx_group_count(const CxWs& w, int g) { return w.iter ? w.iter[g].nk : w.N; }
 // group of sample n and the group's sample count
 __device__ __forceinline__ int cx_group(const CxWs& w, int n, int& ng) {
-  if (!w.iter) { ng = w.N; return 0; }
+  if (!w.iter) { ng = cx_group_count(w, 0); return 0; }
   int m = 0;
   for (int j = 1; j < w.M; ++j)
-    if (w.iter[j].nk > 0 && n >= w.iter[j].x0) m = j;
-  ng = w.iter[m].nk;
+    if (cx_group_count(w, j) > 0 && n >= cx_group_first(w, j)) m = j;
+  ng = cx_group_count(w, m);
   return m;
 }
 __device__ __forceinline__ const float* cx_mu(const CxWs& w, int n) {
   int ng;
   return w.mu + (int64_t)cx_group(w, n, ng) * w.mu_stride;
 }
+__device__ __forceinline__ float inv_norm(float ss) { return 1.0f / fmaxf(sqrtf(ss), 1e-12f); }   // F.normalize eps
+// w = exp((1 - D / (min_j D + 1e-5)) / h), dm = the row minimum + 1e-5 (quotient form; the value-only big form multiplies by a reciprocal)
+__device__ __forceinline__ float cx_weight(float d, float dm, float inv_h) { return __expf((1.0f - d / dm) * inv_h); }
+// a sample's loss term l = scale * -log(cxn [* weight] + 1e-5) [/ ng] and its gradient scale g = dl/dcxn / hw, from cxn = mean_j cmax_j
+__device__ __forceinline__ void cx_loss_term(float cxn, const float* weight_n, int ng, int hw, float scale, float& l, float& g) {
+  float ln, dcxn;
+  if (weight_n) {                     // functional.py:55-57: sum(-log(cx * w + 1e-5))
+    const float wt = *weight_n;
+    ln = -logf(cxn * wt + 1e-5f);
+    dcxn = -wt / (cxn * wt + 1e-5f);
+  } else {                            // mean over the group's samples
+    ln = -logf(cxn + 1e-5f) / (float)ng;
+    dcxn = -1.0f / ((float)ng * (cxn + 1e-5f));
+  }
+  l = scale * ln;
+  g = scale * dcxn / (float)hw;
+}
+// the inverse norms of position np = n * hw + p, once instead of once per use (read by the backward kernels)
+__device__ __forceinline__ void cx_publish_inv_norms(const CxWs& w, int64_t np) {
+  w.inx[np] = inv_norm(w.ssx[np]);
+  w.iny[np] = inv_norm(w.ssy[np]);
+}
+// thread t < groups of ONE block: group t's loss terms, added in sample order, to loss[t * loss_stride].  SAME_LAUNCH: lsum was
+// written by other blocks of this launch (cx_loss_kernel's last arriver) and is read past the caches; a previous launch's
+// (cx_rows_bwd_kernel: the row pass's tail wrote it) is read plainly
+template <bool SAME_LAUNCH>
+__device__ __forceinline__ void cx_group_sums(const CxWs& w, float* __restrict__ loss, int loss_stride) {
+  const int grp = threadIdx.x;
+  if (grp >= cx_groups(w)) return;
+  const int n0 = cx_group_first(w, grp), cnt = cx_group_count(w, grp);
+  float total = 0.0f;
+  for (int q = n0; q < n0 + cnt; ++q) total += SAME_LAUNCH ? share_load(w.lsum + q) : w.lsum[q];
+  if (cnt > 0) atomicAdd(loss + (int64_t)grp * loss_stride, total);
+}
+// xh . dxh of position np: the channel tiles' partials in slot order (nh = N * hw)
+__device__ __forceinline__ float cx_dot_sum(const CxWs& w, int64_t np, int64_t nh, int n_dot) {
+  float dot = 0.0f;
+  for (int q = 0; q < n_dot; ++q) dot += w.dot[(int64_t)q * nh + np];
+  return dot;
+}
+// dx = (dxh - xh (xh . dxh)) * inx, xh = (x - mu) inx
+__device__ __forceinline__ float cx_dx_value(float dxh, float x, float mu, float inx, float dot) { return (dxh - (x - mu) * inx * dot) * inx; }
 
 __host__ __device__ inline int64_t cx_ws_floats(int N, int C, int hw) {
   return (int64_t)NPP_MAX_STACK * (C + 16) + (7LL + C / 32) * N * hw + 3LL * N + 2LL * N * hw * hw + 160;
@@ -86,7 +113,7 @@ __host__ __device__ inline int64_t cx_ws_floats(int N, int C, int hw) {
 __host__ inline CxWs carve(float* base, int N, int C, int hw, const void* iter = nullptr, int M = 0) {
   CxWs w;
   float* p = base;
-  w.iter = (const StackIter*)iter; w.M = M; w.N = N; w.mu_stride = (C + 15) / 16 * 16; w.dot_slots = C / 32; w.min_in_rows = 0;
+  w.iter = (const StackIter*)iter; w.M = M; w.N = N; w.mu_stride = (C + 15) / 16 * 16; w.dot_slots = C / 32; w.sim_atomic_min = 1;
   w.mu = p; p += (int64_t)(M > 0 ? M : 1) * w.mu_stride;
   const int64_t nh = (int64_t)N * hw;
   w.ssx = p; p += nh;
@@ -105,8 +132,6 @@ __host__ inline CxWs carve(float* base, int N, int C, int hw, const void* iter =
   return w;
 }
 
-__device__ __forceinline__ float inv_norm(float ss) { return 1.0f / fmaxf(sqrtf(ss), 1e-12f); }   // F.normalize eps
-
 // Workgroups are dispatched round-robin over the 8 XCDs, each with its own 4 MiB L2.  With the natural block order
 // every XCD touched all samples (x + y = 7 MB at the loop's size) and its L2 thrashed: 75 % of wave time waiting on
 // memory (SQ_WAIT_ANY).  Logical block = (bid % 8) * ceil(nb / 8) + bid / 8 gives each XCD one contiguous run of
@@ -123,7 +148,7 @@ __device__ __forceinline__ int xcd_block(int nb) {
 __global__ void cx_mean_kernel(const float* __restrict__ y, int N, int C, int hw, CxWs w) {
   __shared__ float red[4];
   const int c = blockIdx.x, grp = blockIdx.y;
-  const int n0 = w.iter ? w.iter[grp].x0 : 0, ng = w.iter ? w.iter[grp].nk : N;
+  const int n0 = cx_group_first(w, grp), ng = cx_group_count(w, grp);
   float acc = 0.0f;
   for (int n = n0; n < n0 + ng; ++n)
     for (int p = threadIdx.x; p < hw; p += blockDim.x) acc += y[((int64_t)n * C + c) * hw + p];
@@ -144,10 +169,7 @@ __global__ void cx_mean_kernel(const float* __restrict__ y, int N, int C, int hw
 // Workgroup = 64 x 64 output tile of one sample, 4 waves of 32 x 32; the channel axis is streamed
 // through LDS in chunks of 32 ([32 c][64 pos] per operand, positions contiguous as in NCHW, so the
 // fp32 MFMA operand reads are conflict-free), double buffered.
-#ifndef NPP_CX_KC
-#define NPP_CX_KC 32
-#endif
-constexpr int kCxKc = NPP_CX_KC;           // channels per staged chunk (32 or 64: measured the same, 23.6 / 23.3 us at the loop's size;
+constexpr int kCxKc = 32;                  // channels per staged chunk (32 or 64: measured the same, 23.6 / 23.3 us at the loop's size;
                                            // timing-only builds: without the MFMAs 20.6, without the D stores 23.5, without the row-minimum
                                            // atomics 21.8 -- ~15 us of the launch are none of these, tools/r4_cx_variants.sh)
 constexpr int kCxNR = kCxKc / 16;          // rows of a chunk per thread
@@ -296,7 +318,7 @@ __global__ __launch_bounds__(256) void cx_sim_kernel(const float* __restrict__ x
       d = 1.0f - fminf(fmaxf(raw, 0.0f), 1.0f);
       w.D[((int64_t)n * hw + i) * hw + j] = d;
     }
-    if (w.min_in_rows) continue;                       // (uniform) the block-parallel row pass reads the whole row anyway: 3 us of atomics saved
+    if (!w.sim_atomic_min) continue;                   // (uniform) the block-parallel row pass reads the whole row anyway: 3 us of atomics saved
     float m = d;
 #pragma unroll
     for (int off = 16; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
@@ -304,56 +326,14 @@ __global__ __launch_bounds__(256) void cx_sim_kernel(const float* __restrict__ x
   }
 }
 
-// w = exp((1 - D/(dmin + 1e-5))/h), s = sum_j w, cx = w/s, column maxima.  One wave walks kCxRows
-// consecutive rows of one sample and keeps the running column maxima of its lanes in registers:
-// one atomicMax per column per kCxRows rows.
-constexpr int kCxRows = 8;
+// Row passes: w = exp((1 - D/(dmin + 1e-5))/h), s = sum_j w, cx = w/s, column maxima.  Maps up to 64 * kCxMaxCols positions take
+// cx_rows_fwd32_kernel (below, a row per wave in registers); larger ones the kernel here.
+constexpr int kCxRows = 8;            // consecutive rows of one sample per wave of cx_rows_fwd_big_kernel
 constexpr int kCxMaxCols = 32;        // columns per lane held in registers: hw <= 64 * 32 = 2048
-__global__ __launch_bounds__(256) void cx_rows_fwd_kernel(int N, int hw, float inv_h, CxWs w) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int groups = (hw + kCxRows - 1) / kCxRows;
-  const int64_t gid = (int64_t)blockIdx.x * 4 + wave;
-  if (gid >= (int64_t)N * groups) return;
-  const int n = (int)(gid / groups), r0 = (int)(gid - (int64_t)n * groups) * kCxRows;
-  float cmaxv[kCxMaxCols];
-#pragma unroll
-  for (int q = 0; q < kCxMaxCols; ++q) cmaxv[q] = 0.0f;
-  for (int rr = 0; rr < kCxRows && r0 + rr < hw; ++rr) {
-    const int64_t row = (int64_t)n * hw + r0 + rr;
-    const float dm = __uint_as_float(w.dmin[row]) + 1e-5f;
-    const float* Dr = w.D + row * hw;
-    float* cr = w.cx + row * hw;
-    float wv[kCxMaxCols];
-    float s = 0.0f;
-#pragma unroll
-    for (int q = 0; q < kCxMaxCols; ++q) {
-      const int j = lane + 64 * q;
-      wv[q] = j < hw ? __expf((1.0f - Dr[j] / dm) * inv_h) : 0.0f;
-      s += wv[q];
-    }
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    if (lane == 0) w.s[row] = s;
-    const float inv = 1.0f / s;
-#pragma unroll
-    for (int q = 0; q < kCxMaxCols; ++q) {
-      const int j = lane + 64 * q;
-      if (j < hw) {
-        const float c = wv[q] * inv;
-        cr[j] = c;
-        cmaxv[q] = fmaxf(cmaxv[q], c);
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < kCxMaxCols; ++q) {
-    const int j = lane + 64 * q;
-    if (j < hw) atomicMax(&w.cmax[(int64_t)n * hw + j], __float_as_uint(cmaxv[q]));
-  }
-}
-
-// The same row pass for hw > 64 * kCxMaxCols (whole-image crops of the proposal ranking, NPP_proposal/search.py:180-197): the
-// row sums first (per lane over j = lane + 64 q ascending, then the same butterfly -- the summation order of the kernel
-// above), then the columns in chunks of 64 * kCxMaxCols with the chunk's running maxima in registers.
+// The row pass for hw > 64 * kCxMaxCols (whole-image crops of the proposal ranking, NPP_proposal/search.py:180-197): the
+// row sums first (per lane over j = lane + 64 q ascending, then the same butterfly -- the summation order of
+// cx_rows_fwd32_kernel), then the columns in chunks of 64 * kCxMaxCols with the chunk's running maxima in registers: one atomicMax
+// per column per kCxRows rows.
 __global__ __launch_bounds__(256) void cx_rows_fwd_big_kernel(int N, int hw, float inv_h, CxWs w) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int groups = (hw + kCxRows - 1) / kCxRows;
@@ -369,7 +349,7 @@ __global__ __launch_bounds__(256) void cx_rows_fwd_big_kernel(int N, int hw, flo
       const float dm = __uint_as_float(w.dmin[row]) + 1e-5f;
       const float* Dr = w.D + row * hw;
       float s = 0.0f;
-      for (int j = lane; j < hw; j += 64) s += __expf((1.0f - Dr[j] / dm) * inv_h);
+      for (int j = lane; j < hw; j += 64) s += cx_weight(Dr[j], dm, inv_h);
       for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
       if (lane == 0) w.s[row] = s;
       inv[rr] = 1.0f / s; dmr[rr] = dm;
@@ -389,7 +369,7 @@ __global__ __launch_bounds__(256) void cx_rows_fwd_big_kernel(int N, int hw, flo
       for (int q = 0; q < kCxMaxCols; ++q) {
         const int j = c0 + lane + 64 * q;
         if (j < hw) {
-          const float c = __expf((1.0f - Dr[j] / dmr[rr]) * inv_h) * inv[rr];
+          const float c = cx_weight(Dr[j], dmr[rr], inv_h) * inv[rr];
           cr[j] = c;
           cmaxv[q] = fmaxf(cmaxv[q], c);
         }
@@ -439,10 +419,7 @@ __global__ __launch_bounds__(256) void cx_prep_big_kernel(const float* __restric
   for (int c = half; c < C; c += 2) dst[c * 128 + pl] = live ? (src[(int64_t)c * hw + pos] - mu[c]) * inv : 0.0f;
 }
 
-#ifndef NPP_CXBIG_KC
-#define NPP_CXBIG_KC 16
-#endif
-constexpr int kBigKc = NPP_CXBIG_KC;
+constexpr int kBigKc = 16;
 __global__ __launch_bounds__(256) void cx_sim_big_kernel(const float* __restrict__ xt, const float* __restrict__ yt, int N, int C, int hw,
                                                          CxWs w) {
   __shared__ __attribute__((aligned(16))) float sA[2][kBigKc][128];
@@ -476,12 +453,6 @@ __global__ __launch_bounds__(256) void cx_sim_big_kernel(const float* __restrict
 #define CXBIG_ISSUE(c0, A0, A1, B0, B1) { A0 = xa[(c0) * 32 + tid]; A1 = xa[(c0) * 32 + tid + 256]; B0 = yb[(c0) * 32 + tid]; B1 = yb[(c0) * 32 + tid + 256]; }
 #define CXBIG_FINISH(buf, A0, A1, B0, B1) { float4* da = (float4*)&sA[buf][0][0]; float4* db = (float4*)&sB[buf][0][0]; \
     da[tid] = A0; da[tid + 256] = A1; db[tid] = B0; db[tid + 256] = B1; }
-#ifdef NPP_CXBIG_NOMFMA          // (timing-only build)
-#define CXBIG_MMA(PAR) _Pragma("unroll") for (int ks = 0; ks < 8; ++ks) { \
-      const float a0 = sA[PAR][2 * ks + kh][wi * 64 + l31], a1 = sA[PAR][2 * ks + kh][wi * 64 + 32 + l31]; \
-      const float b0 = sB[PAR][2 * ks + kh][wj * 64 + l31], b1 = sB[PAR][2 * ks + kh][wj * 64 + 32 + l31]; \
-      acc[0][0][ks] += a0 * b0; acc[0][1][ks] += a0 * b1; acc[1][0][ks] += a1 * b0; acc[1][1][ks] += a1 * b1; }
-#else
 #define CXBIG_MMA(PAR) _Pragma("unroll") for (int ks = 0; ks < 8; ++ks) { \
       const float a0 = sA[PAR][2 * ks + kh][wi * 64 + l31], a1 = sA[PAR][2 * ks + kh][wi * 64 + 32 + l31]; \
       const float b0 = sB[PAR][2 * ks + kh][wj * 64 + l31], b1 = sB[PAR][2 * ks + kh][wj * 64 + 32 + l31]; \
@@ -489,7 +460,6 @@ __global__ __launch_bounds__(256) void cx_sim_big_kernel(const float* __restrict
       acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0); \
       acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0); \
       acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0); }
-#endif
   CXBIG_ISSUE(0, pa0, pa1, pb0, pb1);
   CXBIG_ISSUE(16, qa0, qa1, qb0, qb1);                  // (C >= 32)
   CXBIG_FINISH(0, pa0, pa1, pb0, pb1);
@@ -528,18 +498,12 @@ __global__ __launch_bounds__(256) void cx_sim_big_kernel(const float* __restrict
         const int j = j0 + wj * 64 + bj * 32 + l31;
         if (i < hw && j < hw) {
           const float d = 1.0f - fminf(fmaxf(acc[bi][bj][r], 0.0f), 1.0f);
-#ifdef NPP_CXBIG_NOSTORE         // (timing-only build)
-          if (d == 12345.0f)
-#endif
           Dt[(i - i0) * 128 + (j - j0)] = d;
           m = fminf(m, d);
         }
       }
 #pragma unroll
       for (int off = 16; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
-#ifdef NPP_CXBIG_NOATOMIC        // (timing-only build)
-      if (m == 12345.0f)
-#endif
       if (l31 == 0 && i < hw) atomicMin(&w.dmin[(int64_t)n * hw + i], __float_as_uint(m));
     }
 }
@@ -639,49 +603,28 @@ __global__ void cx_loss_kernel(int N, int hw, const float* __restrict__ weight, 
   float acc = 0.0f;
   for (int j = threadIdx.x; j < hw; j += blockDim.x) {
     acc += __uint_as_float(w.cmax[(int64_t)n * hw + j]);
-    w.inx[(int64_t)n * hw + j] = inv_norm(w.ssx[(int64_t)n * hw + j]);
-    w.iny[(int64_t)n * hw + j] = inv_norm(w.ssy[(int64_t)n * hw + j]);
+    cx_publish_inv_norms(w, (int64_t)n * hw + j);
   }
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
     const float cxn = (red[0] + red[1] + red[2] + red[3]) / (float)hw;
-    float l, dcxn;
-    if (weight) {                       // functional.py:55-57: sum(-log(cx * w + 1e-5))
-      const float wt = weight[n];
-      l = -logf(cxn * wt + 1e-5f);
-      dcxn = -wt / (cxn * wt + 1e-5f);
-    } else {                            // mean over the group's samples
-      l = -logf(cxn + 1e-5f) / (float)ng;
-      dcxn = -1.0f / ((float)ng * (cxn + 1e-5f));
-    }
-    share_store(w.lsum + n, scale * l);
-    w.g[n] = scale * dcxn / (float)hw;
+    float l, g;
+    cx_loss_term(cxn, weight ? weight + n : nullptr, ng, hw, scale, l, g);
+    share_store(w.lsum + n, l);
+    w.g[n] = g;
   }
-  if (!block_last_arriver(w.ticket, N)) return;
-  const int groups = w.iter ? w.M : 1;
-  if ((int)threadIdx.x < groups) {
-    const int grp = threadIdx.x;
-    const int n0 = w.iter ? w.iter[grp].x0 : 0, cnt = w.iter ? w.iter[grp].nk : N;
-    float total = 0.0f;
-    for (int q = n0; q < n0 + cnt; ++q) total += share_load(w.lsum + q);
-    if (cnt > 0) atomicAdd(loss + (int64_t)grp * loss_stride, total);
-  }
+  if (block_last_arriver(w.ticket, N)) cx_group_sums<true>(w, loss, loss_stride);
 }
 
 // one wave per row: cx row -> d raw row (in place).
 __global__ __launch_bounds__(256) void cx_rows_bwd_kernel(int N, int hw, float inv_h, CxWs w, float* __restrict__ loss, int loss_stride) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (loss && blockIdx.x == 0 && (int)threadIdx.x < (w.iter ? w.M : 1)) {     // the groups' loss sums, in sample order (lsum: previous launch)
-    const int grp = threadIdx.x;
-    const int n0 = w.iter ? w.iter[grp].x0 : 0, cnt = w.iter ? w.iter[grp].nk : N;
-    float total = 0.0f;
-    for (int q = n0; q < n0 + cnt; ++q) total += w.lsum[q];
-    if (cnt > 0) atomicAdd(loss + (int64_t)grp * loss_stride, total);
-  }
   const int64_t row = (int64_t)blockIdx.x * 4 + wave;
   if (row >= (int64_t)N * hw) return;
+  // (lsum: the row pass's tail, previous launch; the groups' threads sit in wave 0 of block 0, whose row 0 always exists)
+  if (loss && blockIdx.x == 0) cx_group_sums<false>(w, loss, loss_stride);
   const int n = (int)(row / hw);
   const float dmv = __uint_as_float(w.dmin[row]);
   const float dm = dmv + 1e-5f;
@@ -815,10 +758,8 @@ __global__ void cx_dx_finish_kernel(const float* __restrict__ x, int N, int C, i
   const int p = (int)(t % hw);
   const int64_t nc = t / hw;
   const int c = (int)(nc % C), n = (int)(nc / C);
-  const float inx = inv_norm(w.ssx[(int64_t)n * hw + p]);
-  float dot = 0.0f;
-  for (int q = 0; q < n_dot; ++q) dot += w.dot[(int64_t)q * N * hw + (int64_t)n * hw + p];     // fixed order
-  dx[t] = (dx[t] - (x[t] - cx_mu(w, n)[c]) * inx * dot) * inx;
+  const int64_t np = (int64_t)n * hw + p;
+  dx[t] = cx_dx_value(dx[t], x[t], cx_mu(w, n)[c], inv_norm(w.ssx[np]), cx_dot_sum(w, np, (int64_t)N * hw, n_dot));
 }
 
 // The same finish written STRAIGHT into the trunk's flat bf16 gradient tensor (npp_trunk_layout.h), gated by the ReLU of the tapped
@@ -844,23 +785,21 @@ __global__ void cx_dx_finish_flat_kernel(const float* __restrict__ x, const floa
   if (n < N && yy >= 1 && yy <= H && xx >= 1 && xx <= W) {
     const int pos = (yy - 1) * W + (xx - 1);
     const int64_t np = (int64_t)n * hw + pos;
-    const float inx = inv_norm(w.ssx[np]);
-    float dot = 0.0f;
-    for (int q = 0; q < n_dot; ++q) dot += w.dot[(int64_t)q * N * hw + np];          // fixed order
+    const float inx = inv_norm(w.ssx[np]), dot = cx_dot_sum(w, np, (int64_t)N * hw, n_dot);
     const float* mu = cx_mu(w, n);
     const f16x8 m = yact[u];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int c = conv_chan(c8, j);
       const int64_t e = ((int64_t)n * C + c) * hw + pos;
-      const float v = (dxh[e] - (x[e] - mu[c]) * inx * dot) * inx;
+      const float v = cx_dx_value(dxh[e], x[e], mu[c], inx, dot);
       o[j] = (__bf16)((float)m[j] > 0.0f ? v : 0.0f);
     }
   }
   dz[u] = o;
 }
 
-// ---- second-generation backward contraction and row pass (hw % 32 == 0) ---------------------------------------
+// ---- second-generation backward contraction (hw % 32 == 0) and row pass (hw <= 64 * kCxMaxCols) ----------------
 // What was measured on the loop's size (6 x 576 x 576 x 256; rocprofv3 + SQ counters, tools/cx_probe.py):
 //  * the row pass was serial (8 rows per wave, 36 us) -> one row per wave, 16 waves per block: 10 us;
 //  * the backward contraction spent 10 k VALU instructions per wave on sqrt + div for the inverse norms of its operands
@@ -965,7 +904,8 @@ __global__ __launch_bounds__(256) void cx_dx32s_kernel(const float* __restrict__
 
 // Row pass, block-parallel: 16 waves x 1 row = 16 consecutive rows of one sample per block (all rows of the matrix are
 // in flight at once: the pass is one row's latency); the column maxima of the 16 waves meet in LDS -> one atomicMax
-// per column and block.
+// per column and block.  Any hw <= 64 * kCxMaxCols (every index is guarded, the counts are ceiling divisions), not only the
+// multiples of 32 the name recalls.
 constexpr int kCxRowsPerWave = 1;
 constexpr int kCxRowWaves = 16;
 __global__ __launch_bounds__(64 * kCxRowWaves) void cx_rows_fwd32_kernel(int N, int hw, float inv_h, CxWs w, float scale, int with_loss) {
@@ -985,37 +925,24 @@ __global__ __launch_bounds__(64 * kCxRowWaves) void cx_rows_fwd32_kernel(int N, 
     float* cr = w.cx + row * hw;
     float wv[kCxMaxCols];
     float s = 0.0f;
-    float dm;
-    if (w.min_in_rows) {                                 // (uniform) the row is in this wave's registers: its minimum is 6 lane exchanges
-      float mn = 2.0f;                                   // (D <= 1)
+    float mn = 2.0f;                                     // the row is in this wave's registers: its minimum is 6 lane exchanges (D <= 1)
 #pragma unroll
-      for (int q = 0; q < kCxMaxCols; ++q) {
-        if (q < ncol) {
-          const int j = lane + 64 * q;
-          wv[q] = j < hw ? Dr[j] : 2.0f;
-          mn = fminf(mn, wv[q]);
-        }
+    for (int q = 0; q < kCxMaxCols; ++q) {
+      if (q < ncol) {
+        const int j = lane + 64 * q;
+        wv[q] = j < hw ? Dr[j] : 2.0f;
+        mn = fminf(mn, wv[q]);
       }
-      for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_xor(mn, off, 64));
-      if (lane == 0) w.dmin[row] = __float_as_uint(mn);  // the backward row pass reads it
-      dm = mn + 1e-5f;
+    }
+    for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_xor(mn, off, 64));
+    if (lane == 0) w.dmin[row] = __float_as_uint(mn);    // the backward row pass reads it
+    const float dm = mn + 1e-5f;
 #pragma unroll
-      for (int q = 0; q < kCxMaxCols; ++q) {
-        if (q < ncol) {
-          const int j = lane + 64 * q;
-          wv[q] = j < hw ? __expf((1.0f - wv[q] / dm) * inv_h) : 0.0f;
-          s += wv[q];
-        }
-      }
-    } else {
-      dm = __uint_as_float(w.dmin[row]) + 1e-5f;
-#pragma unroll
-      for (int q = 0; q < kCxMaxCols; ++q) {
-        if (q < ncol) {
-          const int j = lane + 64 * q;
-          wv[q] = j < hw ? __expf((1.0f - Dr[j] / dm) * inv_h) : 0.0f;
-          s += wv[q];
-        }
+    for (int q = 0; q < kCxMaxCols; ++q) {
+      if (q < ncol) {
+        const int j = lane + 64 * q;
+        wv[q] = j < hw ? cx_weight(wv[q], dm, inv_h) : 0.0f;
+        s += wv[q];
       }
     }
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
@@ -1054,8 +981,7 @@ __global__ __launch_bounds__(64 * kCxRowWaves) void cx_rows_fwd32_kernel(int N, 
   float acc = 0.0f;
   for (int j = threadIdx.x; j < hw; j += 64 * kCxRowWaves) {
     acc += __uint_as_float(__hip_atomic_load(&w.cmax[(int64_t)n * hw + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    w.inx[(int64_t)n * hw + j] = inv_norm(w.ssx[(int64_t)n * hw + j]);
-    w.iny[(int64_t)n * hw + j] = inv_norm(w.ssy[(int64_t)n * hw + j]);
+    cx_publish_inv_norms(w, (int64_t)n * hw + j);
   }
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
   __syncthreads();
@@ -1068,28 +994,13 @@ __global__ __launch_bounds__(64 * kCxRowWaves) void cx_rows_fwd32_kernel(int N, 
     const float cxn = tot / (float)hw;
     int ng;
     cx_group(w, n, ng);
-    w.lsum[n] = scale * (-logf(cxn + 1e-5f) / (float)ng);        // (mean over the group's samples; the weighted form keeps cx_loss_kernel)
-    w.g[n] = scale * (-1.0f / ((float)ng * (cxn + 1e-5f))) / (float)hw;
+    cx_loss_term(cxn, nullptr, ng, hw, scale, w.lsum[n], w.g[n]);      // (the weighted form keeps cx_loss_kernel)
   }
 }
 
 }  // namespace npp
 
 using namespace npp;
-
-extern "C" int npp_patch_gather(const float* d_img_hwc, const float* d_mask_hw, int H, int W, const int32_t* d_centres_yx,
-                                int M, int P, float* d_out_rgb, float* d_out_mask, void* stream) {
-  if (!d_img_hwc || !d_centres_yx || !d_out_rgb || H < 1 || W < 1 || M < 0 || P < 2 || (P & 1)) {
-    set_error("npp_patch_gather: bad arguments (M=%d, P=%d must be even)", M, P);
-    return NPP_ERR_ARG;
-  }
-  if (d_out_mask && !d_mask_hw) { set_error("npp_patch_gather: out_mask without mask"); return NPP_ERR_ARG; }
-  if (M == 0) return NPP_OK;
-  const int bx = (P * P + 255) / 256;
-  hipLaunchKernelGGL(patch_gather_kernel, dim3(bx, M), dim3(256), 0, (hipStream_t)stream, d_img_hwc, d_mask_hw, H, W,
-                     d_centres_yx, M, P, d_out_rgb, d_out_mask);
-  return check_launch("npp_patch_gather");
-}
 
 extern "C" int64_t npp_cx_workspace_bytes(int N, int C, int hw) {
   if (N < 1 || C < 32 || (C % 32) || hw < 1) { set_error("npp_cx_workspace_bytes: need N>=1, C multiple of 32, hw>=1"); return -1; }
@@ -1120,21 +1031,25 @@ static int cx_launch(const float* d_fx, const float* d_fy, int N, int C, int hw,
   const int groups = M > 0 ? M : 1;
   const int64_t nh = (int64_t)N * hw;
   const float inv_h = 1.0f / band_width;
-  const bool big = hw > 64 * kCxMaxCols;     // whole-image crops: the generic kernels, column-chunked row pass
-  const bool fast = !big && (hw % 32) == 0;  // LDS-free contractions + block-parallel row pass (all loop sizes: hw = (P/4)^2)
-  w.min_in_rows = fast ? 1 : 0;
+  const bool big = hw > 64 * kCxMaxCols;     // whole-image crops: column-chunked row pass (or, value only, the tiled form)
+  // all loop sizes (hw = (P/4)^2).  Selects two things only: the backward contraction (cx_dx32s_kernel against cx_dx_kernel) and
+  // loss_in_rows; every !big map takes the same forward contraction and the same block-parallel row pass
+  const bool fast = !big && (hw % 32) == 0;
+  w.sim_atomic_min = big ? 1 : 0;
   hipLaunchKernelGGL(cx_mean_kernel, dim3(C, groups), dim3(256), 0, s, d_fy, N, C, hw, w);
   const int tiles = (hw + 63) / 64;
-  const bool loss_in_rows = fast && d_dfx && !d_weight;      // the loss terms ride in the row pass, their group sums in the backward row pass
+  // the loss terms ride in the row pass, their group sums in the backward row pass.  (Not for hw % 32 != 0: cx_loss_kernel sums the
+  // column maxima as 256 threads, 4 partials, the row pass's tail as 1024 threads, 16 partials -- the loss bits of those maps would move)
+  const bool loss_in_rows = fast && d_dfx && !d_weight;
   const int t32 = hw / 32;
-  if (fast) {
+  if (!big) {
     hipLaunchKernelGGL(cx_sim_kernel, dim3((unsigned)(((int64_t)N * tiles * tiles + 7) / 8 * 8)), dim3(256), 0, s, d_fx, d_fy, N, C, hw, w);
     const size_t smem = (size_t)kCxRowWaves * hw * sizeof(float);
     constexpr int kRowLdsMax = kCxRowWaves * 64 * kCxMaxCols * 4;      // the limit set: the widest row this form takes (hw <= 64 kCxMaxCols), not this launch's
     const int rc = launch_lds<cx_rows_fwd32_kernel>(who, dim3((unsigned)((int64_t)N * ((hw + kCxRowWaves - 1) / kCxRowWaves))), dim3(64 * kCxRowWaves), smem,
                                                     smem > (size_t)kLdsDefault ? kRowLdsMax : 0, s, N, hw, inv_h, w, scale, (int)loss_in_rows);
     if (rc) return rc;                       // (the launcher checks its own launch: a failure ends the sequence here instead of at its last launch)
-  } else if (big && !d_dfx && big_fwd_fits(N, C, hw)) {
+  } else if (!d_dfx && big_fwd_fits(N, C, hw)) {
     // whole-image crop, value only (the ranking's score): re-tiled normalised operands, 128 x 128 tiles in super-block order, the
     // matrix stored tiled, written once and read twice.  Everything lives in the D + cx regions (2 N hw^2 floats).
     const int t128 = (hw + 127) / 128;
@@ -1150,8 +1065,7 @@ static int cx_launch(const float* d_fx, const float* d_fy, int N, int C, int hw,
   } else {
     hipLaunchKernelGGL(cx_sim_kernel, dim3((unsigned)(((int64_t)N * tiles * tiles + 7) / 8 * 8)), dim3(256), 0, s, d_fx, d_fy, N, C, hw, w);
     const int64_t row_groups = (int64_t)N * ((hw + kCxRows - 1) / kCxRows);
-    if (big) hipLaunchKernelGGL(cx_rows_fwd_big_kernel, dim3((unsigned)((row_groups + 3) / 4)), dim3(256), 0, s, N, hw, inv_h, w);
-    else hipLaunchKernelGGL(cx_rows_fwd_kernel, dim3((unsigned)((row_groups + 3) / 4)), dim3(256), 0, s, N, hw, inv_h, w);
+    hipLaunchKernelGGL(cx_rows_fwd_big_kernel, dim3((unsigned)((row_groups + 3) / 4)), dim3(256), 0, s, N, hw, inv_h, w);
   }
   if (!loss_in_rows) hipLaunchKernelGGL(cx_loss_kernel, dim3(N), dim3(256), 0, s, N, hw, d_weight, scale, d_loss, loss_stride, w);
   if (d_dfx) {

@@ -7,9 +7,32 @@
 // later folds the k tiled copies back onto the n_p*P*P prediction rows.  About twenty small torch kernels
 // each way; here: compose_fwd writes the concatenated (2*n_p*k, 3, P, P) batch [x | y] the trunks take,
 // compose_bwd turns dL/dx into dL/dpred rows.
+//
+// K5 patch gather replaces extract_glimpse(mode='nearest', padding 'zeros') as models/sampler.py:171-178,
+// 284-291 calls it (utils/extract_glimpse.py:53-79): an integer crop [c - P/2, c + P/2) with
+// zeros outside the image; the reference first tiles the whole image once per crop.
 #include "npp_common.h"
 
 namespace npp {
+
+// ---------------------------------------------------------------- K5 patch gather
+__global__ void patch_gather_kernel(const float* __restrict__ img, const float* __restrict__ mask, int H, int W,
+                                    const int32_t* __restrict__ centres, int M, int P, float* __restrict__ out_rgb,
+                                    float* __restrict__ out_mask) {
+  const int m = blockIdx.y;
+  const int cy = centres[2 * m], cx = centres[2 * m + 1];
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < P * P; idx += gridDim.x * blockDim.x) {
+    const int py = idx / P, px = idx - py * P;
+    const int y = cy - P / 2 + py, x = cx - P / 2 + px;
+    const bool in = y >= 0 && y < H && x >= 0 && x < W;
+    const int64_t src = (int64_t)y * W + x;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out_rgb[((int64_t)m * 3 + c) * P * P + idx] = in ? img[src * 3 + c] : 0.0f;
+    if (out_mask) out_mask[(int64_t)m * P * P + idx] = in ? mask[src] : 0.0f;
+  }
+}
+
+// ---------------------------------------------------------------- patch compose
 
 // pred rows: (n_p*P*P, 3) row-major, row = (p*P + y)*P + x  (train.py:178-181 coordinate order)
 // fake (n_p,3,P,P), fmask (n_p,1,P,P): the fake patch and its known-pixel mask (untiled)
@@ -96,6 +119,20 @@ __global__ void batch_assemble_kernel(const int32_t* __restrict__ i_train, const
 }  // namespace npp
 
 using namespace npp;
+
+extern "C" int npp_patch_gather(const float* d_img_hwc, const float* d_mask_hw, int H, int W, const int32_t* d_centres_yx,
+                                int M, int P, float* d_out_rgb, float* d_out_mask, void* stream) {
+  if (!d_img_hwc || !d_centres_yx || !d_out_rgb || H < 1 || W < 1 || M < 0 || P < 2 || (P & 1)) {
+    set_error("npp_patch_gather: bad arguments (M=%d, P=%d must be even)", M, P);
+    return NPP_ERR_ARG;
+  }
+  if (d_out_mask && !d_mask_hw) { set_error("npp_patch_gather: out_mask without mask"); return NPP_ERR_ARG; }
+  if (M == 0) return NPP_OK;
+  const int bx = (P * P + 255) / 256;
+  hipLaunchKernelGGL(patch_gather_kernel, dim3(bx, M), dim3(256), 0, (hipStream_t)stream, d_img_hwc, d_mask_hw, H, W,
+                     d_centres_yx, M, P, d_out_rgb, d_out_mask);
+  return check_launch("npp_patch_gather");
+}
 
 extern "C" int npp_batch_assemble(const int32_t* d_i_train, int64_t n_train, const int64_t* d_pix, int64_t n_pix,
                                   const int32_t* d_cen, int n_p, int P, int64_t Bp, const float* d_img_hwc,

@@ -844,9 +844,9 @@ def _cx_workspace(device, nbytes, st):
     return ws
 
 
-def cx_fwd_bwd(fx, fy, band_width=0.5, weight=None, scale=1.0, loss=None, want_grad=True):
-    """contextual_loss(x, y, band_width, weight, 'cosine') on features (N,C,h,w) + dL/dx
-    (externel_lib/contextual_loss/functional.py:9-63).  Returns (loss tensor[1], dfx or None)."""
+def _cx_intake(fx, fy):
+    """What the three CX wrappers do first: fp32 features (N, C, h, w) of one shape -> N, C, hw, the stream's workspace, its byte
+    count and the stream."""
     _req(fx, torch.float32, "fx")
     _req(fy, torch.float32, "fy", fx.shape)
     N, C = fx.shape[:2]
@@ -854,7 +854,13 @@ def cx_fwd_bwd(fx, fy, band_width=0.5, weight=None, scale=1.0, loss=None, want_g
     nbytes = lib().npp_cx_workspace_bytes(N, C, hw)
     check(nbytes, "npp_cx_workspace_bytes")
     st = _stream()
-    ws = _cx_workspace(fx.device, nbytes, st)
+    return N, C, hw, _cx_workspace(fx.device, nbytes, st), nbytes, st
+
+
+def cx_fwd_bwd(fx, fy, band_width=0.5, weight=None, scale=1.0, loss=None, want_grad=True):
+    """contextual_loss(x, y, band_width, weight, 'cosine') on features (N,C,h,w) + dL/dx
+    (externel_lib/contextual_loss/functional.py:9-63).  Returns (loss tensor[1], dfx or None)."""
+    N, C, hw, ws, nbytes, st = _cx_intake(fx, fy)
     if loss is None:
         loss = torch.zeros(1, dtype=torch.float32, device=fx.device)
     dfx = torch.empty_like(fx) if want_grad else None
@@ -2046,14 +2052,7 @@ def trunk_patch_in_loss_stack(pred, row0, crops, cmasks, M, n_p, P, X, N_total, 
 
 def cx_fwd_bwd_groups(fx, fy, it, M, band_width, scale, loss, loss_stride=1):
     """npp_cx_fwd_bwd over sample groups (one per image of a stack): fx / fy (X, C, h, w); loss (M * loss_stride,) accumulated."""
-    _req(fx, torch.float32, "fx")
-    _req(fy, torch.float32, "fy", fx.shape)
-    N, Cc = fx.shape[:2]
-    hw = fx.shape[2] * fx.shape[3]
-    nbytes = lib().npp_cx_workspace_bytes(N, Cc, hw)
-    check(nbytes, "npp_cx_workspace_bytes")
-    st = _stream()
-    ws = _cx_workspace(fx.device, nbytes, st)
+    N, Cc, hw, ws, nbytes, st = _cx_intake(fx, fy)
     dfx = torch.empty_like(fx)
     check(lib().npp_cx_fwd_bwd_groups(_p(fx), _p(fy), N, Cc, hw, band_width, scale, _p(loss), loss_stride, _p(dfx), _p(it), M, _p(ws),
                                       int(nbytes), st), "npp_cx_fwd_bwd_groups")
@@ -2064,13 +2063,8 @@ def cx_fwd_bwd_flat(fx, fy, yact, dz, N_total, band_width, scale, loss, loss_str
     """The contextual core with dL/dx written straight into the trunk's flat bf16 gradient tensor dz, gated by [yact > 0] (yact: the
     tapped layer's flat fp16 output; both of geometry N_total x C x H x W) -- no fp32 gradient tensor, no npp_trunk_grad_in launch.
     it / M: sample groups of a stacked launch (cx_fwd_bwd_groups)."""
-    _req(fx, torch.float32, "fx")
-    _req(fy, torch.float32, "fy", fx.shape)
-    N, Cc, H, W = fx.shape
-    nbytes = lib().npp_cx_workspace_bytes(N, Cc, H * W)
-    check(nbytes, "npp_cx_workspace_bytes")
-    st = _stream()
-    ws = _cx_workspace(fx.device, nbytes, st)
+    N, Cc, _, ws, nbytes, st = _cx_intake(fx, fy)
+    H, W = fx.shape[2:]
     key2 = (fx.device, "dxh", N * Cc * H * W, st.value)
     dxh = _cx_ws.get(key2)
     if dxh is None:

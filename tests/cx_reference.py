@@ -64,9 +64,9 @@ def dispatch(N, C, hw, grad, weight):
     """What cx_launch does with (N, C, hw, d_dfx != null, d_weight != null): the launch sequence (`form`) and the kernel-internal
     paths the shape takes."""
     big = hw > 64 * CX_MAX_COLS
-    fast = not big and hw % 32 == 0
+    fast = not big and hw % 32 == 0                    # selects the backward contraction (cx_dx32s_kernel) and loss_in_rows, nothing else
     loss_in_rows = fast and grad and not weight
-    raised_lds = fast and rows_lds_bytes(hw) > K_LDS_DEFAULT
+    raised_lds = not big and rows_lds_bytes(hw) > K_LDS_DEFAULT      # every non-big form takes cx_rows_fwd32_kernel
     fits = big_fwd_fits(N, C, hw)
     if fast:
         form = "fast"
@@ -87,7 +87,10 @@ def dispatch(N, C, hw, grad, weight):
         if not vec or hw % 64:
             bodies.add("non-FULL")                     # scalar loads, or a last tile that is partial
     chunks = C // 32
+    # the row minima: by atomicMin in cx_sim_kernel where cx_rows_fwd_big_kernel reads them (CxWs::sim_atomic_min), in the row pass's
+    # registers on every smaller map, in cx_sim_big_kernel on the value-only big form
     return dict(form=form, big=big, fast=fast, loss_in_rows=loss_in_rows, raised_lds=raised_lds, big_fwd_fits=fits,
+                sim_atomic_min=big and uses_sim,
                 loads="vector" if vec else "scalar", sim_bodies=bodies,
                 chunks="one" if chunks == 1 else ("odd" if chunks % 2 else "even"))
 
@@ -135,14 +138,15 @@ CASES = (
     Case("gen_hw65", "generic", (1, 32, 5, 13), "hw = 65: one column into the second tile; scalar loads", seed=0),
     Case("gen_hw120", "generic", (2, 64, 10, 12), "hw = 120: generic with vector loads (added: the issue's generic shapes are all scalar)",
          seed=2),
-    Case("gen_hw2047", "generic", (1, 32, 23, 89), "hw = 2047: largest small form, odd", seed=3),
+    Case("gen_hw2047", "generic", (1, 32, 23, 89), "hw = 2047: largest small form, odd; raised-limit launch of the row pass (131 008 B of LDS)",
+         seed=3),
     Case("big_hw2049", "big-gradient", (1, 32, 3, 683),
          "hw = 2049: second column chunk holds a single column; scalar loads; value only: 17 tiles of 128, one-column last tile, t8 = 3",
          seed=11, value_form="big-value"),
     Case("big_hw2112", "big-gradient", (1, 32, 33, 64), "hw = 2112: a multiple of 32, yet not the fast form; value only: 17 full tiles",
          seed=6, value_form="big-value"),
     Case("big_nofit_c864", "big-gradient", (1, 864, 3, 683),
-         "C = 864: smallest C at hw = 2049 for which big_fwd_fits is false -> value-only call falls back to the generic kernels",
+         "C = 864: smallest C at hw = 2049 for which big_fwd_fits is false -> value-only call falls back to cx_sim_kernel + cx_rows_fwd_big_kernel",
          seed=1, value_form="big-value-no-fit"),
     # variations
     Case("fast_bw0.1", "fast", (2, 32, 8, 8), "band width 0.1", seed=0, band_width=0.1),
@@ -150,7 +154,8 @@ CASES = (
     Case("gen_bw0.1", "generic", (2, 64, 7, 9), "band width 0.1", seed=0, band_width=0.1),
     Case("gen_bw1.0", "generic", (2, 64, 7, 9), "band width 1.0", seed=0, band_width=1.0),
     Case("fast_weighted", "fast", (2, 32, 8, 8), "weights: loss_in_rows off, cx_loss_kernel after cx_rows_fwd32_kernel", seed=0, weighted=True),
-    Case("gen_weighted", "generic", (2, 64, 7, 9), "weights on the generic form", seed=0, weighted=True),
+    Case("gen_weighted", "generic", (2, 64, 7, 9), "weights on the generic form (cx_loss_kernel after cx_rows_fwd32_kernel, as every generic case)",
+         seed=0, weighted=True),
     Case("big_weighted", "big-gradient", (2, 32, 3, 683), "weights on the big forms (N = 2: two different weights)", seed=9, weighted=True,
          value_form="big-value"),
 )

@@ -67,6 +67,14 @@ def test_every_dispatch_outcome_occurs():
     assert any(m == "value" for c, m, d in fast if not d["loss_in_rows"])
     assert any(m == "grad" and c.weighted for c, m, d in fast if not d["loss_in_rows"])
     assert {d["raised_lds"] for _, _, d in fast} == {True, False}
+    # the generic form takes the same row pass (cx_rows_fwd32_kernel): gen_hw2047 over the default LDS limit, the small ones under
+    generic = [(c, m, d) for c, m, d in runs if d["form"] == "generic"]
+    assert {c.name for c, m, d in generic if d["raised_lds"]} == {"gen_hw2047"}
+    assert {c.name for c, m, d in generic if not d["raised_lds"]} >= {"gen_hw2", "gen_hw63", "gen_hw65", "gen_hw120"}
+    assert not any(d["raised_lds"] for _, _, d in runs if d["big"])
+    assert not any(d["loss_in_rows"] for _, _, d in runs if not d["fast"])
+    # cx_sim_kernel issues the row minima's atomicMin exactly where cx_rows_fwd_big_kernel follows it
+    assert {d["form"] for _, _, d in runs if d["sim_atomic_min"]} == {"big-gradient", "big-value-no-fit"}
     for form in ("fast", "generic", "big-gradient"):                 # (the forms that run cx_sim_kernel on shapes of either kind)
         bodies = set().union(*[d["sim_bodies"] for _, _, d in runs if d["form"] == form])
         assert bodies == {"FULL", "non-FULL"}, (form, bodies)
@@ -91,6 +99,11 @@ def test_boundary_facts_by_arithmetic():
     hw = {c.name: c.hw for c in ALL}
     assert hw["fast_hw768"] == 768 and hw["fast_hw800"] == 800
     assert not R.dispatch(1, 64, 768, True, False)["raised_lds"] and R.dispatch(1, 32, 800, True, False)["raised_lds"]
+    # the same limit on the generic form: 767 under, 769 over; hw = 2047 needs 131 008 B, inside the limit the launch raises it to
+    # (the widest row of the pass, 16 * 64 * kCxMaxCols * 4)
+    assert not R.dispatch(1, 32, 767, True, False)["raised_lds"] and R.dispatch(1, 32, 769, True, False)["raised_lds"]
+    assert R.dispatch(1, 32, 2047, True, False)["raised_lds"] and not R.dispatch(1, 32, 2049, True, False)["raised_lds"]
+    assert R.rows_lds_bytes(2047) == 131008 <= R.CX_ROW_WAVES * 64 * R.CX_MAX_COLS * 4
     # the switch between the small and the big forms
     assert (hw["gen_hw2047"], hw["fast_hw2048"], hw["big_hw2049"], hw["big_hw2112"]) == (2047, 2048, 2049, 2112)
     assert [R.dispatch(1, 32, n, True, False)["form"] for n in (2047, 2048, 2049, 2112)] == ["generic", "fast", "big-gradient", "big-gradient"]
