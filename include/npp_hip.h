@@ -234,6 +234,40 @@ int npp_mlp_fwd32_view_ss(const npp_view* view, int ss, const npp_embed_cfg* cfg
  * sample not in view), sample_in_view (n ss^2 bytes, 0 / 1, may be null) and the per-pixel inside bytes (n, may be null). */
 int npp_grid_samples_host(const npp_grid* grid, int ss, float* out_yx);
 int npp_view_samples_host(const npp_view* view, int ss, int H, int W, float* out_yx, uint8_t* sample_in_view, uint8_t* inside);
+/* ---- adaptive supersampling: a class per canvas pixel of a view, and launches over listed pixels --------------------------------
+ * A view under perspective is coarse at its far end and fine near the camera, so one ss for the whole canvas pays the far end's
+ * price everywhere.  The class launch gives every canvas pixel the ss its own footprint asks for; the listed launch is the _view_ss
+ * launch over the pixels of one class.  Every pixel of the result is, bit for bit, what the uniform launch at that pixel's ss writes.
+ * The class rule, for canvas pixel (i, j) of an npp_view with a .. k = m[0 .. 8] converted fp32 -> float64:
+ *   class 0       iff the point launch's inside byte of the pixel centre is 0 (the fp32 rule of the _view forms, unchanged).
+ *   otherwise     in float64, every operation rounded separately (no contraction), no square root and no quotient:
+ *                   d    = |(g i + h j) + k|
+ *                   t    = (d d) d
+ *                   adet = |(a (e k - f h) - b (d1 k - f g)) + c (d1 h - e g)|,  d1 = m[3]: once per launch, on the host
+ *                 the class is the smallest S in {1, 2, 4, 8} with adet <= (2.25 S^2) t, else 8; the constants 2.25, 9, 36, 144 are
+ *                 exact and (2.25 S^2) t is one rounded product.
+ * This is the uniform rule (S = the next of 1, 2, 4, 8 at or above density / 1.5) on density = sqrt|det J| at the pixel centre, with
+ * |det J| = |det M| / |d|^3, rearranged so that NumPy, the host twin and the kernel agree byte for byte.
+ * npp_view_ss_classes: one thread per pixel of [start, start + n): d_cls (n bytes: 0, 1, 2, 4 or 8) and, unless null, d_inside (n
+ * bytes: the centre's inside byte for a fit of H x W).  _host: the same function in plain C++ on host memory.  NPP_ERR_ARG (with a
+ * message) for everything the _view forms refuse in a view, H or W < 1, a null d_cls with n > 0; n == 0 is a no-op. */
+int npp_view_ss_classes(const npp_view* view, int H, int W, uint8_t* d_cls, uint8_t* d_inside, void* stream);
+int npp_view_ss_classes_host(const npp_view* view, int H, int W, uint8_t* cls, uint8_t* inside);
+/* Listed launches: the _view_ss launch over a listed subset of the canvas window.  view->start, n, width name the window that d_out
+ * (n, 3) and d_inside (n, may be null) cover; d_pix holds n_list absolute row-major canvas pixel indices.
+ *   chain rows    row r of a launch is sample r % ss^2 of pixel d_pix[min(r / ss^2, n_list - 1)]: n_list ss^2 rows.
+ *   per pixel     positions, counting, ordered mean and inside byte are those of _view_ss for that pixel p, stored at
+ *                 d_out[(p - start) 3 + c] and d_inside[p - start].
+ *   ss = 1        a listed pixel gets the point launch's bits, colour and byte (the one sample is stored as it is: +0 + o would
+ *                 turn -0.0 into +0.0).
+ *   nothing else  no other word changes: unlisted pixels are not touched, and an index outside [start, start + n) is skipped by the
+ *                 kernel and stores nothing.  An index listed twice is written twice with the same bits.
+ * n_list == 0 (or n == 0) is a no-op.  NPP_ERR_ARG (with a message) for everything _view_ss refuses, for n_list < 0, for a null list
+ * with n_list > 0 and for n_list ss^2 rows beyond the 2^31 - 1 tiles of a launch. */
+int npp_mlp_fwd_view_list(const npp_view* view, int ss, const int64_t* d_pix, int64_t n_list, const npp_embed_cfg* cfg, int width,
+                          const void* d_wf, const float* d_params, float* d_out, uint8_t* d_inside, int out_act, void* stream);
+int npp_mlp_fwd32_view_list(const npp_view* view, int ss, const int64_t* d_pix, int64_t n_list, const npp_embed_cfg* cfg, int width,
+                            const void* d_w32, const float* d_params, float* d_out, uint8_t* d_inside, int out_act, void* stream);
 /* npp_mlp_fwd_act (inference) on fp32 positions: coords (Bp, 2) -> d_pred (Bp, 3), Bp a multiple of NPP_ROW_TILE. */
 int npp_mlp_fwd_coordf(const float* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_wf,
                        const float* d_params, float* d_pred, int out_act, void* stream);

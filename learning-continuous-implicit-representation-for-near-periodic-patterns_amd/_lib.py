@@ -146,6 +146,10 @@ SYMBOLS = {
     "npp_mlp_fwd32_view_ss": (_i32, [_viewp, _i32, _cfgp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "npp_grid_samples_host": (_i32, [_gridp, _i32, _vp]),
     "npp_view_samples_host": (_i32, [_viewp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "npp_view_ss_classes": (_i32, [_viewp, _i32, _i32, _vp, _vp, _vp]),
+    "npp_view_ss_classes_host": (_i32, [_viewp, _i32, _i32, _vp, _vp]),
+    "npp_mlp_fwd_view_list": (_i32, [_viewp, _i32, _vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "npp_mlp_fwd32_view_list": (_i32, [_viewp, _i32, _vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "npp_mlp_fwd_coordf": (_i32, [_vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _i32, _vp]),
     "npp_mlp_fwd32_coordf": (_i32, [_vp, _i64, _cfgp, _i32, _vp, _vp, _vp, _i32, _vp]),
     "npp_warp_fwd_coordf": (_i32, [_vp, _i64, _cfgp, _vp, _vp]),

@@ -2,7 +2,8 @@
 // how its colour leaves them (include/npp_hip.h "continuous coordinates"), with the host-side argument checks the entry points of
 // those kernels share.  A new coordinate mode is one
 // CoordMode value, one branch in row_coord and one in store_rgb, one entry point per chain and one table row in ops.render.  (The
-// supersampled modes also need the samples of a pixel together: average_rgb, behind a barrier after store_rgb.)
+// supersampled modes also need the samples of a pixel together: average_rgb, behind a barrier after store_rgb.  The listed mode is
+// the supersampled view over pixels named by an index list: the same three branches.)
 #pragma once
 #include "npp_common.h"
 
@@ -98,6 +99,9 @@ int check_view(const npp_view* v, const char* who);
 // What supersampling adds to a checked canvas (include/npp_hip.h "supersampled launches"): ss in {1, 2, 4, 8}; with ss > 1 indices
 // below 2^20 and n ss^2 rows within one launch
 int check_ss(int ss, int64_t start, int64_t n, int32_t width, const char* who);
+// What an index list adds to a checked supersampled view (include/npp_hip.h "listed launches"): n_list >= 0, a list where n_list > 0,
+// n_list ss^2 rows within one launch
+int check_list(int ss, const int64_t* pix, int64_t n_list, const char* who);
 
 // The checks every fused-forward entry point makes before it launches, in this order: network width (NPP_ERR_UNSUPPORTED), the row
 // count, null pointers, out_act (NPP_ERR_ARG).  canvas: `rows` is the pixel count n of a grid / view launch (already >= 0 by
@@ -124,8 +128,9 @@ static inline int fwd_entry_check(const char* who, const npp_embed_cfg* cfg, int
 // ---- coordinate intake of the render paths ------------------------------------------------------------------------------------
 // Coordinate modes of the forward kernels: how row r's (y, x) enters.  A template parameter: the int32 form compiles as before.
 // The SS modes are the grid and the view with ss x ss samples per canvas pixel, averaged in the store epilogue (src.ss > 1).
-enum CoordMode { kCoordI32 = 0, kCoordF32 = 1, kCoordGrid = 2, kCoordView = 3, kCoordGridSS = 4, kCoordViewSS = 5 };
-constexpr bool coord_is_ss(int cm) { return cm == kCoordGridSS || cm == kCoordViewSS; }
+// kCoordViewList is the view's SS mode over a listed subset of the canvas window (src.pix; src.ss may be 1 there).
+enum CoordMode { kCoordI32 = 0, kCoordF32 = 1, kCoordGrid = 2, kCoordView = 3, kCoordGridSS = 4, kCoordViewSS = 5, kCoordViewList = 6 };
+constexpr bool coord_is_ss(int cm) { return cm == kCoordGridSS || cm == kCoordViewSS || cm == kCoordViewList; }
 
 // What a view launch adds to the forward kernels' arguments (the other modes never read it)
 struct ViewArgs {
@@ -140,7 +145,9 @@ struct CoordSrc {
   const float* coordsf;
   npp_grid g;
   ViewArgs view;
-  int32_t ss;             // the SS modes: samples per canvas pixel in each direction (2, 4 or 8)
+  int32_t ss;             // the SS modes: samples per canvas pixel in each direction (2, 4 or 8; the listed mode also 1)
+  const int64_t* pix;     // the listed mode: n_list absolute row-major canvas pixel indices (include/npp_hip.h "listed launches")
+  int64_t n_list;
 };
 
 // One separately rounded fp32 operation: the _rn intrinsics on the device, the plain operator on the host (every source is compiled
@@ -219,12 +226,29 @@ __host__ __device__ __forceinline__ uint8_t view_sample(const npp_view& v, int H
   return view_at(v, H, W, fi, fj, y, x);
 }
 
+// ---- listed launches (include/npp_hip.h "listed launches") ---------------------------------------------------------------------
+// Pixel q of a listed launch: pix[min(q, n_list - 1)] as an offset into the window [v.start, v.start + v.n), or -1 where the index
+// lies outside it (such a pixel computes on the window's first pixel and stores nothing)
+__device__ __forceinline__ int64_t list_pixel(const CoordSrc& src, int64_t q) {
+  const int64_t w = src.pix[q < src.n_list ? q : src.n_list - 1] - src.view.v.start;
+  return w >= 0 && w < src.view.v.n ? w : -1;
+}
+// Row r of a listed launch: sample r % ss^2 of listed pixel r / ss^2 at view_sample's position (ss = 1: the pixel centre, off[0] = 0)
+__device__ __forceinline__ uint8_t list_sample(const CoordSrc& src, int64_t r, float& y, float& x) {
+  const int lg2 = 2 * __builtin_ctz((unsigned)src.ss);
+  const int64_t w = list_pixel(src, r >> lg2);
+  float fi, fj;
+  ss_canvas_pos(src.view.v.width, src.ss, src.view.v.start + (w < 0 ? 0 : w), 1, r & ((1 << lg2) - 1), fi, fj);
+  return view_at(src.view.v, src.view.H, src.view.W, fi, fj, y, x);
+}
+
 // (y, x) of row r in coordinate mode CM: int32 pixel indices (coords, (N, 2) [y, x]), fp32 positions (src.coordsf, the same shape),
 // the implicit grid or the view.  Returns the inside byte of the position: a view's (0: not in view, y = x = 0), 3 in every other mode.
 template <int CM>
 __device__ __forceinline__ uint8_t row_coord(const int32_t* coords, const CoordSrc& src, int64_t r, float& y, float& x) {
   if (CM == kCoordView) return view_row(src.view, r, y, x);
   if (CM == kCoordViewSS) return view_sample(src.view.v, src.view.H, src.view.W, src.ss, r, y, x);
+  if (CM == kCoordViewList) return list_sample(src, r, y, x);
   if (CM == kCoordGridSS) {
     grid_sample(src.g, src.ss, r, y, x);
   } else if (CM == kCoordGrid) {
@@ -256,6 +280,10 @@ __device__ __forceinline__ void store_rgb(const CoordSrc& src, float* pred, int6
       float y, x;
       ((uint32_t*)stage)[NPP_ROW_TILE * 3 + lr] = view_sample(src.view.v, src.view.H, src.view.W, src.ss, row, y, x) != 0;
     }
+    if (CM == kCoordViewList && c == 0) {
+      float y, x;
+      ((uint32_t*)stage)[NPP_ROW_TILE * 3 + lr] = list_sample(src, row, y, x) != 0;
+    }
   } else if (CM == kCoordView) {
     if (row < src.view.v.n) {
       float y, x;
@@ -270,28 +298,34 @@ __device__ __forceinline__ void store_rgb(const CoordSrc& src, float* pred, int6
 // forms channel c of the tile's pixel q -- acc = +0, then the ss^2 staged samples in order, one rounded add for each that counts (in a
 // grid all do), and an IEEE quotient by their number -- and stores it if the pixel is one of the launch's n.  A view's pixel keeps the
 // inside byte of its centre (view_coord, what the point launch writes); where that is 0 or no sample counts it stores zeros and byte 0.
+// The listed mode: pixel q of the tile is listed pixel row0 / ss^2 + q, stored at its place in the window (nothing for a surplus
+// pixel or an index outside the window); with ss = 1 the colour is the one staged sample itself, as the point launch stores it
+// (+0 + o would turn -0.0 into +0.0).
 template <int CM>
 __device__ __forceinline__ void average_rgb(const CoordSrc& src, float* pred, int64_t row0, int tid, const float* stage) {
   const int lg2 = 2 * __builtin_ctz((unsigned)src.ss);
   if (tid >= (NPP_ROW_TILE >> lg2) * 3) return;
   const int q = tid / 3, c = tid - q * 3;
-  const int64_t pix = (row0 >> lg2) + q;
-  if (pix >= (CM == kCoordViewSS ? src.view.v.n : src.g.n)) return;
+  int64_t pix = (row0 >> lg2) + q;
+  if (CM == kCoordViewList) {
+    if (pix >= src.n_list || (pix = list_pixel(src, pix)) < 0) return;
+  } else if (pix >= (CM == kCoordViewSS ? src.view.v.n : src.g.n)) return;
   const uint32_t* counts = (const uint32_t*)stage + NPP_ROW_TILE * 3;
   float acc = 0.0f;
   int cnt = 0;
   for (int s = 0; s < (1 << lg2); ++s) {
     const int lr = (q << lg2) + s;
-    if (CM == kCoordViewSS && !counts[lr]) continue;
+    if (CM != kCoordGridSS && !counts[lr]) continue;
     acc = __fadd_rn(acc, stage[lr * 3 + c]);
     ++cnt;
   }
   uint8_t in = 3;
-  if (CM == kCoordViewSS) {
+  if (CM != kCoordGridSS) {
     float y, x;
     in = cnt ? view_coord(src.view.v, src.view.H, src.view.W, src.view.v.start + pix, y, x) : 0;
     if (c == 0 && src.view.inside) src.view.inside[pix] = in;
   }
+  if (CM == kCoordViewList && lg2 == 0) acc = stage[q * 3 + c];          // (cnt is 1 wherever `in` is not 0)
   pred[pix * 3 + c] = in ? __fdiv_rn(acc, (float)cnt) : 0.0f;
 }
 

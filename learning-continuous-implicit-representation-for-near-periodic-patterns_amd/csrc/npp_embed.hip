@@ -97,6 +97,17 @@ int check_ss(int ss, int64_t start, int64_t n, int32_t width, const char* who) {
   return NPP_OK;
 }
 
+// What an index list adds to a view that check_view and check_ss passed (include/npp_hip.h "listed launches")
+int check_list(int ss, const int64_t* pix, int64_t n_list, const char* who) {
+  if (n_list < 0) { set_error("%s: n_list=%lld must be >= 0", who, (long long)n_list); return NPP_ERR_ARG; }
+  if (n_list > 0 && !pix) { set_error("%s: null pixel list with n_list=%lld", who, (long long)n_list); return NPP_ERR_ARG; }
+  if (n_list > (0x7fffffffLL * NPP_ROW_TILE) / (ss * ss)) {
+    set_error("%s: n_list=%lld x ss^2=%d rows are too many for one launch", who, (long long)n_list, ss * ss);
+    return NPP_ERR_ARG;
+  }
+  return NPP_OK;
+}
+
 #ifndef NPP_EMB_ROWS
 #define NPP_EMB_ROWS 32
 #endif

@@ -642,7 +642,8 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[NTW][kNB], char* out, int
 // CM: coordinate mode (npp_coord.h CoordMode) of the render paths -- fp32 positions (npp_mlp_fwd_coordf) or the implicit canvas
 // grid (npp_mlp_fwd_grid) or that canvas under a projective map (npp_mlp_fwd_view); all read the nonlinearity from A_.out_act like
 // ACT; the SS modes (npp_mlp_fwd_grid_ss / _view_ss) are the last two with ss x ss samples per canvas pixel, averaged behind the
-// output nonlinearity.  kCoordI32 is every other launch, unchanged.
+// output nonlinearity, and the listed mode (npp_mlp_fwd_view_list) is the view's SS mode over an index list.  kCoordI32 is every other
+// launch, unchanged.
 template <int TRAIN, bool MULTI, bool EMB_IN = false, bool STACK = false, bool ACT = false, int CM = kCoordI32>
 __global__ __launch_bounds__(kThreads, kWavesPerSimdF) void mlp_fwd_kernel(FwdArgs A_, EmbedDev e_arg, NetDesc d) {
   static_assert(CM == kCoordI32 || (TRAIN == 0 && !EMB_IN && !STACK), "the render coordinate modes are inference-only");
@@ -943,8 +944,8 @@ using namespace npp;
 
 // Every launched instantiation of mlp_fwd_kernel, as one selection over (kernel form, stash form T, K > 1).  The entry point names
 // the form; T: 0 no stash (inference), 1 the 16-bit training stash, 2 the 8-bit one (npp_tune "stash8").  The stacked form always
-// trains and the render forms never do, so only those T exist for them: 3 forms x 3 T + stacked x 2 T + 5 render forms, x 2 for K.
-enum FwdForm { kFwdPlain, kFwdEmbIn, kFwdStack, kFwdAct, kFwdCoordF, kFwdGrid, kFwdView, kFwdGridSS, kFwdViewSS };
+// trains and the render forms never do, so only those T exist for them: 3 forms x 3 T + stacked x 2 T + 6 render forms, x 2 for K.
+enum FwdForm { kFwdPlain, kFwdEmbIn, kFwdStack, kFwdAct, kFwdCoordF, kFwdGrid, kFwdView, kFwdGridSS, kFwdViewSS, kFwdViewList };
 struct FwdLaunch {
   const FwdArgs& A; const EmbedDev& e; const NetDesc& d;
   dim3 grid; hipStream_t stream; const char* who;
@@ -952,7 +953,7 @@ struct FwdLaunch {
   int go() const {
     constexpr bool EMB_IN = F == kFwdEmbIn, STACK = F == kFwdStack, ACT = F == kFwdAct;      // ACT: the output nonlinearity is read from the arguments
     constexpr int CM = F == kFwdCoordF ? kCoordF32 : F == kFwdGrid ? kCoordGrid : F == kFwdView ? kCoordView :
-                       F == kFwdGridSS ? kCoordGridSS : F == kFwdViewSS ? kCoordViewSS : kCoordI32;
+                       F == kFwdGridSS ? kCoordGridSS : F == kFwdViewSS ? kCoordViewSS : F == kFwdViewList ? kCoordViewList : kCoordI32;
     const dim3 block(kThreads);
     return d.K > 1 ? launch_lds<mlp_fwd_kernel<T, true, EMB_IN, STACK, ACT, CM>>(who, grid, block, kSmemFwd, kSmemFwd, stream, A, e, d)
                    : launch_lds<mlp_fwd_kernel<T, false, EMB_IN, STACK, ACT, CM>>(who, grid, block, kSmemFwd, kSmemFwd, stream, A, e, d);
@@ -969,7 +970,7 @@ static int fwd_launch(FwdForm f, const FwdArgs& A, const EmbedDev& e, const NetD
   if (f == kFwdAct) return T == 2 ? L.go<2, kFwdAct>() : T == 1 ? L.go<1, kFwdAct>() : L.go<0, kFwdAct>();
   if (f == kFwdPlain) return T == 2 ? L.go<2, kFwdPlain>() : T == 1 ? L.go<1, kFwdPlain>() : L.go<0, kFwdPlain>();
   return f == kFwdCoordF ? L.go<0, kFwdCoordF>() : f == kFwdGrid ? L.go<0, kFwdGrid>() : f == kFwdView ? L.go<0, kFwdView>() :
-         f == kFwdGridSS ? L.go<0, kFwdGridSS>() : L.go<0, kFwdViewSS>();
+         f == kFwdGridSS ? L.go<0, kFwdGridSS>() : f == kFwdViewSS ? L.go<0, kFwdViewSS>() : L.go<0, kFwdViewList>();
 }
 
 // The body of the entry points that launch on a coordinate tensor (d_actT: the training stash, null for a render)
@@ -1066,6 +1067,22 @@ extern "C" int npp_mlp_fwd_view_ss(const npp_view* view, int ss, const npp_embed
   CoordSrc src{};
   src.view.v = *view; src.view.inside = d_inside; src.view.H = cfg->H; src.view.W = cfg->W; src.ss = ss;
   return fwd_canvas(who, kFwdViewSS, view->n * ss * ss, src, cfg, d_wf, d_params, d_out, out_act, stream);
+}
+
+// npp_mlp_fwd_view_ss over the n_list listed pixels of the window (include/npp_hip.h "listed launches"): n_list ss^2 rows; ss = 1 too
+// runs the listed mode (its store keeps the point launch's bits)
+extern "C" int npp_mlp_fwd_view_list(const npp_view* view, int ss, const int64_t* d_pix, int64_t n_list, const npp_embed_cfg* cfg,
+                                     int width, const void* d_wf, const float* d_params, float* d_out, uint8_t* d_inside, int out_act,
+                                     void* stream) {
+  const char* who = "npp_mlp_fwd_view_list";
+  int rc = check_view(view, who);
+  if (rc || (rc = check_ss(ss, view->start, view->n, view->width, who)) || (rc = check_list(ss, d_pix, n_list, who)) ||
+      (rc = fwd_entry_check(who, cfg, width, view->n, true, nullptr, d_wf, d_params, d_out, out_act)) || view->n == 0 || n_list == 0)
+    return rc;
+  CoordSrc src{};
+  src.view.v = *view; src.view.inside = d_inside; src.view.H = cfg->H; src.view.W = cfg->W; src.ss = ss;
+  src.pix = d_pix; src.n_list = n_list;
+  return fwd_canvas(who, kFwdViewList, n_list * ss * ss, src, cfg, d_wf, d_params, d_out, out_act, stream);
 }
 
 // ---- stacked form: M images per launch (npp_common.h "stacked launches") ----------------------------------------------------

@@ -402,6 +402,22 @@ extern "C" int npp_mlp_fwd32_view_ss(const npp_view* view, int ss, const npp_emb
   return fwd32_launch<kCoordViewSS>(A, cfg, stream, who);
 }
 
+// npp_mlp_fwd32_view_ss over the n_list listed pixels of the window (include/npp_hip.h "listed launches"): n_list ss^2 rows; ss = 1 too
+// runs the listed mode (its store keeps the point launch's bits)
+extern "C" int npp_mlp_fwd32_view_list(const npp_view* view, int ss, const int64_t* d_pix, int64_t n_list, const npp_embed_cfg* cfg,
+                                       int width, const void* d_w32, const float* d_params, float* d_out, uint8_t* d_inside, int out_act,
+                                       void* stream) {
+  const char* who = "npp_mlp_fwd32_view_list";
+  int rc = check_view(view, who);
+  if (rc || (rc = check_ss(ss, view->start, view->n, view->width, who)) || (rc = check_list(ss, d_pix, n_list, who)) ||
+      (rc = fwd_entry_check(who, cfg, width, view->n, true, nullptr, d_w32, d_params, d_out, out_act)) || view->n == 0 || n_list == 0)
+    return rc;
+  Fwd32Args A = fwd32_args(n_list * ss * ss, d_w32, d_params, d_out, out_act);
+  A.src.view.v = *view; A.src.view.inside = d_inside; A.src.view.H = cfg->H; A.src.view.W = cfg->W; A.src.ss = ss;
+  A.src.pix = d_pix; A.src.n_list = n_list;
+  return fwd32_launch<kCoordViewList>(A, cfg, stream, who);
+}
+
 // The forward of the exact-fp32 fit: npp_mlp_fwd32 plus the stash (d_stash: sizes[1] of npp_train_workspace32)
 extern "C" int npp_mlp_fwd32_train(const int32_t* d_coords_yx, int64_t Bp, const npp_embed_cfg* cfg, int width, const void* d_w32,
                                    const float* d_params, float* d_pred, void* d_stash, int out_act, void* stream) {

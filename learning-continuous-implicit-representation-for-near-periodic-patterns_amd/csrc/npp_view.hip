@@ -166,6 +166,46 @@ __global__ __launch_bounds__(256) void warp_image_ss_kernel(const uint8_t* __res
   warp_pixel_ss(src, Hs, Ws, C, M, mode, ss, reduce, i, j, out + p * C, inside ? inside + p : nullptr);
 }
 
+// ---- the supersampling class of a view's canvas pixel (include/npp_hip.h "adaptive supersampling") ---------------------------------
+// |det M| of a view's fp32 matrix in float64, in the written order: formed once on the host by the entry points
+static double view_abs_det(const npp_view& v) {
+  const double a = v.m[0], b = v.m[1], c = v.m[2], d1 = v.m[3], e = v.m[4], f = v.m[5], g = v.m[6], h = v.m[7], k = v.m[8];
+  const double t0 = warp_mul(a, warp_sub(warp_mul(e, k), warp_mul(f, h)));
+  const double t1 = warp_mul(b, warp_sub(warp_mul(d1, k), warp_mul(f, g)));
+  const double t2 = warp_mul(c, warp_sub(warp_mul(d1, h), warp_mul(e, g)));
+  return fabs(warp_add(warp_sub(t0, t1), t2));
+}
+
+// Canvas pixel p (row-major): class 0 where the point launch's inside byte (returned in `in`) is 0; else the smallest S in {1, 2, 4, 8}
+// with adet <= (2.25 S^2) t, t = (d d) d, d = |(m6 i + m7 j) + m8| in float64, every operation rounded separately; 8 where none does.
+__host__ __device__ __forceinline__ uint8_t view_ss_class(const npp_view& v, int H, int W, double adet, int64_t p, uint8_t& in) {
+  float y, x;
+  in = view_coord(v, H, W, p, y, x);
+  if (!in) return 0;
+  const int64_t i = p / v.width;
+  const double fi = (double)i, fj = (double)(p - i * v.width);
+  const double d = fabs(warp_add(warp_add(warp_mul((double)v.m[6], fi), warp_mul((double)v.m[7], fj)), (double)v.m[8]));
+  const double t = warp_mul(warp_mul(d, d), d);
+  return adet <= warp_mul(2.25, t) ? 1 : adet <= warp_mul(9.0, t) ? 2 : adet <= warp_mul(36.0, t) ? 4 : 8;
+}
+
+__global__ __launch_bounds__(256) void view_ss_classes_kernel(npp_view v, int H, int W, double adet, uint8_t* __restrict__ cls,
+                                                              uint8_t* __restrict__ inside) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= v.n) return;
+  uint8_t in;
+  cls[r] = view_ss_class(v, H, W, adet, v.start + r, in);
+  if (inside) inside[r] = in;
+}
+
+static int classes_check(const char* who, const npp_view* view, int H, int W, const void* cls) {
+  const int rc = check_view(view, who);
+  if (rc) return rc;
+  if (H < 1 || W < 1) { set_error("%s: image size %d x %d must be >= 1", who, H, W); return NPP_ERR_ARG; }
+  if (view->n > 0 && !cls) { set_error("%s: null pointer", who); return NPP_ERR_ARG; }
+  return NPP_OK;
+}
+
 static int warp_check(const char* who, const void* src, int Hs, int Ws, int C, int Ho, int Wo, const double* m, int mode, const void* out) {
   if (!src || !out || src == out || !m) { set_error("%s: null pointer (the output needs an array of its own)", who); return NPP_ERR_ARG; }
   if (Hs < 1 || Ws < 1 || Ho < 1 || Wo < 1 || (int64_t)Hs * Ws >= ((int64_t)1 << 31) || (int64_t)Ho * Wo >= ((int64_t)1 << 31)) {
@@ -255,6 +295,29 @@ extern "C" int npp_view_coords_host(const npp_view* view, int H, int W, float* o
     const uint8_t in = view_coord(*view, H, W, view->start + r, y, x);
     out_yx[2 * r] = y;
     out_yx[2 * r + 1] = x;
+    if (inside) inside[r] = in;
+  }
+  return NPP_OK;
+}
+
+// The supersampling class (0, 1, 2, 4, 8) of canvas pixels [start, start + n), one thread per pixel, and the centre's inside byte
+extern "C" int npp_view_ss_classes(const npp_view* view, int H, int W, uint8_t* d_cls, uint8_t* d_inside, void* stream) {
+  const char* who = "npp_view_ss_classes";
+  const int rc = classes_check(who, view, H, W, d_cls);
+  if (rc || view->n == 0) return rc;
+  hipLaunchKernelGGL(view_ss_classes_kernel, dim3((unsigned)((view->n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *view, H, W,
+                     view_abs_det(*view), d_cls, d_inside);
+  return check_launch(who);
+}
+
+// ... and its host twin: the same function per pixel on host memory
+extern "C" int npp_view_ss_classes_host(const npp_view* view, int H, int W, uint8_t* cls, uint8_t* inside) {
+  const int rc = classes_check("npp_view_ss_classes_host", view, H, W, cls);
+  if (rc) return rc;
+  const double adet = view_abs_det(*view);
+  for (int64_t r = 0; r < view->n; ++r) {
+    uint8_t in;
+    cls[r] = view_ss_class(*view, H, W, adet, view->start + r, in);
     if (inside) inside[r] = in;
   }
   return NPP_OK;

@@ -255,13 +255,19 @@ class NPPNet:
         render() of the full int32 grid bit for bit; at an integer scale S, pixel (S i, S j) is pixel (i, j) of scale 1.
         supersample = S in (1, 2, 4, 8): every pixel is the mean of S x S samples spread evenly over its footprint (offsets
         (2 a + 1) / (2 S) - 0.5 of a pixel), averaged inside the launch -- antialiasing for a canvas coarser than the fit, at S^2
-        times the chain rows and no extra memory; chunk_rows keeps bounding the rows of a launch, and the result does not depend on it."""
+        times the chain rows and no extra memory; chunk_rows keeps bounding the rows of a launch, and the result does not depend on it.
+        supersample = "adaptive" is one S for the whole canvas, view.supersample_for_density(max(1 / sy, 1 / sx)), the choice of
+        `render --supersample auto`: a grid's density is the same at every pixel, so there is nothing to adapt (render_view is
+        where the classes differ)."""
         Hc, Wc, chunk = self._canvas(size, chunk_rows)
         o, s = _pair(origin), _pair(scale)
+        if isinstance(supersample, str) and supersample == "adaptive":
+            from . import view
+            supersample = view.supersample_for_density(max(1.0 / s[0], 1.0 / s[1]))
         return self._render(lambda s0, n: ops.grid_arg(s0, n, Wc, o, s), precision, Hc * Wc, chunk,
                             supersample=supersample).view(Hc, Wc, 3)
 
-    def render_view(self, size, M, precision="bf16", chunk_rows=1 << 22, return_inside=False, supersample=1):
+    def render_view(self, size, M, precision="bf16", chunk_rows=1 << 22, return_inside=False, supersample=1, return_classes=False):
         """render_grid under a projective map (view.py): pixel (i, j) of the size = (H', W') canvas is the network at
         ((m0 i + m1 j) + m2, (m3 i + m4 j) + m5) / ((m6 i + m7 j) + m8) of the fit's frame, M the row-major 3 x 3 map, converted to
         float32 once -> (H', W', 3) float32 on the device, and with return_inside also (H', W') uint8: 0 the pixel is not in view
@@ -269,14 +275,45 @@ class NPPNet:
         rectangle.  Chunked view launches, no coordinate buffer.  The affine map [[1/sy, 0, y0], [0, 1/sx, x0], [0, 0, 1]] with
         power-of-two scales is render_grid bit for bit.  A non-finite or singular M raises ValueError before any launch.
         supersample = S as in render_grid, the sample positions going through the map; a sample that is not in view does not count,
-        and the inside bytes stay those of the pixel centres (a pixel whose centre is not in view renders zero)."""
+        and the inside bytes stay those of the pixel centres (a pixel whose centre is not in view renders zero).
+        supersample = "adaptive": every pixel gets the S its own footprint asks for (the rule of "auto" at the pixel centre, exact:
+        include/npp_hip.h "adaptive supersampling") and is bit for bit the pixel of render_view(supersample=that S).  One class
+        launch over the canvas, then per class S the row-major list of its pixels in listed launches of at most
+        max(1, chunk_rows // S^2) pixels; an empty class launches nothing, a pixel not in view (class 0) is +0 with byte 0, and the
+        result does not depend on chunk_rows.  return_classes adds the (H', W') uint8 class map (0, 1, 2, 4, 8) as the last result
+        (of a uniform render: S where the pixel is in view)."""
         from . import view
         Hc, Wc, chunk = self._canvas(size, chunk_rows)
         m32 = view.check_matrix(M).astype(np.float32)
-        inside = torch.empty(Hc * Wc, dtype=torch.uint8, device=self.device) if return_inside else None
+        if isinstance(supersample, str) and supersample == "adaptive":
+            return self._render_view_adaptive(Hc, Wc, m32, precision, chunk, return_inside, return_classes)
+        inside = torch.empty(Hc * Wc, dtype=torch.uint8, device=self.device) if return_inside or return_classes else None
         out = self._render(lambda s0, n: ops.view_arg(s0, n, Wc, m32), precision, Hc * Wc, chunk, inside,
                            supersample=supersample).view(Hc, Wc, 3)
-        return (out, inside.view(Hc, Wc)) if return_inside else out
+        res = (out,) + ((inside.view(Hc, Wc),) if return_inside else ())
+        if return_classes:
+            res += ((inside.view(Hc, Wc) != 0).to(torch.uint8) * ops.check_supersample(supersample),)
+        return res if len(res) > 1 else out
+
+    def _render_view_adaptive(self, Hc, Wc, m32, precision, chunk_rows, return_inside, return_classes):
+        """render_view(supersample="adaptive") behind its argument checks."""
+        if precision not in ("bf16", "fp32"):
+            raise ValueError(f"precision {precision!r}: 'bf16' (fused chain) or 'fp32' (exact chain)")
+        total = Hc * Wc
+        whole = ops.view_arg(0, total, Wc, m32)
+        cls = torch.empty(total, dtype=torch.uint8, device=self.device)
+        ops.view_ss_classes(whole, (self.cfg.H, self.cfg.W), cls)
+        out = torch.zeros((total, 3), dtype=torch.float32, device=self.device)
+        inside = torch.zeros(total, dtype=torch.uint8, device=self.device)
+        pack = self._w32_pack() if precision == "fp32" else self._wf_pack()
+        for ss in ops.SUPERSAMPLES:
+            pix = torch.nonzero(cls == ss).view(-1)             # row-major; its length is read by the host here
+            chunk = max(1, chunk_rows // (ss * ss))
+            for s0 in range(0, int(pix.shape[0]), chunk):
+                ops.render(whole, self.cfg, pack, self.params, precision=precision, out=out, inside=inside, out_act=self.out_act,
+                           width=self.width, supersample=ss, pixels=pix[s0:s0 + chunk])
+        res = (out.view(Hc, Wc, 3),) + ((inside.view(Hc, Wc),) if return_inside else ()) + ((cls.view(Hc, Wc),) if return_classes else ())
+        return res if len(res) > 1 else res[0]
 
     # ---- model file (modelfile.py) ---------------------------------------------------------
     def embedder_config(self):

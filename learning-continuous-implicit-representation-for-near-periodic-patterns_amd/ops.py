@@ -378,7 +378,8 @@ _RENDER = {("int32", "bf16"): lambda L, *a: L.npp_mlp_fwd_act(*a), ("int32", "fp
            ("grid", "bf16"): lambda L, *a: L.npp_mlp_fwd_grid(*a), ("grid", "fp32"): lambda L, *a: L.npp_mlp_fwd32_grid(*a),
            ("view", "bf16"): lambda L, *a: L.npp_mlp_fwd_view(*a), ("view", "fp32"): lambda L, *a: L.npp_mlp_fwd32_view(*a),
            ("grid_ss", "bf16"): lambda L, *a: L.npp_mlp_fwd_grid_ss(*a), ("grid_ss", "fp32"): lambda L, *a: L.npp_mlp_fwd32_grid_ss(*a),
-           ("view_ss", "bf16"): lambda L, *a: L.npp_mlp_fwd_view_ss(*a), ("view_ss", "fp32"): lambda L, *a: L.npp_mlp_fwd32_view_ss(*a)}
+           ("view_ss", "bf16"): lambda L, *a: L.npp_mlp_fwd_view_ss(*a), ("view_ss", "fp32"): lambda L, *a: L.npp_mlp_fwd32_view_ss(*a),
+           ("view_list", "bf16"): lambda L, *a: L.npp_mlp_fwd_view_list(*a), ("view_list", "fp32"): lambda L, *a: L.npp_mlp_fwd32_view_list(*a)}
 SUPERSAMPLES = (1, 2, 4, 8)     # samples per canvas pixel and direction of a supersampled launch (include/npp_hip.h)
 
 
@@ -389,14 +390,17 @@ def check_supersample(supersample):
     return int(supersample)
 
 
-def render(src, cfg, pack, params, precision="bf16", out=None, inside=None, out_act=1, width=NPP_WIDTH, supersample=1):
+def render(src, cfg, pack, params, precision="bf16", out=None, inside=None, out_act=1, width=NPP_WIDTH, supersample=1, pixels=None):
     """The fused embedder + MLP render (no stash) of one coordinate source -> out (rows, 3) float32.  src: an int32 (Bp, 2) tensor of
     pixel indices or a float32 (Bp, 2) tensor of positions [y, x], Bp % 64 == 0 (out: (Bp, 3)); a grid_arg(...) or a view_arg(...):
     src.n canvas pixels -> out[:src.n], no coordinate buffer and no padding (out: at least (n, 3)).  precision: 'bf16' (the fused
     chain; pack = the wf pack) or 'fp32' (the exact chain; pack = the w32 pack).  inside (uint8, a view only, optional) receives
     the bytes 0 not in view (the row is zero) / 1 in view / 3 also inside the fit's image rectangle.  out_act: 1 sigmoid, 2 tanh, 0 raw.
     supersample (a grid or a view only): S in SUPERSAMPLES; every pixel is the ordered mean of S x S samples, formed inside the one
-    launch of n S^2 chain rows (include/npp_hip.h "supersampled launches"); 1 is the point-sampled launch."""
+    launch of n S^2 chain rows (include/npp_hip.h "supersampled launches"); 1 is the point-sampled launch.
+    pixels (a view only): an int64 tensor of absolute row-major canvas pixel indices; only those pixels of the window are computed
+    and stored, each with the bits of the supersample = S launch, and no other word of out / inside changes (include/npp_hip.h
+    "listed launches": len(pixels) S^2 chain rows; an index outside the window stores nothing)."""
     from ._lib import Grid, View
     ss = check_supersample(supersample)
     if precision not in ("bf16", "fp32"):
@@ -407,13 +411,20 @@ def render(src, cfg, pack, params, precision="bf16", out=None, inside=None, out_
     if ss != 1 and not canvas:
         raise ValueError(f"supersample={ss}: only a grid_arg(...) or a view_arg(...) is supersampled, not a tensor of positions "
                          "(place the samples yourself)")
+    if pixels is not None and not isinstance(src, View):
+        raise ValueError("pixels: only a view_arg(...) launch takes a pixel list, not a grid or a tensor of positions")
     if canvas:
         kind = "view" if isinstance(src, View) else "grid"
         out = _grid_out(out, src.n, params.device)
         head = (C.byref(src), C.byref(cfg), width, _p(pack), _p(params), _p(out))
-        if ss != 1:
+        if pixels is not None:
+            _req(pixels, torch.int64, "pixels")
+            if pixels.dim() != 1:
+                raise ValueError(f"pixels: expected a 1-d tensor of canvas pixel indices, got {tuple(pixels.shape)}")
+            kind, head = "view_list", (head[0], ss, _p(pixels), int(pixels.shape[0])) + head[1:]
+        elif ss != 1:
             kind, head = kind + "_ss", (head[0], ss) + head[1:]
-        tail = (_p(_view_inside(inside, src.n)),) if kind in ("view", "view_ss") else ()
+        tail = (_p(_view_inside(inside, src.n)),) if kind in ("view", "view_ss", "view_list") else ()
     else:
         if not (isinstance(src, torch.Tensor) and src.dtype in (torch.int32, torch.float32)):
             raise TypeError("src: expected an int32 or float32 (Bp, 2) tensor, a grid_arg(...) or a view_arg(...)")
@@ -436,6 +447,27 @@ def view_coords_host(view, res):
     check(lib().npp_view_coords_host(C.byref(view), int(res[0]), int(res[1]), C.c_void_p(yx.ctypes.data), C.c_void_p(inside.ctypes.data)),
           "npp_view_coords_host")
     return yx, inside
+
+
+def view_ss_classes(view, res, cls=None, inside=None):
+    """npp_view_ss_classes: the supersampling class (0 not in view, else 1, 2, 4 or 8 samples per direction) of each of the view's
+    n canvas pixels, one launch -> cls (uint8, at least (n,); made on the current device when neither tensor is given); inside (uint8, optional) receives the point launch's inside bytes for a
+    fit of res = (H, W).  The rule is exact (include/npp_hip.h "adaptive supersampling"): the host twin gives the same bytes."""
+    if cls is None:
+        cls = torch.empty(view.n, dtype=torch.uint8, device=inside.device if inside is not None else torch.device("cuda", torch.cuda.current_device()))
+    _view_inside(cls, view.n)
+    check(lib().npp_view_ss_classes(C.byref(view), int(res[0]), int(res[1]), _p(cls), _p(_view_inside(inside, view.n)), _stream()),
+          "npp_view_ss_classes")
+    return cls
+
+
+def view_ss_classes_host(view, res):
+    """npp_view_ss_classes_host: (classes (n,), inside bytes (n,)) of view_ss_classes as NumPy arrays, by plain C++ on the host."""
+    cls = np.zeros(view.n, np.uint8)
+    inside = np.zeros(view.n, np.uint8)
+    check(lib().npp_view_ss_classes_host(C.byref(view), int(res[0]), int(res[1]), C.c_void_p(cls.ctypes.data),
+                                         C.c_void_p(inside.ctypes.data)), "npp_view_ss_classes_host")
+    return cls, inside
 
 
 def grid_samples_host(grid, supersample):

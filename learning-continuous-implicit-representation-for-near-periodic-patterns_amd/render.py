@@ -19,7 +19,10 @@ is in view; --mask: only where that photo-frame mask is black, i.e. unknown); ev
 
 --supersample S (1, 2, 4, 8 or auto; default 1) renders every canvas pixel as the mean of S x S samples spread over its footprint,
 averaged inside the render launch: antialiasing for a canvas that is coarser than the fit (a --scale below 1, the far end of a
---view).  auto takes the smallest S that brings the coarsest spot down to view.MINIFY_WARN fit pixels per sample, at most 8."""
+--view).  auto takes the smallest S that brings the coarsest spot down to view.MINIFY_WARN fit pixels per sample, at most 8.
+adaptive applies that rule per canvas pixel of a --view (NPPNet.render_view supersample="adaptive": every pixel is the pixel of the
+uniform render at its own S, and the near field of a receding plane stops paying for the far end); the closing line names each
+class's share and the chain rows against auto.  Without --view a grid has one density, and adaptive is auto."""
 import argparse
 import math
 import os
@@ -39,7 +42,8 @@ def parse(argv=None):
     ap.add_argument("--npy", default=None, help="also write the (H, W, 3) float32 canvas as .npy")
     ap.add_argument("--chunk_rows", type=int, default=1 << 22, help="canvas pixels per launch (times S^2 samples: chain rows per launch)")
     ap.add_argument("--supersample", default=None, metavar="S",
-                    help="S x S samples per canvas pixel, averaged in the launch: 1, 2, 4, 8 or auto (default 1: point sampling)")
+                    help="S x S samples per canvas pixel, averaged in the launch: 1, 2, 4, 8, auto or adaptive (per pixel of a --view; "
+                         "default 1: point sampling)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--view", default=None, help="view.json of `python -m npp_amd.rectify`: render in the photograph's frame")
     ap.add_argument("--into", default=None, help="with --view: the photograph (PNG) to put the render into")
@@ -69,9 +73,9 @@ def parse(argv=None):
         ap.error(f"--chunk_rows {args.chunk_rows}: must be >= 1")
     args.scale = (sy, sx)
     args.supersample_given = args.supersample is not None        # the closing line names S only when the flag was given
-    if args.supersample != "auto":
+    if args.supersample not in ("auto", "adaptive"):
         if args.supersample not in (None, "1", "2", "4", "8"):
-            ap.error(f"--supersample {args.supersample}: must be 1, 2, 4, 8 or auto")
+            ap.error(f"--supersample {args.supersample}: must be 1, 2, 4, 8 or auto, or adaptive (a class per pixel of a --view)")
         args.supersample = int(args.supersample or 1)
     return args, ap
 
@@ -104,7 +108,7 @@ def main(argv=None):
     from . import io as nio
     from .model import NPPNet
     net = NPPNet.load(args.model, device=args.device)
-    ss = auto_supersample((sy, sx)) if args.supersample == "auto" else args.supersample
+    ss = auto_supersample((sy, sx)) if args.supersample in ("auto", "adaptive") else args.supersample
     img = net.render_grid(size, origin=tuple(args.origin), scale=(sy, sx), precision=args.precision, chunk_rows=args.chunk_rows,
                           supersample=ss)
     img = img.cpu().numpy()
@@ -119,7 +123,10 @@ def main(argv=None):
 
 def _ss_note(args, ss):
     """What the closing line says about supersampling: nothing unless the flag was given."""
-    return f", {ss} x {ss} samples per pixel" + (" (auto)" if args.supersample == "auto" else "") if args.supersample_given else ""
+    if not args.supersample_given:
+        return ""
+    how = {"auto": " (auto)", "adaptive": " (adaptive: a grid has one density, so this is auto)"}.get(args.supersample, "")
+    return f", {ss} x {ss} samples per pixel" + how
 
 
 def _main_view(args, ap, res):
@@ -141,14 +148,15 @@ def _main_view(args, ap, res):
     for flag, a in (("--into", photo), ("--mask", mask)):
         if a is not None and tuple(a.shape[:2]) != tuple(size):
             ap.error(f"{flag}: {a.shape[0]} x {a.shape[1]}, the view's photograph is {size[0]} x {size[1]}")
+    adaptive = args.supersample == "adaptive"
     ss = view.supersample_for(v["photo_to_rect"], size) if args.supersample == "auto" else args.supersample
     print(view.density_report(v["photo_to_rect"], size, "sampling density of the photograph on the fit's plane", ss))
 
     from . import io as nio
     from .model import NPPNet
     net = NPPNet.load(args.model, device=args.device)
-    img, inside = net.render_view(size, v["photo_to_rect"], precision=args.precision, chunk_rows=args.chunk_rows, return_inside=True,
-                                  supersample=ss)
+    img, inside, *classes = net.render_view(size, v["photo_to_rect"], precision=args.precision, chunk_rows=args.chunk_rows,
+                                            return_inside=True, supersample=ss, return_classes=adaptive)
     if photo is not None:
         from PIL import Image
         Image.fromarray(view.composite(photo, img, inside, mask=mask, beyond=args.beyond).cpu().numpy()).save(args.out)
@@ -159,7 +167,8 @@ def _main_view(args, ap, res):
         np.save(args.npy, img)
     n_in, n_fit = int((inside != 0).sum()), int((inside == 3).sum())
     print(f"rendered {size[0]} x {size[1]} ({args.precision}) under {args.view}: {n_in} pixels in view, {n_fit} inside the "
-          f"{res[0]} x {res[1]} fit" + _ss_note(args, ss) + (f", put into {args.into}" if args.into else "") + f" -> {args.out}")
+          f"{res[0]} x {res[1]} fit" + (", " + view.adaptive_note(classes[0].cpu().numpy(), auto=view.supersample_for(v["photo_to_rect"], size))
+                                        if adaptive else _ss_note(args, ss)) + (f", put into {args.into}" if args.into else "") + f" -> {args.out}")
     return img
 
 

@@ -151,11 +151,43 @@ def supersample_for(M, size):
     return supersample_for_density(sampling_density(M, size)[1])
 
 
+def supersample_classes(M, size, res=(1, 1)):
+    """The (H', W') uint8 map of render_view(supersample="adaptive"): per pixel of the size = (H', W') canvas 0 where it is not in
+    view, else supersample_for_density of sqrt|det J| at the pixel centre -- the exact rule of include/npp_hip.h "adaptive
+    supersampling" on M stored as float32, by the library's host twin (the device launch gives the same bytes).  res = (H, W) of the
+    fit: it does not enter the classes (only inside byte 3, which this does not return)."""
+    from . import ops
+    Hc, Wc = _size(size)
+    return ops.view_ss_classes_host(ops.view_arg(0, Hc * Wc, Wc, check_matrix(M)), res)[0].reshape(Hc, Wc)
+
+
+def class_rows(classes, auto=None):
+    """Of a class map -> (shares, rows, ratio, top): {S: share of the in-view pixels with class S}, the chain rows of the adaptive
+    render, their ratio to the rows of the uniform render of the whole canvas at S = top, and top itself: `auto`, or by default the
+    largest class present (1 for a canvas with nothing in view)."""
+    c = np.asarray(classes).reshape(-1)
+    counts = {S: int((c == S).sum()) for S in SUPERSAMPLES}
+    n_in = sum(counts.values())
+    top = auto if auto is not None else max([S for S in SUPERSAMPLES if counts[S]], default=1)
+    rows = sum(S * S * k for S, k in counts.items())
+    return {S: (counts[S] / n_in if n_in else 0.0) for S in SUPERSAMPLES}, rows, rows / (c.size * top * top), top
+
+
+def adaptive_note(classes, auto=None):
+    """What the commands say about an adaptive render: each class's share of the in-view pixels and the chain rows against uniform."""
+    shares, rows, ratio, top = class_rows(classes, auto)
+    return ("adaptive samples per pixel: " + ", ".join(f"{S} x {S} on {100 * shares[S]:.1f} %" for S in SUPERSAMPLES) +
+            f" of the pixels in view; {rows} chain rows, {ratio:.3f} of uniform {top} x {top}")
+
+
 def density_report(M, size, what, supersample=1):
     """One line for the commands: the density range, with a warning when the view minifies by more than MINIFY_WARN per sample
-    (supersample = S: S x S samples per canvas pixel, named in the line when S > 1)."""
+    (supersample = S: S x S samples per canvas pixel, named in the line when S > 1; "adaptive": each class's share of the in-view
+    pixels and the chain rows against uniform `auto`, from supersample_classes)."""
     lo, hi = sampling_density(M, size)
     line = f"{what}: {lo:.3f} .. {hi:.3f} target pixels per canvas pixel"
+    if isinstance(supersample, str) and supersample == "adaptive":
+        return line + "; " + adaptive_note(supersample_classes(M, size), auto=supersample_for(M, size))
     if supersample == 1:
         if hi > MINIFY_WARN:
             line += f"  WARNING: minifies by more than {MINIFY_WARN} -- point sampling aliases there (no antialiasing)"
