@@ -1,7 +1,11 @@
 // npp_chain32.h -- the building blocks of the fused exact-fp32 chains (v_mfma_f32_32x32x2_f32): weight fragments streamed from a
-// packed fp32 buffer (16 bytes = four k-steps of one lane), activations as the B operand from an LDS region [feature][64 rows].
-// Shared by npp_mlp_fwd32.hip (the coordinate MLP's full-image render, BASELINE c4) and npp_light.hip (NPP_Net_light's training
-// chains).  Layout of a packed layer: unit u (16 bytes) = [k-step group g][neuron tile nt][lane]; a group is four
+// packed fp32 buffer (16 bytes = four k-steps of one lane), activations as the B operand from an LDS region [feature][NB * 32 rows].
+// Shared by npp_mlp_fwd32.hip (the coordinate MLP's render and the forward of the exact-fp32 fit, BASELINE c4), npp_mlp_train32.hip
+// (that fit's backward chain) and npp_light.hip (NPP_Net_light's training chains).  Holds the contraction (wg32_load,
+// ActSrc32, part32), bias32 / zero32, snake_deriv32 and the stash-less forward epilogue epi32, all for NB batch tiles of 32 rows per
+// workgroup.  The stashing epilogues, the backward epilogues and the two heads stay with their kernels: the fit and the light chains
+// spell their addresses differently, and neither spelling suits both (profiles/chain32_resource_usage.txt).
+// Layout of a packed layer: unit u (16 bytes) = [k-step group g][neuron tile nt][lane]; a group is four
 // k-steps, k-step 4 g + e contracts input features (8 g + e, 8 g + e + 4) -- lane half h holds feature 8 g + e + 4 h.
 #pragma once
 #include "npp_common.h"
@@ -78,22 +82,31 @@ __device__ __forceinline__ void bias32(f32x16 (&acc)[NTW][NB], const float* __re
     }
 }
 
-// snake (or nothing) + store as the next layer's input: region[feature][row]
-template <bool SNAKE, int NTW>
-__device__ __forceinline__ void epi32(f32x16 (&acc)[NTW][kNB], char* region, int nt0, int b, int h) {
+template <int NTW, int NB>
+__device__ __forceinline__ void zero32(f32x16 (&acc)[NTW][NB]) {
 #pragma unroll
   for (int nt = 0; nt < NTW; ++nt)
 #pragma unroll
-    for (int bt = 0; bt < kNB; ++bt)
+    for (int bt = 0; bt < NB; ++bt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[nt][bt][r] = 0.0f;
+}
+
+__device__ __forceinline__ float snake_deriv32(float z) { return 1.0f + __builtin_amdgcn_sinf(z * (2.0f * kInv2Pi)); }   // activations.py:29-35: 1 + sin 2z
+
+// snake (or nothing) + store as the next layer's input: region[feature][NB * 32 rows]
+template <bool SNAKE, int NTW, int NB>
+__device__ __forceinline__ void epi32(f32x16 (&acc)[NTW][NB], char* region, int nt0, int b, int h) {
+#pragma unroll
+  for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+    for (int bt = 0; bt < NB; ++bt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         float z = acc[nt][bt][r];
-        if (SNAKE) {
-          const float s = __builtin_amdgcn_sinf(z * kInv2Pi);
-          z = fmaf(s, s, z);
-        }
+        if (SNAKE) z = snake_fast(z);
         acc[nt][bt][r] = z;
-        if (region) *(float*)(region + (((nt0 + nt) * 32 + acc_row(r, h)) * kRowTile + bt * 32 + b) * 4) = z;
+        if (region) *(float*)(region + (((nt0 + nt) * 32 + acc_row(r, h)) * (NB * 32) + bt * 32 + b) * 4) = z;
       }
 }
 

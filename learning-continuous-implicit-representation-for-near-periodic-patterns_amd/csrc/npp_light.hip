@@ -271,7 +271,7 @@ __device__ __forceinline__ void light_bepi(f32x16 (&acc)[2][NB], char* region, c
       for (int r = 0; r < 16; ++r) {
         const uint32_t gi = g + (uint32_t)((r & 3) + 8 * (r >> 2)) * B;
         float d = acc[nt][bt][r];
-        if (DERIV) d *= 1.0f + __builtin_amdgcn_sinf((PRE ? zpre[nt][bt][r] : zT[gi]) * (2.0f * kInv2Pi));      // activations.py:29-35: 1 + sin 2z
+        if (DERIV) d *= snake_deriv32(PRE ? zpre[nt][bt][r] : zT[gi]);
         dT[gi] = d;
         if (region) *(float*)(rg + ((r & 3) + 8 * (r >> 2)) * (NB * 32) * 4) = d;
       }
@@ -288,16 +288,6 @@ __device__ __forceinline__ void light_zfetch(f32x16 (&zpre)[2][NB], const float*
       for (int r = 0; r < 16; ++r) zpre[nt][bt][r] = zT[g + (uint32_t)((r & 3) + 8 * (r >> 2)) * B];
     }
 }
-template <int NB>
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][NB]) {
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int bt = 0; bt < NB; ++bt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[nt][bt][r] = 0.0f;
-}
-
 template <int NB>
 __global__ __launch_bounds__(kLThreads, NB == 2 ? 2 : 3) void light_bwd_kernel(LightArgs a, LightPackDesc pd) {
   constexpr int RT = NB * 32;
@@ -331,7 +321,7 @@ __global__ __launch_bounds__(kLThreads, NB == 2 ? 2 : 3) void light_bwd_kernel(L
       d = fmaf(sD[row * 3 + 1], Wr[ldr + k], d);
       d = fmaf(sD[row * 3 + 2], Wr[2 * ldr + k], d);
       const int64_t g = (int64_t)k * B + row0 + row;
-      d *= 1.0f + __builtin_amdgcn_sinf(zp[g] * (2.0f * kInv2Pi));
+      d *= snake_deriv32(zp[g]);
       dzp[g] = d;
       Rf[k * RT + row] = d;
     }
@@ -341,7 +331,7 @@ __global__ __launch_bounds__(kLThreads, NB == 2 ? 2 : 3) void light_bwd_kernel(L
   const ActSrc32 act{R + ((4 * h) * RT + b) * 4};
   f32x16 acc[2][NB];
   // d f1 = W_pos[:, :256]^T d z_p   (feature_linear1 is linear: this IS its d z; x_pos gets no gradient)
-  zero_acc(acc);
+  zero32(acc);
   part32<2, 8>(acc, rsrc, (uint32_t)pd.b_off[LB_POS], pd.b_groups[LB_POS], nt0, lane, act);
   wg_barrier();
   f32x16 zpre[2][NB];
@@ -351,7 +341,7 @@ __global__ __launch_bounds__(kLThreads, NB == 2 ? 2 : 3) void light_bwd_kernel(L
 #pragma unroll 1
   for (int j = 0; j < 4; ++j) {
     const int l = 3 - j;                        // hidden layer whose d z this step produces
-    zero_acc(acc);
+    zero32(acc);
     constexpr bool kPre = NB == 1;
     if (kPre) light_zfetch(zpre, S + (int64_t)(LS_Z0 + 256 * l) * B, (uint32_t)B, (uint32_t)row0, nt0, b, h);
     part32<2, 8>(acc, rsrc, (uint32_t)pd.b_off[LB_F1 + j], pd.b_groups[LB_F1 + j], nt0, lane, act);

@@ -33,10 +33,10 @@ struct Bwd32Args {
   int32_t out_act;
 };
 
-__device__ __forceinline__ float snake_deriv32(float z) { return 1.0f + __builtin_amdgcn_sinf(z * (2.0f * kInv2Pi)); }   // activations.py:29-35: 1 + sin 2z
-
 // epilogue of a data-gradient step: d h (acc) -> d z = d h * snake'(z) (z from the stash; DERIV false: d z = d h) -> gradient rows
-// drow0 + feature (+ the region, the next step's B operand)
+// drow0 + feature (+ the region, the next step's B operand).  Not merged with npp_light.hip's light_bepi: the two spell the
+// region address differently, light_bwd_kernel<1> spills in this spelling and this kernel ran 1.8 % slower at K = 3 in that one,
+// with 6 % fewer instructions (profiles/chain32_resource_usage.txt)
 template <bool DERIV>
 __device__ __forceinline__ void bepi32(f32x16 (&acc)[2][kNB], char* region, const float* __restrict__ zT, float* __restrict__ dT, int64_t Bp,
                                        int64_t row0, int nt0, int b, int h) {
@@ -55,14 +55,6 @@ __device__ __forceinline__ void bepi32(f32x16 (&acc)[2][kNB], char* region, cons
         if (region) *(float*)(region + ((f0 + fo) * kRowTile + bt * 32 + b) * 4) = dv;
       }
     }
-}
-__device__ __forceinline__ void zero32(f32x16 (&acc)[2][kNB]) {
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int bt = 0; bt < kNB; ++bt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[nt][bt][r] = 0.0f;
 }
 
 template <bool MULTI>
